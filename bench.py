@@ -5,6 +5,8 @@
     N > 1: one rank per GPU over RCCL.  Started by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the
     environment) it is one of the ranks; started from a plain shell it launches the N ranks itself (torch.distributed.run on
     127.0.0.1, a free port) and passes rank 0's JSON line through.  Fewer than N visible devices: one line on stderr, exit 2.
+    --dump-outputs DIR: rank 0 writes the result arrays of the last timed step to DIR/<name>.npy (dump_outputs); the inputs are
+    seeded, so two builds run with the same arguments can be compared array for array.
 
 metric  "I/Q Msamples/s end-to-end (demod->FEC->MBE) per GPU; % HBM roofline"
 step    BASELINE configs[2] with the vocoder on: B = 4096 P25 Phase 1 channels per GPU x n = 48000 complex cu8 samples (1 s
@@ -444,6 +446,118 @@ def front_end_stage(torch, ddn, chain, d_iq, B, n, steps):
     return out_d
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+# --dump-outputs writes three tiers of arrays, each over a fixed, seeded sample of the batch's channels (the whole batch when it is
+# no larger than the tier's channel cap): per-channel counts, per-frame-slot words (within DUMP_FRAME_BYTES), and the bulky
+# per-channel payloads (within what is left of DUMP_LIMIT_BYTES)
+DUMP_COUNT_CHANNELS, DUMP_FRAME_CHANNELS, DUMP_PAYLOAD_CHANNELS = 65536, 4096, 64
+DUMP_FRAME_BYTES = 16 << 20
+DUMP_COUNTS = ("counts", "new", "n_syncs", "dropped_syncs", "n_events", "n_ldu", "n_pdu")
+
+
+def dump_plan(chain, np):
+    """-> the channel samples of the three tiers and the bytes they will take; made before the timed steps, so that a shape
+    whose dump cannot fit DUMP_LIMIT_BYTES stops the run before it is measured rather than after"""
+    B, F, V, E = chain.B, chain.F, chain.Fv * 9, chain.E
+    stride = int(chain.stride)
+    per_count = 8 * (len(DUMP_COUNTS) + 1)                                  # float64 each, + the sample index
+    per_frame = 8 * F * 4 + 8 * F + 4 * 3 * F + 8                           # nid4, sync_pos, tsbk_crc, sample index
+    per_payload = (4 * stride * 10 + 4 * stride + 2 * 8 * E * 4 + 4 * 3 * F * 12            # records10, flags, events x2, tsbk
+                   + 4 * F * (2 * 240 + 12 * 6 + 16 * 6 + 2) + 4 * F * (32 + 2)           # LDU words / RS data / status, LSD
+                   + 4 * F * (120 + 1) + 4 * F * (72 + 1)                                  # HDU, TDULC
+                   + 4 * V * 88 + 2 * 8 * V * 5 + 4 * V * 160 + 8)                          # voice bits, result words x2, PCM, index
+    n_count = min(B, DUMP_COUNT_CHANNELS)
+    n_frame = min(B, DUMP_FRAME_CHANNELS, DUMP_FRAME_BYTES // per_frame)
+    left = DUMP_LIMIT_BYTES - n_count * per_count - n_frame * per_frame
+    n_payload = min(B, DUMP_PAYLOAD_CHANNELS, max(left, 0) // per_payload)
+    if min(n_frame, n_payload) < 1:
+        raise SystemExit("--dump-outputs: one channel's outputs at this shape do not fit %d bytes" % DUMP_LIMIT_BYTES)
+
+    def sample(n, seed):
+        return np.arange(B) if n >= B else np.sort(np.random.default_rng(seed).choice(B, n, replace=False))
+
+    return {"count": sample(n_count, 2), "frame": sample(n_frame, 1), "payload": sample(n_payload, 0),
+            "bytes": n_count * per_count + n_frame * per_frame + n_payload * per_payload}
+
+
+def dump_outputs(chain, np, out_dir, plan):
+    """--dump-outputs DIR: the result arrays of the chain's most recent call (the last timed step), as a caller of
+    ddn_p25_chain_run_pipelined receives them, to DIR/<name>.npy in float32 / float64 (integer outputs as float64, byte outputs as
+    float32, both exact).  The channels of each tier are in DIR/{count,frame,payload}_channels.npy (dump_plan): per-channel counts;
+    the per-frame NID / sync / CRC words; records, handler decisions, TSDU blocks, LDU / HDU / TDULC / LSD payloads, voice bits,
+    result words and PCM.  Entries the call did not write (records beyond a row's count, frame slots beyond a channel's syncs or of
+    another frame type, voice frames beyond its LDUs) are zeroed, so that stale buffer contents never differ."""
+    B, F, Fv, E = chain.B, chain.F, chain.Fv, chain.E
+    S, V = B * F, Fv * 9
+    r = chain.results()
+    stride = int(r.stride_symbols)
+
+    def rows(ptr, dt, row_shape, sel, base=0):
+        # rows[c] of an array laid out [B][row_shape] (base: elements in front of row 0)
+        n = int(np.prod(row_shape))
+        isz = np.dtype(dt).itemsize
+        return np.stack([chain.fetch(ptr + (base + int(c) * n) * isz, dt, row_shape) for c in sel])
+
+    out = {}
+    full = {name: chain.fetch(getattr(r, "d_" + name), np.int32, (B,)) for name in DUMP_COUNTS}
+    sel = plan["count"]
+    out["count_channels"] = sel.astype(np.float64)
+    for name in DUMP_COUNTS:
+        out[name] = full[name][sel].astype(np.float64)
+
+    sel = plan["frame"]
+    out["frame_channels"] = sel.astype(np.float64)
+    used = np.arange(F)[None, :] < full["n_syncs"][sel][:, None]                         # [C][F]
+    out["nid4"] = (rows(r.d_nid4, np.int32, (F, 4), sel) * used[:, :, None]).astype(np.float64)
+    out["sync_pos"] = (rows(r.d_sync_pos, np.int32, (F,), sel) * used).astype(np.float64)
+    out["tsbk_crc"] = (np.stack([rows(r.d_tsbk_crc, np.uint8, (F,), sel, base=i * S) for i in range(3)])
+                       * used[None]).astype(np.float32)
+
+    sel = plan["payload"]
+    out["payload_channels"] = sel.astype(np.float64)
+    u = np.arange(F)[None, :] < full["n_syncs"][sel][:, None]
+    nid4 = rows(r.d_nid4, np.int32, (F, 4), sel)
+    cnt, ok, duid = full["counts"][sel], u & (nid4[:, :, 0] > 0), nid4[:, :, 2]          # [C] / [C][F]
+    rec_live = np.arange(stride)[None, :] < cnt[:, None]
+    out["records10"] = (rows(r.d_records10, np.uint8, (stride, 10), sel) * rec_live[:, :, None]).astype(np.float32)
+    out["flags"] = (rows(r.d_flags, np.uint8, (stride,), sel) * rec_live).astype(np.float32)
+    ev_live = (np.arange(E)[None, :] < full["n_events"][sel][:, None])[:, :, None]
+    out["events"] = (rows(r.d_events, np.int32, (E, 4), sel) * ev_live).astype(np.float64)
+    out["event_data"] = (rows(r.d_event_data, np.int32, (E, 4), sel) * ev_live).astype(np.float64)
+    out["tsbk"] = (np.stack([rows(r.d_tsbk, np.uint8, (F, 12), sel, base=i * S * 12) for i in range(3)])
+                   * u[None, :, :, None]).astype(np.float32)
+    for i, (tag, d) in enumerate((("ldu1", 5), ("ldu2", 10))):
+        m = ok & (duid == d)
+        out[tag + "_words"] = (rows(r.d_ldu_words[i], np.uint8, (F, 24, 10), sel) * m[:, :, None, None]).astype(np.float32)
+        out[tag + "_rs_data"] = (rows(r.d_ldu_rs_data[i], np.uint8, (F, 12 + 4 * i, 6), sel) * m[:, :, None, None]).astype(np.float32)
+        out[tag + "_rs_status"] = (rows(r.d_ldu_rs_status[i], np.uint8, (F,), sel) * m).astype(np.float32)
+    m = ok & ((duid == 5) | (duid == 10))
+    out["lsd_bits"] = (rows(r.d_lsd_bits, np.uint8, (F, 2, 16), sel) * m[:, :, None, None]).astype(np.float32)
+    out["lsd_ok"] = (rows(r.d_lsd_ok, np.uint8, (F, 2), sel) * m[:, :, None]).astype(np.float32)
+    m = ok & (duid == 0)
+    out["hdu_rs_data"] = (rows(r.d_hdu_rs_data, np.uint8, (F, 20, 6), sel) * m[:, :, None, None]).astype(np.float32)
+    out["hdu_rs_status"] = (rows(r.d_hdu_rs_status, np.uint8, (F,), sel) * m).astype(np.float32)
+    m = ok & (duid == 15)
+    out["tdulc_rs_data"] = (rows(r.d_tdulc_rs_data, np.uint8, (F, 12, 6), sel) * m[:, :, None, None]).astype(np.float32)
+    out["tdulc_rs_status"] = (rows(r.d_tdulc_rs_status, np.uint8, (F,), sel) * m).astype(np.float32)
+    v_live = np.arange(V)[None, :] < 9 * full["n_ldu"][sel][:, None]                     # [C][V]
+    out["imbe_bits"] = (rows(r.d_imbe_bits, np.uint8, (V, 88), sel) * v_live[:, :, None]).astype(np.float32)
+    imbe_res = rows(r.d_imbe_result, np.int32, (V, 5), sel) * v_live[:, :, None]
+    out["imbe_result"] = imbe_res.astype(np.float64)
+    out["synth_result"] = (rows(r.d_synth_result, np.int32, (V, 5), sel) * v_live[:, :, None]).astype(np.float64)
+    synth = v_live & ((imbe_res[:, :, 0].view(np.uint32) & 0x80000000) == 0)
+    out["pcm"] = rows(r.d_pcm, np.float32, (V, 160), sel) * synth[:, :, None]
+
+    total = sum(a.nbytes for a in out.values())
+    assert total == plan["bytes"] <= DUMP_LIMIT_BYTES, (total, plan["bytes"])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "arrays": len(out), "bytes": int(total),
+            "channels": {k: int(len(plan[k])) for k in ("count", "frame", "payload")}}
+
+
 def self_launch(args, argv):
     """--gpus N from a plain shell: start the N ranks (one per GPU) and hand their output through"""
     import socket
@@ -525,7 +639,13 @@ def main():
                     "FEC / vocoder stages of step k with the front end / receive loop of step k + 1)")
     ap.add_argument("--dry-run-cpu", action="store_true", help="test mode, never a measurement: gloo between the ranks and the CPU "
                     "oracle as compute (the launch / sharding / reporting logic without GPUs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the result arrays of the "
+                    "last timed step to DIR/<name>.npy (float32 / float64; per-channel payloads of a fixed, seeded channel sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.dry_run_cpu:
+        ap.error("--dump-outputs writes the GPU chain's outputs; --dry-run-cpu has none")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args, sys.argv[1:]))
@@ -592,6 +712,7 @@ def main():
         def step():
             chain.run_pipelined(iq_ptr)
 
+    plan = dump_plan(chain, np) if args.dump_outputs and rank == 0 else None
     parity = parity_gate(chain, iq_ptr, voice, ctrl, ch_first, B, n)
     if not parity["bit_exact"] and not os.environ.get("DDN_BENCH_NOPARITY"):
         raise SystemExit("parity gate failed: %s" % json.dumps(parity))
@@ -612,6 +733,9 @@ def main():
     l.ddn_p25_rx_get_timing_avg(chain.rx, rx_timed.ctypes.data, C.byref(rx_timed_n))
     l.ddn_p25_rx_set_timing(chain.rx, 0)
     dt = ddn_shard.reduce_max_seconds(dt, dev)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(chain, np, args.dump_outputs, plan)
 
     # what one step decoded (the last one): counted from the chain's result arrays
     F, Fv, S = chain.F, chain.Fv, B * chain.F
@@ -742,6 +866,8 @@ def main():
                          "launch_ms_alone": round(float(rx_ms[1]), 4),   # the same kernel with nothing else on the device
                          "chain_frac": round(alg_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 5)},
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if serial_ms is not None:
             line["one_stream_ms_per_step"] = round(serial_ms, 4)
         if world == 1 and not args.no_extras:
@@ -957,16 +1083,16 @@ def configs3_mixed(torch, ddn, np, d_iq_p25, B_per_gpu, n, steps, rank, world, d
         out["work_per_step"] = {"dmr_syncs": int(res[1][2].sum()) if 1 in res else 0, "nxdn_syncs": int(res[2][2].sum()) if 2 in res else 0}
         if world == 1:
             # the overlapped schedule (ddn_mixed_chain_config.overlap = 1: front ends on streams of their own, two discriminator buffers per group, the
-            # fsk4 loops one channel per wavefront) needs more hardware queues than HIP's default four, and more queues cost the
-            # headline chain (8.07 -> 8.64 ms at six): a process of its own, same shape, same library
+            # fsk4 loops one channel per wavefront): a process of its own, same shape, same library, with the hardware queues the
+            # environment gives it (its seven streams share them when there are fewer)
             import subprocess
-            env = dict(os.environ, MIX_OVERLAP="1", GPU_MAX_HW_QUEUES="6")
+            env = dict(os.environ, MIX_OVERLAP="1")
             try:
                 r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_mixed.py"), str(total), "10"], env=env, capture_output=True,
                                    text=True, timeout=300)
                 ms = float(r.stdout.strip().splitlines()[-1].split(":")[1].split()[0])
                 out["overlapped_schedule"] = {"ms_per_step": ms, "Msamples_per_s": round(total * n / ms / 1e3, 1),
-                                              "config": {"ddn_mixed_chain_config.overlap": 1}, "env": {"GPU_MAX_HW_QUEUES": "6"},
+                                              "config": {"ddn_mixed_chain_config.overlap": 1},
                                               "note": "opt-in (tests/test_chain_mixed_gpu.py passes in both modes); separate process"}
             except Exception as ex:  # informational only
                 out["overlapped_schedule"] = {"error": str(ex)[:200]}

@@ -786,7 +786,7 @@ ddn_mixed_chain_create(const ddn_mixed_chain_config* cfg, ddn_mixed_chain** out)
         }
     }
     {   // cfg.overlap = 1 (off by default): front ends on streams of their own, two discriminator buffers per group - call k + 1's
-        // front ends beside call k's loops.  Seven streams: it needs GPU_MAX_HW_QUEUES=6 or 7 in the process environment (HIP's default
+        // front ends beside call k's loops.  Seven streams: it needs six or seven hardware queues per process (HIP's default
         // four hardware queues make streams share queues: 17-18 ms per step; with 6: 11.75 ms against 13.2 - profiles/README.md)
         const char* e = DDN_EXP_ENV("DDN_MIX_OVERLAP");
         m->overlap = cfg->overlap != 0 || (e && e[0] == '1');

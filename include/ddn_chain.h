@@ -412,7 +412,7 @@ typedef struct ddn_mixed_chain_config {
     /* appended in round 6: */
     int overlap; /* 1 = the overlapped schedule: the front ends on streams of their own into two discriminator buffers per group (call
                     k + 1's front ends beside call k's loops), the fsk4 loops one channel per wavefront where a group has <= 1536
-                    channels.  Seven streams: it pays only with GPU_MAX_HW_QUEUES >= 6 in the process environment (HIP's default
+                    channels.  Seven streams: it pays only with six or more hardware queues per process (HIP's default
                     four hardware queues make streams share queues - slower than the default schedule).  Same results. */
 } ddn_mixed_chain_config;
 typedef struct ddn_mixed_chain ddn_mixed_chain;

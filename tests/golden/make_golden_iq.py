@@ -1,7 +1,11 @@
 """Copies two of the reference's own I/Q regression captures (data files under tests/fixtures/iq, cu8 @48 ksps) into
 tests/golden together with the known answers the reference's full-chain tests assert on them
 (tests/CMakeLists.txt:8888-8900: DECODE_IQ_P25P1_C4FM_CC expects "NAC/CC: 140", DECODE_IQ_P25P1_C4FM_VOICE expects
-"Group Voice Channel User", i.e. a voice call: LDU1/LDU2 frames).  Run in the build container only."""
+"Group Voice Channel User", i.e. a voice call: LDU1/LDU2 frames), and every capture's JSON sidecar, verbatim, into
+iq_fixture_sidecars.json (tests/test_iq_capture.py writes captures and sidecars back out as files).  Run in the build
+container only."""
+import glob
+import json
 import os
 
 import numpy as np
@@ -29,8 +33,16 @@ for name, nac_hex, note in (("p25p1_c4fm_cc", "140", "control channel: TSDU fram
                             ("ysf", "", "Yaesu System Fusion, V/D mode 2 communication channel frames; DECODE_IQ_YSF (-fy) expects "
                                         "'V/D2 RID Mode Repeater CC' (tests/CMakeLists.txt:8953-8957)"),
                             ("p25p2_cc", "", "P25 Phase 2 TDMA control channel; DECODE_IQ_P25P2_CC (-f2) expects 'P25p2 SACCH' "
-                                             "(tests/CMakeLists.txt:8923)")):
+                                             "(tests/CMakeLists.txt:8923)"),
+                            ("dpmr", "", "dPMR capture (read by the capture-reader test only)"),
+                            ("dstar", "", "D-STAR capture (read by the capture-reader test only)"),
+                            ("edacs", "", "EDACS capture (read by the capture-reader test only)")):
     iq = np.fromfile(os.path.join(SRC, name + ".iq"), dtype=np.uint8).reshape(-1, 2)
     np.savez_compressed(os.path.join(HERE, "iq_%s.npz" % name), iq=iq, rate=np.int32(48000),
                         expected_nac_hex=np.bytes_(nac_hex), note=np.bytes_(note))
     print(name, iq.shape)
+sidecars = {os.path.basename(p)[:-8]: open(p).read() for p in sorted(glob.glob(os.path.join(SRC, "*.iq.json")))}
+with open(os.path.join(HERE, "iq_fixture_sidecars.json"), "w") as f:
+    json.dump(sidecars, f, indent=0, sort_keys=True)
+    f.write("\n")
+print(len(sidecars), "sidecars")

@@ -47,8 +47,11 @@ def have_ref():
 
 
 def ref():
+    """the compiled reference, or None where oracle/_ref was not built (callers skip on None)"""
     global _ref
     if _ref is None:
+        if not have_ref():
+            return None
         r = C.CDLL(REF_SO)
         r.refh_fe_create.restype = C.c_void_p
         r.refh_fe_create.argtypes = [C.c_int] * 5 + [C.c_float, C.c_int]

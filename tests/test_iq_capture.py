@@ -1,9 +1,9 @@
 """dsd-neo I/Q capture reader (ddn_iq_capture_*) vs the reference's own reader
 (dsd_iq_replay_read_metadata / _open / _read of src/io/iq/iq_replay.c, compiled in place into oracle/_ref): every field,
 the replayable-byte rule, the data bytes delivered, and the error code for each kind of broken sidecar.  Host-only code,
-runs without a GPU; the sweep over the reference's 16 fixture captures runs where /root/reference exists."""
+runs without a GPU.  The sweep covers the reference's 16 fixture captures (tests/fixtures/iq), stored under tests/golden: the
+data as iq_<name>.npz, the JSON sidecars verbatim in iq_fixture_sidecars.json (tests/golden/make_golden_iq.py)."""
 import ctypes as C
-import glob
 import json
 import os
 
@@ -15,7 +15,20 @@ import orc
 from conftest import golden
 
 needs_ref = pytest.mark.skipif(not orc.have_ref(), reason="compiled reference (oracle/_ref) not present")
-FIXTURES = sorted(glob.glob("/root/reference/tests/fixtures/iq/*.iq.json"))
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+with open(os.path.join(GOLDEN, "iq_fixture_sidecars.json")) as _f:
+    SIDECARS = json.load(_f)
+FIXTURES = sorted(SIDECARS)
+
+
+@pytest.fixture(scope="module")
+def fixture_dir(tmp_path_factory):
+    """the fixture captures as the reference keeps them: <name>.iq (raw cu8 bytes) beside <name>.iq.json"""
+    d = tmp_path_factory.mktemp("iq_fixtures")
+    for name in FIXTURES:
+        np.ascontiguousarray(golden("iq_%s.npz" % name)["iq"], np.uint8).tofile(str(d / (name + ".iq")))
+        (d / (name + ".iq.json")).write_text(SIDECARS[name])
+    return str(d)
 
 
 class Info(C.Structure):
@@ -91,9 +104,10 @@ def write_capture(tmp, meta, data_len=2001, name="cap.iq"):
 
 
 @needs_ref
-@pytest.mark.skipif(not FIXTURES, reason="/root/reference not present")
-@pytest.mark.parametrize("meta_path", FIXTURES, ids=[os.path.basename(p)[:-8] for p in FIXTURES])
-def test_reference_fixture_captures(built, meta_path):
+@pytest.mark.parametrize("name", FIXTURES)
+def test_reference_fixture_captures(built, fixture_dir, name):
+    assert len(FIXTURES) == 16
+    meta_path = os.path.join(fixture_dir, name + ".iq.json")
     rc_r, out, stage, dp, _ = ref_meta(meta_path)
     rc_m, info = mine(meta_path)
     assert rc_r == 0 and rc_m == 0

@@ -72,10 +72,7 @@ def test_front_end_oracle_matches_reference(built, block_len, squelch, profile):
 
 @pytest.mark.skipif(not orc.have_ref(), reason="compiled reference (oracle/_ref) not present")
 def test_oracle_matches_reference_on_full_fixture(built):
-    import os
-    if not os.path.exists(orc.REFERENCE_ROOT):
-        pytest.skip("reference fixtures not present")
-    iq = orc.load_fixture_cu8("p25p1_c4fm_vc.iq")
+    iq = np.ascontiguousarray(golden("iq_p25p1_c4fm_vc.npz")["iq"])     # the whole p25p1_c4fm_vc.iq capture
     want, _, _ = orc.ref_front_end_cu8(iq, 8192)
     got = orc.OracleFrontEnd().run_cu8(iq, 8192)
     assert np.array_equal(bits(got), bits(want))
