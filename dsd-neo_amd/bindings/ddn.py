@@ -456,6 +456,11 @@ class P25ChainResults(C.Structure):  # == ddn_p25_chain_results
                 ("d_imbe_bits", C.c_void_p), ("d_imbe_result", C.c_void_p), ("d_pcm", C.c_void_p), ("d_synth_result", C.c_void_p)]
 
 
+class P25LongPduResults(C.Structure):  # == ddn_p25_long_pdu_results
+    _fields_ = [("max_blocks", C.c_int), ("per_channel", C.c_int)] + [
+        (k, C.c_void_p) for k in ("d_n", "d_sync_record", "d_header", "d_info", "d_blocks", "d_block_valid", "d_blocks18", "d_crc9_ok")]
+
+
 class P25ChainHostOut(C.Structure):  # == ddn_p25_chain_host_out
     _fields_ = [("records10", C.c_void_p), ("flags", C.c_void_p), ("counts", C.c_void_p), ("events", C.c_void_p),
                 ("n_events", C.c_void_p), ("event_data", C.c_void_p), ("nid4", C.c_void_p), ("tsbk", C.c_void_p), ("pcm", C.c_void_p),
@@ -488,6 +493,8 @@ PROTOTYPES.update({
     "ddn_p25_chain_set_first_channel": (C.c_int, [C.c_void_p, C.c_int]),
     "ddn_mbe_batch_set_first_stream": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "ddn_p25_chain_get_stage_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ddn_p25_chain_set_long_data_units": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "ddn_p25_chain_get_long_pdu_results": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_p25_chain_front_end": (C.c_void_p, [C.c_void_p]),
     "ddn_p25_chain_rx": (C.c_void_p, [C.c_void_p]),
     "ddn_p25_chain_mbe": (C.c_void_p, [C.c_void_p]),
@@ -824,6 +831,15 @@ class P25ChainC:
     def results(self):
         r = P25ChainResults()
         _check(lib().ddn_p25_chain_get_results(self.h, C.byref(r)), "ddn_p25_chain_get_results")
+        return r
+
+    def set_long_data_units(self, max_blocks=127, per_channel=0):
+        """data units longer than pdu_blocks decoded whole across calls (0 = off); before the first call or right after flush()"""
+        _check(lib().ddn_p25_chain_set_long_data_units(self.h, max_blocks, per_channel), "ddn_p25_chain_set_long_data_units")
+
+    def long_pdu_results(self):
+        r = P25LongPduResults()
+        _check(lib().ddn_p25_chain_get_long_pdu_results(self.h, C.byref(r)), "ddn_p25_chain_get_long_pdu_results")
         return r
 
     def set_timing(self, on):

@@ -153,6 +153,9 @@ struct ddn_p25_chain {
     // stage timing (ddn_p25_chain_set_timing): events at the stage boundaries of the most recent call
     int timing;
     hipEvent_t ev_t[6];
+    // long data units (ddn_p25_chain_set_long_data_units; lp.MB == 0: off, nothing is issued for them)
+    DdnLongPdu lp;
+    int after_flush; // the last call was ddn_p25_chain_flush (the switch may be set)
 };
 
 template <typename T>
@@ -164,12 +167,25 @@ dalloc(T** p, size_t count) {
     return hipMemset(*p, 0, count * sizeof(T)) == hipSuccess;
 }
 
+static void
+lpdu_free(ddn_p25_chain* c) {
+    DdnLongPdu& l = c->lp;
+    void* all[] = {l.open, l.open_buf, l.sync, l.next, l.end, l.base, l.open_rec, l.open_hdr, l.blocks, l.valid, l.blocks18, l.crc9,
+                   l.n, l.out_rec, l.out_hdr, l.out_info, l.fin, l.nw, l.wk_row, l.wk_dst, l.wk_want, l.wk_want34, l.wk_llr, l.wk_cand,
+                   l.wk_cnt, l.wk_metric, l.wk_b12, l.wk_b18, l.wk_c9};
+    for (void* p : all) {
+        (void)hipFree(p);
+    }
+    memset(&l, 0, sizeof(l));
+}
+
 extern "C" void
 ddn_p25_chain_destroy(ddn_p25_chain* c) {
     if (!c) {
         return;
     }
     (void)hipDeviceSynchronize();
+    lpdu_free(c);
     if (c->out_thread) {
         {   // jobs the worker has not picked up are dropped (their host buffers may be gone already); the one it is working on
             // is finished before the join returns
@@ -819,6 +835,29 @@ chain_settle_pending(ddn_p25_chain* c, hipStream_t st, bool deferred_too = true)
     return DDN_OK;
 }
 
+// long data units (the switch on): the blocks this call's records complete - of the unit carried from the previous decode and of
+// this call's units - through the same decoders as the data blocks above, into the per-channel store; the units that end here are
+// published.  Every decode reads and writes the carried state, so decode k + 1 must follow decode k: it does, on the stream that
+// already orders the carried event lists (k_chain_events of decode k + 1 reads what decode k wrote).
+static int
+chain_long_pdu(ddn_p25_chain* c, int cur, int flush, hipStream_t st) {
+    const DdnLongPdu* lp = &c->lp;
+    const int NW = lp->B * lp->W;
+    const int32_t *d_ns = nullptr, *d_sp = nullptr;
+    DDN_TRY(ddn_p25p1_framer_device_syncs(c->fr, &d_ns, &d_sp));
+    HIP_TRY(ddn_dev_lpdu_index(lp, c->d_evl[cur], c->d_evdl[cur], c->d_nevl[cur], c->EL, d_sp, d_ns, c->d_nid[cur], c->d_cnt_full[cur],
+                               c->stride, c->d_new[set_prev(cur)], c->step > 0 ? 1 : 0, flush, c->F, c->T, c->off97[0], st));
+    HIP_TRY(ddn_dev_lpdu_gather(lp, c->d_rec[cur], c->d_cnt_full[cur], c->stride, st));
+    // (groups of slots without a wanted block leave at once; wk_cand holds the half-rate candidates, then the rate 3/4 ones)
+    HIP_TRY(ddn_dev_p25_half_rate_list_wanted_wide(lp->wk_llr, NW, 8, lp->wk_want, (uint32_t*)lp->wk_cand, lp->wk_cnt, st));
+    HIP_TRY(ddn_dev_chain_pdu_take_first(lp->wk_cand, lp->wk_cnt, NW, lp->wk_b12, lp->wk_metric, st));
+    DDN_TRY(ddn_fec_p25_mbf34_list_batch(lp->wk_llr, (size_t)NW, 8, lp->wk_want34, (ddn_p25_mbf34_candidate*)lp->wk_cand, lp->wk_cnt, st));
+    HIP_TRY(ddn_dev_chain_pdu_r34_select(lp->wk_cand, lp->wk_cnt, lp->wk_want34, NW, lp->wk_b18, lp->wk_c9, st));
+    HIP_TRY(ddn_dev_lpdu_scatter(lp, st));
+    HIP_TRY(ddn_dev_lpdu_finish(lp, st));
+    return DDN_OK;
+}
+
 // framer + every frame type's FEC + voice of buffer set `cur` on stream st
 static int
 chain_decode(ddn_p25_chain* c, int cur, int flush, hipStream_t st, hipEvent_t ev_pre = nullptr, bool defer_synth = false) {
@@ -911,6 +950,9 @@ chain_decode(ddn_p25_chain* c, int cur, int flush, hipStream_t st, hipEvent_t ev
         HIP_TRY(ddn_dev_p25_half_rate_list_wanted(c->d_pdu_hllr, (int)NE, 8, c->d_pdu_wanted, (uint32_t*)c->d_pdu_cand, c->d_pdu_cnt, st));
         HIP_TRY(ddn_dev_chain_pdu_finish(c->d_pdu_slot, c->d_pdu_blocks, c->d_pdu_valid, c->d_pdu_blocks18, c->d_pdu_cand, c->d_pdu_cnt,
                                          c->d_pdu_wanted, (int)NE, c->PB, c->d_pdu_hdr, c->d_pdu_info, st));
+    }
+    if (c->lp.MB > 0) {
+        DDN_TRY(chain_long_pdu(c, cur, flush, st));
     }
     if (c->timing) {
         HIP_TRY(hipEventRecord(c->ev_t[4], st));
@@ -1026,6 +1068,7 @@ ddn_p25_chain_run(ddn_p25_chain* c, const void* d_iq, void* hip_stream) {
     if (!c || !d_iq) {
         return DDN_EINVAL;
     }
+    c->after_flush = 0;
     hipStream_t st = (hipStream_t)hip_stream;
     DDN_TRY(chain_settle_pending(c, st));
     const int cur = (int)(c->step % NSET);
@@ -1044,6 +1087,7 @@ ddn_p25_chain_stage(ddn_p25_chain* c, int stage, const void* d_iq, void* hip_str
     if (!c || stage < 0 || stage > 2 || (stage == 0 && !d_iq)) {
         return DDN_EINVAL;
     }
+    c->after_flush = 0;
     hipStream_t st = (hipStream_t)hip_stream;
     const int cur = (int)(c->step % NSET);
     int rc = DDN_OK;
@@ -1077,6 +1121,7 @@ ddn_p25_chain_stage0_prepare(ddn_p25_chain* c, void* hip_stream, float** disc_ou
     if (!c || !disc_out || c->cq) {
         return DDN_EINVAL;
     }
+    c->after_flush = 0;
     hipStream_t st = (hipStream_t)hip_stream;
     const int cur = (int)(c->step % NSET);
     DDN_TRY(chain_settle_pending(c, st));
@@ -1110,6 +1155,7 @@ ddn_p25_chain_run_pipelined(ddn_p25_chain* c, const void* d_iq) {
     if (!c || !d_iq) {
         return DDN_EINVAL;
     }
+    c->after_flush = 0;
     const int cur = (int)(c->step % NSET);
     const bool beside = c->synth_beside_loop != 0 && c->cfg.vocoder && !c->timing;
     if (c->step >= NSET) { // the decode of call k - NSET has read this set (and call k - 1's decode has read its carried tail source);
@@ -1139,6 +1185,7 @@ ddn_p25_chain_run_host(ddn_p25_chain* c, const void* h_iq, const ddn_p25_chain_h
     if (!c || !h_iq) {
         return DDN_EINVAL;
     }
+    c->after_flush = 0;
     const int cur = (int)(c->step % NSET);
     if (!c->d_iq[0]) {
         HIP_TRY(hipMalloc(&c->d_iq[0], c->iq_bytes + 16));
@@ -1261,6 +1308,7 @@ ddn_p25_chain_flush(ddn_p25_chain* c) {
     HIP_TRY(hipMemsetAsync(c->d_fl[cur], 0, (size_t)c->B * c->stride, c->s_aux));
     c->last_set = cur;
     c->step++;
+    c->after_flush = 1;
     return ddn_p25_chain_wait(c);
 }
 
@@ -1332,6 +1380,79 @@ ddn_p25_chain_get_results(ddn_p25_chain* c, ddn_p25_chain_results* r) {
     r->d_imbe_result = c->d_imbe_res;
     r->d_pcm = c->d_pcm[cur];
     r->d_synth_result = c->d_res_out;
+    return DDN_OK;
+}
+
+extern "C" int
+ddn_p25_chain_set_long_data_units(ddn_p25_chain* c, int max_blocks, int per_channel) {
+    if (!c) {
+        return DDN_EINVAL;
+    }
+    if (max_blocks != 0 && (max_blocks < c->PB + 1 || max_blocks > 127 || per_channel < 0)) {
+        ddn_set_error("ddn_p25_chain_set_long_data_units: max_blocks %d outside [%d, 127] or per_channel %d < 0", max_blocks, c->PB + 1,
+                      per_channel);
+        return DDN_EINVAL;
+    }
+    if (c->step > 0 && !c->after_flush) {
+        ddn_set_error("ddn_p25_chain_set_long_data_units: only before the first call or right after ddn_p25_chain_flush");
+        return DDN_EINVAL;
+    }
+    if (c->step > 0) {
+        DDN_TRY(ddn_p25_chain_wait(c));
+    }
+    lpdu_free(c);
+    if (max_blocks == 0) {
+        return DDN_OK;
+    }
+    DdnLongPdu& l = c->lp;
+    const size_t B = (size_t)c->B, MB = (size_t)max_blocks;
+    // back-to-back units of PB + 1 data blocks: 24 sync + 32 NID dibits + (PB + 2) blocks of 98, a status symbol per 35 dibits
+    const int unit_sym = (24 + 32 + 98 * (c->PB + 2) + 34) / 35 * 36;
+    const int P = per_channel > 0 ? per_channel : (int)(c->stride / (size_t)unit_sym) + 1;
+    // the blocks one row can complete (their records are disjoint: 98 payload dibits each)
+    const int W = (int)(c->stride / 98) + 2;
+    const size_t U = 2 * B + B * (size_t)P, NW = B * (size_t)W;
+    bool ok = dalloc(&l.open, B) && dalloc(&l.open_buf, B) && dalloc(&l.sync, B) && dalloc(&l.next, B) && dalloc(&l.end, B)
+              && dalloc(&l.base, B) && dalloc(&l.open_rec, B) && dalloc(&l.open_hdr, B * 12) && dalloc(&l.blocks, U * MB * 12)
+              && dalloc(&l.valid, U * MB) && dalloc(&l.blocks18, U * MB * 18) && dalloc(&l.crc9, U * MB) && dalloc(&l.n, B)
+              && dalloc(&l.out_rec, B * P) && dalloc(&l.out_hdr, B * P * 12) && dalloc(&l.out_info, B * P * 4) && dalloc(&l.fin, B * P)
+              && dalloc(&l.nw, B) && dalloc(&l.wk_row, NW) && dalloc(&l.wk_dst, NW) && dalloc(&l.wk_want, NW) && dalloc(&l.wk_want34, NW)
+              && dalloc(&l.wk_llr, NW * 196) && dalloc(&l.wk_cand, NW * 8 * 24) && dalloc(&l.wk_cnt, NW) && dalloc(&l.wk_metric, NW)
+              && dalloc(&l.wk_b12, NW * 12) && dalloc(&l.wk_b18, NW * 18) && dalloc(&l.wk_c9, NW);
+    if (!ok) {
+        lpdu_free(c);
+        ddn_set_error("ddn_p25_chain_set_long_data_units: device allocation failed");
+        return DDN_ENOMEM;
+    }
+    l.B = c->B;
+    l.MB = max_blocks;
+    l.P = P;
+    l.W = W;
+    l.PB = c->PB;
+    return DDN_OK;
+}
+
+extern "C" int
+ddn_p25_chain_get_long_pdu_results(ddn_p25_chain* c, ddn_p25_long_pdu_results* r) {
+    if (!c || !r) {
+        return DDN_EINVAL;
+    }
+    memset(r, 0, sizeof(*r));
+    const DdnLongPdu& l = c->lp;
+    if (l.MB == 0) {
+        return DDN_OK; // (switched off: max_blocks = 0, no arrays)
+    }
+    const size_t o = 2 * (size_t)l.B * (size_t)l.MB; // the output entries follow the two carry buffers per channel in the store
+    r->max_blocks = l.MB;
+    r->per_channel = l.P;
+    r->d_n = l.n;
+    r->d_sync_record = l.out_rec;
+    r->d_header = l.out_hdr;
+    r->d_info = l.out_info;
+    r->d_blocks = l.blocks + o * 12;
+    r->d_block_valid = l.valid + o;
+    r->d_blocks18 = l.blocks18 + o * 18;
+    r->d_crc9_ok = l.crc9 + o;
     return DDN_OK;
 }
 

@@ -592,7 +592,287 @@ k_chain_pdu_finish(const int32_t* __restrict__ pdu_slot, const uint8_t* __restri
     pdu_info[(size_t)e * 4 + 3] = crc32_ok;
 }
 
-// NXDN voice stage bookkeeping (nxdn_voice(): the LICH's profile says which of a frame's four 36-dibit fields are voice): the
+// ---- long data units (ddn_p25_chain_set_long_data_units) ----------------------------------------------------------------------
+// A data unit whose header announces more than PB data blocks (the reference reads up to 127: P25_MPDU_MAX_DATA_BLOCKS, the block
+// loop of p25_mpdu_collect_blocks) runs past what one row holds behind its sync.  The receive loop stays in frame for the whole unit,
+// so at most one unit per channel is unfinished at the end of a call: that one is carried (its sync re-based to the next row as
+// k_chain_events re-bases carried events), and each call decodes the blocks its records complete.  k_lpdu_index (one thread per
+// channel) lays out the work: a fixed slot per block that becomes complete, the store place it is decoded into (the output entry of
+// a unit that ends in this call, else one of the channel's two carry buffers), the output entries of the units that end here.
+// Block b's last payload dibit is n = 56 + 98 b + 97, at row index sync - 23 + n + n / 35 (as k_chain_pdu_gather).
+__device__ __forceinline__ int
+lpdu_block_last(int sync, int b) {
+    const int n = 56 + 98 * b + 97;
+    return sync - 23 + n + n / 35;
+}
+
+__global__ void
+k_lpdu_index(DdnLongPdu lp, const int32_t* __restrict__ list, const int32_t* __restrict__ data, const int32_t* __restrict__ n_list, int EL,
+             const int32_t* __restrict__ sync_pos, const int32_t* __restrict__ n_syncs, const int32_t* __restrict__ nid4,
+             const int32_t* __restrict__ cnt_full, int max_sym, const int32_t* __restrict__ new_prev, int have_prev, int flush, int F,
+             int T, int off0) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= lp.B) {
+        return;
+    }
+    const int MB = lp.MB, P = lp.P, W = lp.W;
+    const int shift = have_prev ? new_prev[c] : 0;
+    const int64_t base = lp.base[c] + shift;
+    lp.base[c] = base;
+    const int cnt = cnt_full[c] < max_sym ? cnt_full[c] : max_sym;
+    for (int w = 0; w < W; w++) {
+        lp.wk_want[(size_t)c * W + w] = 0;
+        lp.wk_want34[(size_t)c * W + w] = 0;
+    }
+    const int ob = lp.open_buf[c];
+    int nw = 0, total = 0;
+    bool opened = false;
+    // one unit: the blocks this row completes get work slots; a unit that ends here (or is closed: flush, or a later unit's sync)
+    // takes the next output entry
+    auto unit = [&](int sync, int end, int next, const uint8_t* hdr, int64_t rec, int carried_buf, bool closes) {
+        const bool r34 = ((hdr[0] >> 6) & 1) && (hdr[0] & 0x1F) == 0x16;
+        int last = next - 1;
+        while (last + 1 < end && lpdu_block_last(sync, last + 1) < cnt) {
+            last++;
+        }
+        const bool complete = last == end - 1;
+        int dst = -1;
+        if (complete || flush || closes) {
+            const int r = total++;
+            if (r < P) {
+                const size_t e = (size_t)c * P + r;
+                lp.out_rec[e] = rec;
+                for (int i = 0; i < 12; i++) {
+                    lp.out_hdr[e * 12 + i] = hdr[i];
+                }
+                lp.out_info[e * 4 + 0] = end;
+                lp.out_info[e * 4 + 1] = 0;
+                lp.out_info[e * 4 + 2] = (r34 ? 4 : 0) | (complete ? 0 : 8) | (end - 1 > MB ? 16 : 0);
+                lp.out_info[e * 4 + 3] = 0;
+                if (carried_buf >= 0) {
+                    dst = c * 2 + carried_buf;
+                    lp.fin[e] = dst;
+                } else {
+                    dst = 2 * lp.B + (int)e;
+                    lp.fin[e] = -1;
+                }
+            }
+        } else { // the unit goes on in the next call
+            const int buf = carried_buf >= 0 ? carried_buf : 1 - ob;
+            dst = c * 2 + buf;
+            opened = true;
+            lp.open_buf[c] = buf;
+            lp.sync[c] = sync;
+            lp.next[c] = last + 1;
+            lp.end[c] = end;
+            lp.open_rec[c] = rec;
+            for (int i = 0; i < 12; i++) {
+                lp.open_hdr[(size_t)c * 12 + i] = hdr[i];
+            }
+        }
+        if (dst < 0) {
+            return; // (an entry beyond P: counted only)
+        }
+        if (carried_buf < 0) {
+            for (int b = 0; b < MB; b++) {
+                lp.valid[(size_t)dst * MB + b] = 0;
+            }
+        }
+        for (int b = next; b <= last && b <= MB && nw < W; b++) {
+            const size_t s = (size_t)c * W + nw++;
+            lp.wk_row[s] = sync - 23;
+            lp.wk_dst[s] = dst * MB + b - 1;
+            lp.wk_want[s] = 1;
+            lp.wk_want34[s] = r34 ? 1 : 0;
+        }
+    };
+    // this call's long units: kind-3 decisions whose sync this call decodes, header CRC16 good, more than PB data blocks
+    const int ns = n_syncs[c] < F ? n_syncs[c] : F;
+    const int32_t* sp = sync_pos + (size_t)c * F;
+    const int4* l = reinterpret_cast<const int4*>(list) + (size_t)c * EL;
+    const int4* d = reinterpret_cast<const int4*>(data) + (size_t)c * EL;
+    const int n = n_list[c] < EL ? n_list[c] : EL;
+    auto is_long = [&](int j, int& k, int& a) -> bool {
+        const int4 e = l[j];
+        if (e.y != 3) {
+            return false;
+        }
+        a = e.x - off0;
+        while (k < ns && sp[k] < a) {
+            k++;
+        }
+        if (k >= ns || sp[k] != a) {
+            return false;
+        }
+        const size_t slot = (size_t)c * F + k;
+        return nid4[slot * 4] > 0 && nid4[slot * 4 + 2] == 0xC && (d[j].w & 1) && (e.w & 0xFFFF) - 1 > lp.PB;
+    };
+    int nl = 0;
+    for (int j = 0, k = 0, a = 0; j < n; j++) {
+        nl += is_long(j, k, a) ? 1 : 0;
+    }
+    if (lp.open[c]) {
+        uint8_t h[12];
+        for (int i = 0; i < 12; i++) {
+            h[i] = lp.open_hdr[(size_t)c * 12 + i];
+        }
+        unit(lp.sync[c] - shift, lp.end[c], lp.next[c], h, lp.open_rec[c], ob, nl > 0);
+    }
+    for (int j = 0, k = 0, a = 0, i = 0; j < n; j++) {
+        if (!is_long(j, k, a)) {
+            continue;
+        }
+        const int4 v = d[j];
+        uint8_t h[12];
+        const uint32_t w3[3] = {(uint32_t)v.x, (uint32_t)v.y, (uint32_t)v.z};
+        for (int q = 0; q < 12; q++) {
+            h[q] = (uint8_t)(w3[q >> 2] >> (8 * (q & 3)));
+        }
+        unit(a, l[j].w & 0xFFFF, 1, h, base + a - T, -1, i < nl - 1);
+        i++;
+    }
+    lp.open[c] = opened ? 1 : 0;
+    lp.nw[c] = nw;
+    lp.n[c] = total;
+}
+
+// the work slots' 98 LLR pairs in received order, one workgroup per channel
+__global__ __launch_bounds__(128) void
+k_lpdu_gather(DdnLongPdu lp, const uint8_t* __restrict__ rec, const int32_t* __restrict__ cnt_full, int max_sym) {
+    const int c = blockIdx.x, j = threadIdx.x;
+    const int nw = lp.nw[c];
+    const int cnt = cnt_full[c] < max_sym ? cnt_full[c] : max_sym;
+    if (j >= 98) {
+        return;
+    }
+    for (int s = 0; s < nw; s++) {
+        const size_t slot = (size_t)c * lp.W + s;
+        const int b = lp.wk_dst[slot] % lp.MB + 1;
+        const int nn = 56 + 98 * b + j;
+        const int idx = lp.wk_row[slot] + nn + nn / 35;
+        int l0 = 0, l1 = 0;
+        if (idx >= 0 && idx < cnt) {
+            const uint8_t* q = rec + ((size_t)c * max_sym + (size_t)idx) * 10;
+            l0 = (int16_t)((uint16_t)q[2] | ((uint16_t)q[3] << 8));
+            l1 = (int16_t)((uint16_t)q[4] | ((uint16_t)q[5] << 8));
+        }
+        lp.wk_llr[slot * 196 + 2 * j] = (int16_t)l0;
+        lp.wk_llr[slot * 196 + 2 * j + 1] = (int16_t)l1;
+    }
+}
+
+// the decoded blocks (half-rate candidate 0; rate 3/4: first good CRC9) into their store places
+__global__ void
+k_lpdu_scatter(DdnLongPdu lp) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)lp.B * lp.W || !lp.wk_want[i]) {
+        return;
+    }
+    const size_t d = (size_t)lp.wk_dst[i];
+    const bool r34 = lp.wk_want34[i] != 0;
+    for (int k = 0; k < 12; k++) {
+        lp.blocks[d * 12 + k] = lp.wk_b12[i * 12 + k];
+    }
+    for (int k = 0; k < 18; k++) {
+        lp.blocks18[d * 18 + k] = r34 ? lp.wk_b18[i * 18 + k] : (uint8_t)0;
+    }
+    lp.crc9[d] = r34 ? lp.wk_c9[i] : (uint8_t)0;
+    lp.valid[d] = 1;
+}
+
+// crc32mbf (MSB first, polynomial 0x04C11DB7, initial 0, inverted at the end) a byte at a time
+struct LpduCrcTable {
+    uint32_t t[256];
+};
+constexpr LpduCrcTable
+lpdu_crc_table() {
+    LpduCrcTable r{};
+    for (uint32_t i = 0; i < 256; i++) {
+        uint32_t v = i << 24;
+        for (int k = 0; k < 8; k++) {
+            v = (v & 0x80000000u) ? (v << 1) ^ 0x04C11DB7u : (v << 1);
+        }
+        r.t[i] = v;
+    }
+    return r;
+}
+__constant__ LpduCrcTable g_lpdu_crc = lpdu_crc_table();
+
+// one workgroup (a wavefront) per entry of a unit that ended in this call: its blocks copied from the carry buffer when it was
+// carried and the blocks never decoded zeroed (the lanes side by side), then one lane counts the decoded data blocks and runs the
+// CRC32 over the data (p25_mpdu_handle_rate12 / p25_mpdu_compute_rate34_crc: 96 blks - 32 / 128 blks - 32 bits, byte-aligned)
+// when every block is in
+__global__ __launch_bounds__(64) void
+k_lpdu_finish(DdnLongPdu lp) {
+    const int e = blockIdx.x, lane = threadIdx.x;
+    const int c = e / lp.P, r = e - c * lp.P;
+    if (r >= lp.n[c]) {
+        return;
+    }
+    const int MB = lp.MB;
+    const size_t u = (size_t)(2 * lp.B + e) * MB;
+    const int src = lp.fin[e];
+    if (src >= 0) {
+        const size_t s = (size_t)src * MB;
+        for (int b = lane; b < MB; b += 64) {
+            lp.valid[u + b] = lp.valid[s + b];
+            lp.crc9[u + b] = lp.crc9[s + b];
+        }
+        for (int i = lane; i < MB * 12; i += 64) {
+            lp.blocks[u * 12 + i] = lp.blocks[s * 12 + i];
+        }
+        for (int i = lane; i < MB * 18; i += 64) {
+            lp.blocks18[u * 18 + i] = lp.blocks18[s * 18 + i];
+        }
+        __syncthreads();
+    }
+    for (int i = lane; i < MB * 12; i += 64) {
+        if (!lp.valid[u + i / 12]) {
+            lp.blocks[u * 12 + i] = 0;
+        }
+    }
+    for (int i = lane; i < MB * 18; i += 64) {
+        if (!lp.valid[u + i / 18]) {
+            lp.blocks18[u * 18 + i] = 0;
+        }
+    }
+    for (int b = lane; b < MB; b += 64) {
+        if (!lp.valid[u + b]) {
+            lp.crc9[u + b] = 0;
+        }
+    }
+    __syncthreads();
+    if (lane != 0) {
+        return;
+    }
+    int decoded = 0;
+    for (int b = 0; b < MB; b++) {
+        decoded += lp.valid[u + b] ? 1 : 0;
+    }
+    const int end = lp.out_info[(size_t)e * 4 + 0], flags = lp.out_info[(size_t)e * 4 + 2];
+    const int nd = end - 1;
+    int ok = 0;
+    if (!(flags & (8 | 16)) && decoded == nd) {
+        const bool r34 = (flags & 4) != 0;
+        const int len = (r34 ? 16 : 12) * nd - 4;
+        uint32_t crc = 0;
+        for (int i = 0; i < len; i++) {
+            const uint8_t by = r34 ? lp.blocks18[(u + (size_t)(i >> 4)) * 18 + 2 + (i & 15)] : lp.blocks[u * 12 + (size_t)i];
+            crc = (crc << 8) ^ g_lpdu_crc.t[((crc >> 24) ^ by) & 0xFF];
+        }
+        crc ^= 0xFFFFFFFFu;
+        uint32_t want = 0;
+        for (int i = len; i < len + 4; i++) {
+            const uint8_t by = r34 ? lp.blocks18[(u + (size_t)(i >> 4)) * 18 + 2 + (i & 15)] : lp.blocks[u * 12 + (size_t)i];
+            want = (want << 8) | by;
+        }
+        ok = crc == want ? 1 : 0;
+    }
+    lp.out_info[(size_t)e * 4 + 1] = decoded;
+    lp.out_info[(size_t)e * 4 + 3] = ok;
+}
+
+// NXDN voice stage bookkeeping (nxdn_voice():the LICH's profile says which of a frame's four 36-dibit fields are voice): the
 // first vf sync slots of every channel feed the voice gather; field v of slot (c, j) is skipped unless the LICH parity held, the
 // frame is complete and the LICH value announces voice in that half.
 __global__ void
@@ -1000,5 +1280,46 @@ ddn_dev_tsbk_select(const uint8_t* cand, const int32_t* counts, size_t n, uint8_
         return hipSuccess;
     }
     hipLaunchKernelGGL(k_tsbk_select, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cand, counts, n, out12, crc_ok, sel);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+ddn_dev_lpdu_index(const DdnLongPdu* lp, const int32_t* list, const int32_t* data, const int32_t* n_list, int EL, const int32_t* sync_pos,
+                   const int32_t* n_syncs, const int32_t* nid4, const int32_t* cnt_full, size_t max_sym, const int32_t* new_prev, int have_prev,
+                   int flush, int F, int T, int off0, hipStream_t st) {
+    if (lp->B <= 0) {
+        return hipSuccess;
+    }
+    hipLaunchKernelGGL(k_lpdu_index, dim3((unsigned)((lp->B + DDN_WG - 1) / DDN_WG)), dim3(DDN_WG), 0, st, *lp, list, data, n_list, EL,
+                       sync_pos, n_syncs, nid4, cnt_full, (int)max_sym, new_prev, have_prev, flush, F, T, off0);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+ddn_dev_lpdu_gather(const DdnLongPdu* lp, const uint8_t* rec, const int32_t* cnt_full, size_t max_sym, hipStream_t st) {
+    if (lp->B <= 0) {
+        return hipSuccess;
+    }
+    hipLaunchKernelGGL(k_lpdu_gather, dim3((unsigned)lp->B), dim3(128), 0, st, *lp, rec, cnt_full, (int)max_sym);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+ddn_dev_lpdu_scatter(const DdnLongPdu* lp, hipStream_t st) {
+    const size_t n = (size_t)lp->B * (size_t)lp->W;
+    if (n == 0) {
+        return hipSuccess;
+    }
+    hipLaunchKernelGGL(k_lpdu_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, *lp);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+ddn_dev_lpdu_finish(const DdnLongPdu* lp, hipStream_t st) {
+    const int n = lp->B * lp->P;
+    if (n <= 0) {
+        return hipSuccess;
+    }
+    hipLaunchKernelGGL(k_lpdu_finish, dim3((unsigned)n), dim3(64), 0, st, *lp);
     return hipGetLastError();
 }

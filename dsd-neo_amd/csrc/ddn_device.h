@@ -299,6 +299,8 @@ hipError_t ddn_dev_p25_half_rate(const int16_t* llr, int n, uint8_t* out, int32_
 hipError_t ddn_dev_r34(const uint8_t* dibits, const uint8_t* reliab, int n, uint8_t* out, hipStream_t st);
 hipError_t ddn_dev_p25_half_rate_list_wanted(const int16_t* llr, int n, int max_cand, const uint8_t* wanted, uint32_t* cand, int32_t* count,
                                              hipStream_t st);
+hipError_t ddn_dev_p25_half_rate_list_wanted_wide(const int16_t* llr, int n, int max_cand, const uint8_t* wanted, uint32_t* cand,
+                                                  int32_t* count, hipStream_t st);
 hipError_t ddn_dev_k5_nxdn_wanted(const uint8_t* sym, const uint8_t* rel, int n, int n_steps, int n_bits, uint16_t* metrics_io,
                                   uint8_t* out, int out_stride, const uint8_t* wanted, int wanted_div, hipStream_t st);
 hipError_t ddn_dev_trellis_greedy_wanted(const uint8_t* src, int src_stride, size_t n, int result_len, uint8_t* out, int out_stride,
@@ -418,7 +420,39 @@ hipError_t ddn_dev_chain_pdu_r34_wanted(const int32_t* pdu_slot, const uint8_t* 
                                         int n_blocks, int PB, uint8_t* wanted, hipStream_t st);
 hipError_t ddn_dev_chain_pdu_r34_select(const uint8_t* cand24, const int32_t* counts, const uint8_t* wanted, int n_blocks,
                                         uint8_t* blocks18, uint8_t* crc9_ok, hipStream_t st);
-hipError_t ddn_dev_chain_frames(const int32_t* list, const int32_t* data, const int32_t* n_list, int EL, const int32_t* sync_pos,
+/* long data units (ddn_p25_chain_set_long_data_units): the per-channel state carried across calls, the block store, the work list
+ * and the outputs.  Block store: units [2 B] (two carry buffers per channel) then [B * P] (the output entries), MB blocks each. */
+typedef struct DdnLongPdu {
+    int B, MB, P, W, PB;
+    int32_t* open;      /* [B] 1 = a unit is open at the end of the last decode */
+    int32_t* open_buf;  /* [B] carry buffer (0 / 1) of the open unit */
+    int32_t* sync;      /* [B] its sync's row index in the last decode's row */
+    int32_t* next;      /* [B] its next data block to decode (1 ..) */
+    int32_t* end;       /* [B] blocks the reference reads, header included */
+    int64_t* base;      /* [B] new records of every decode before this one (since the switch was set) */
+    int64_t* open_rec;  /* [B] stream record of the open unit's sync */
+    uint8_t* open_hdr;  /* [B][12] */
+    uint8_t *blocks, *valid, *blocks18, *crc9; /* store: [U][MB][12], [U][MB], [U][MB][18], [U][MB] */
+    int32_t* n;         /* [B] units finished in this call */
+    int64_t* out_rec;   /* [B][P] */
+    uint8_t* out_hdr;   /* [B][P][12] */
+    int32_t* out_info;  /* [B][P][4] */
+    int32_t* fin;       /* [B][P] store unit the entry's blocks are copied from at finish, -1 = decoded in place */
+    int32_t* nw;        /* [B] work slots used */
+    int32_t *wk_row, *wk_dst; /* [B][W] row index of the unit's frame start (sync - 23); store unit * MB + block - 1 */
+    uint8_t *wk_want, *wk_want34;
+    int16_t* wk_llr;    /* [B][W][196] */
+    uint8_t* wk_cand;   /* [B][W][8][24] */
+    int32_t *wk_cnt, *wk_metric;
+    uint8_t *wk_b12, *wk_b18, *wk_c9;
+} DdnLongPdu;
+hipError_t ddn_dev_lpdu_index(const DdnLongPdu* lp, const int32_t* list, const int32_t* data, const int32_t* n_list, int EL,
+                              const int32_t* sync_pos, const int32_t* n_syncs, const int32_t* nid4, const int32_t* cnt_full,
+                              size_t max_sym, const int32_t* new_prev, int have_prev, int flush, int F, int T, int off0, hipStream_t st);
+hipError_t ddn_dev_lpdu_gather(const DdnLongPdu* lp, const uint8_t* rec, const int32_t* cnt_full, size_t max_sym, hipStream_t st);
+hipError_t ddn_dev_lpdu_scatter(const DdnLongPdu* lp, hipStream_t st);
+hipError_t ddn_dev_lpdu_finish(const DdnLongPdu* lp, hipStream_t st);
+hipError_t ddn_dev_chain_frames(const int32_t* list,const int32_t* data, const int32_t* n_list, int EL, const int32_t* sync_pos,
                                 const int32_t* n_syncs, int n_channels, int F, int off0, int off1, int off2, int32_t* nid4,
                                 uint8_t* tsbk, uint8_t* tsbk_crc, uint8_t* cls, int32_t* lists, int32_t* list_n, hipStream_t st);
 enum { DDN_CLS_LDU1 = 1, DDN_CLS_LDU2 = 2, DDN_CLS_HDU = 4, DDN_CLS_TDULC = 8 }; /* frame-type bits of a slot's class byte */

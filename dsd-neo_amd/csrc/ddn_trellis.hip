@@ -866,6 +866,20 @@ ddn_dev_p25_half_rate_list_wanted(const int16_t* llr, int n, int max_cand, const
     return hipGetLastError();
 }
 
+// the same sparse form with more workgroups: a list that may be dense (the long data units' blocks - up to ~50 per channel and
+// call under packet traffic) would run through 1024 workgroups one group of four after the other
+extern "C" hipError_t
+ddn_dev_p25_half_rate_list_wanted_wide(const int16_t* llr, int n, int max_cand, const uint8_t* wanted, uint32_t* cand, int32_t* count,
+                                       hipStream_t st) {
+    if (n <= 0) {
+        return hipSuccess;
+    }
+    const unsigned groups = (unsigned)((n + 3) / 4);
+    hipLaunchKernelGGL((k_p25_half_rate_list<4, 64>), dim3(groups > 16384 ? 16384u : groups), dim3(64), 0, st, llr, n, max_cand, cand, count,
+                       wanted);
+    return hipGetLastError();
+}
+
 extern "C" hipError_t
 ddn_dev_p25_half_rate_list(const int16_t* llr, int n, int max_cand, uint32_t* cand, int32_t* count, hipStream_t st) {
     return ddn_dev_p25_half_rate_list_wanted(llr, n, max_cand, nullptr, cand, count, st);

@@ -189,6 +189,39 @@ int ddn_p25_chain_set_timing(ddn_p25_chain* c, int enable);
  * a channel's number - the vocoder's unvoiced-noise sequence - follows the global number.  Before the first call only. */
 int ddn_p25_chain_set_first_channel(ddn_p25_chain* c, int first);
 int ddn_p25_chain_get_stage_ms(ddn_p25_chain* c, float out4[4]);
+/* Long data units (DUID 0xC whose header announces more than pdu_blocks data blocks - packet data: the reference reads up to 127,
+ * p25p1_mdpu.c).  The d_pdu_* arrays file such a unit in its sync's call with its first pdu_blocks blocks and flag 8, whatever this
+ * switch says (a host tells that it goes on by d_pdu_info[1] - 1 > pdu_blocks).  With the switch on, the chain also carries one open
+ * unit per channel from call to call, decodes each data block in the call whose records complete it and reports the whole unit once,
+ * in the results of the call that brings its last block (or of ddn_p25_chain_flush, which closes an open unit).
+ *   max_blocks: 0 = off (the default; nothing is decoded or allocated for it), else in [pdu_blocks + 1, 127]
+ *   per_channel: units reported per channel and call, 0 = derived from the row length (enough for back-to-back units of
+ *   pdu_blocks + 1 blocks: stride_symbols / 1080 + 1)
+ * Allowed before the first call or right after ddn_p25_chain_flush() (the carried state starts empty; d_sync_record counts from
+ * there).  Applies to every form of the chain (C4FM and CQPSK, _run / _run_pipelined / _run_host / _stage, the P25 part of a mixed
+ * chain, a node's parts); units whose header the reference reads as at most pdu_blocks data blocks (SAP 61 / 63 with more than ten
+ * announced blocks included: they read four) never appear here.
+ * Device memory, allocated here and freed by ddn_p25_chain_destroy: about B * 32 * max_blocks * (2 + per_channel) bytes of block
+ * store plus a work list of B * (stride_symbols / 98 + 2) blocks at 630 bytes - 4096 channels x 48000 samples, max_blocks 127:
+ * 0.13 GB + 0.17 GB. */
+int ddn_p25_chain_set_long_data_units(ddn_p25_chain* c, int max_blocks, int per_channel);
+typedef struct ddn_p25_long_pdu_results { /* device pointers, valid until the next run (like the d_pdu_* arrays); entry = channel *
+                                             per_channel + rank in air order */
+    int max_blocks, per_channel;  /* 0, 0 and NULL pointers while the switch is off */
+    const int32_t* d_n;           /* [B] units that ended in this call (beyond per_channel: counted only) */
+    const int64_t* d_sync_record; /* [B][per_channel] record index of the unit's sync in the channel's stream: records since the switch
+                                     was set = sum of d_new over the earlier calls + d_sync_pos - carry_symbols of the call that
+                                     decoded the sync */
+    const uint8_t* d_header;      /* [..][12] as the loop decoded it (CRC16 good: a unit is only long when its header decoded) */
+    const int32_t* d_info;        /* [..][4] {blocks the reference reads (header included), data blocks decoded, flags, CRC32 good};
+                                     flags: 4 confirmed data (the blocks are in d_blocks18 too), 8 the stream ended (flush) before the last
+                                     block, 16 the unit announced more than max_blocks (the first max_blocks kept, CRC32 not checked) */
+    const uint8_t* d_blocks;      /* [..][max_blocks][12] half-rate data blocks 1.., as d_pdu_blocks (zero where not decoded) */
+    const uint8_t* d_block_valid; /* [..][max_blocks] */
+    const uint8_t* d_blocks18;    /* [..][max_blocks][18] confirmed data (flag 4), as d_pdu_blocks18 */
+    const uint8_t* d_crc9_ok;     /* [..][max_blocks] */
+} ddn_p25_long_pdu_results;
+int ddn_p25_chain_get_long_pdu_results(ddn_p25_chain* c, ddn_p25_long_pdu_results* out);
 /* ---- P25 Phase 2: the TDMA channel as one object -----------------------------------------------------------------------------------
  *   cu8 / cf32 I/Q -> CQPSK demodulator at 6000 symbols/s (ddn_cqpsk_run) -> symbol-rate receive loop (ddn_cq_rx, DDN_CQ_P25P2: S-ISCH
  *   sync exact or under the rotated constellations, 700 in-frame dibits per sync) -> the 700 dibits behind every sync
