@@ -11,6 +11,7 @@
 #include "ddn_device.h"
 #include "ddn_fsk4.h"
 #include "ddn_tables_fsk4.h"
+#include "ddn_tables_dpmr.h"
 
 #define HIP_TRY(expr)                                                                                                  \
     do {                                                                                                               \
@@ -67,6 +68,7 @@ struct ddn_fsk4_rx {
     int32_t *d_events, *d_n_events;
     size_t max_events;
     int32_t *d_ev_own, *d_nev_own; // event buffers of the host convenience calls (ddn_fsk4_rx_events_host_*)
+    int tap_set;                   // the matched filter's tap table (0 DMR, 1 NXDN48, 2 dPMR): the taps create() uploaded
     bool timing;
     hipEvent_t ev[3];
 };
@@ -140,13 +142,14 @@ ddn_fsk4_rx_create(const ddn_fsk4_rx_config* cfg, ddn_fsk4_rx** out) {
     *out = nullptr;
     if (cfg->n_channels <= 0 || cfg->out_rate_hz <= 0
         || (cfg->protocol != DDN_FSK4_DMR && cfg->protocol != DDN_FSK4_NXDN48 && cfg->protocol != DDN_FSK4_NXDN96 && cfg->protocol != DDN_FSK4_M17
-            && cfg->protocol != DDN_FSK4_YSF)
-        || (cfg->rf_mod != 0 && cfg->rf_mod != 2) || (cfg->inverted && cfg->protocol != DDN_FSK4_DMR)) {
-        ddn_set_error("ddn_fsk4_rx_create: bad configuration (protocol DMR | NXDN48 | NXDN96 | M17 | YSF, rf_mod 0 | 2, inverted only for DMR)");
+            && cfg->protocol != DDN_FSK4_YSF && cfg->protocol != DDN_FSK4_DPMR)
+        || (cfg->rf_mod != 0 && cfg->rf_mod != 2) || (cfg->inverted && cfg->protocol != DDN_FSK4_DMR && cfg->protocol != DDN_FSK4_DPMR)) {
+        ddn_set_error("ddn_fsk4_rx_create: bad configuration (protocol DMR | NXDN48 | NXDN96 | M17 | YSF | DPMR, rf_mod 0 | 2, inverted only "
+                      "for DMR and DPMR)");
         return DDN_EINVAL;
     }
     {
-        const int sym_rate = cfg->protocol == DDN_FSK4_NXDN48 ? 2400 : 4800;
+        const int sym_rate = (cfg->protocol == DDN_FSK4_NXDN48 || cfg->protocol == DDN_FSK4_DPMR) ? 2400 : 4800;
         if (cfg->out_rate_hz / sym_rate < 8 || cfg->out_rate_hz / sym_rate > 21) {
             // the kernel's per-round hand-off queue and its whole-symbol pass are sized for 8..21 samples per symbol
             ddn_set_error("ddn_fsk4_rx_create: out_rate_hz / symbol rate must be within 8..21 (48 ksps: DMR 10, NXDN48 20)");
@@ -214,6 +217,22 @@ ddn_fsk4_rx_create(const ddn_fsk4_rx_config* cfg, ddn_fsk4_rx** out) {
         d.nt = DDN_DMR_FILTER_TAPS;
         tap_bits = ddn_dmr_filter_bits;
         lock_default[0] = 460;
+    } else if (cfg->protocol == DDN_FSK4_DPMR) {
+        // -fm: FS2 only, exact over 12 symbols, the plain word or - under -xd (inverted) - the inverted one
+        // (frame_sync_try_dpmr(), src/dsp/dsd_frame_sync.c:832-862; include/dsd-neo/core/sync_patterns.h:123-132; types =
+        // synctype_ids.h:92,96 + 1).  Neither type is a four-level negative type to digitize() (src/core/frames/dsd_dibit.c:916-935):
+        // the dibits stay as sliced, processdPMRvoice() XORs them with 2 itself under -xd - pat_neg stays 0.
+        // dpmr_filter once a dPMR type is held (src/dsp/dsd_symbol.c:316-321); 372 dibits behind a sync (dpmr_voice.c:397-425).
+        static const char kFs2[] = "113333131331", kFs2Inv[] = "331111313113";
+        d.sym_rate = 2400;
+        d.win_len = d.t_max = d.warm_len = 12;
+        d.n_pat = 1;
+        d.pat_bits[0] = sign_bits(cfg->inverted ? kFs2Inv : kFs2);
+        d.pat_type[0] = cfg->inverted ? 26 : 22;
+        d.nt = DDN_DPMR_FILTER_TAPS;
+        tap_bits = ddn_dpmr_filter_bits;
+        b->tap_set = 2;
+        lock_default[0] = 372;
     } else if (cfg->protocol == DDN_FSK4_DMR) {
         d.sym_rate = 4800;
         d.win_len = d.t_max = d.warm_len = 24;
@@ -260,6 +279,7 @@ ddn_fsk4_rx_create(const ddn_fsk4_rx_config* cfg, ddn_fsk4_rx** out) {
         }
         d.nt = n96 ? DDN_DMR_FILTER_TAPS : DDN_NXDN48_FILTER_TAPS;
         tap_bits = n96 ? ddn_dmr_filter_bits : ddn_nxdn48_filter_bits;
+        b->tap_set = n96 ? 0 : 1;
         lock_default[0] = 182;
     }
     bool all_zero = true;
@@ -336,6 +356,10 @@ ddn_fsk4_rx_set_handlers(ddn_fsk4_rx* b, int enable) {
     }
     if (enable && b->cfg.inverted) {
         ddn_set_error("ddn_fsk4_rx_set_handlers: the handlers are the reference's plain -fs ones (inverted = 0)");
+        return DDN_EINVAL;
+    }
+    if (enable && b->cfg.protocol == DDN_FSK4_DPMR) {
+        ddn_set_error("ddn_fsk4_rx_set_handlers: dPMR superframes are a fixed count (no handler family)");
         return DDN_EINVAL;
     }
     b->dc.handlers = enable ? 1 : 0;
@@ -459,7 +483,7 @@ ddn_fsk4_rx_run(ddn_fsk4_rx* b, const float* d_disc, size_t n, uint8_t* d_record
             HIP_TRY(hipMalloc(&b->d_filt, sizeof(float) * (size_t)B * n));
             b->filt_cap = n;
         }
-        HIP_TRY(ddn_dev_fsk4_matched_filter(b->dc.nt, d_disc, (long)n, n, B, b->d_fhist, b->d_filt, st));
+        HIP_TRY(ddn_dev_fsk4_matched_filter(b->dc.nt, b->tap_set, d_disc, (long)n, n, B, b->d_fhist, b->d_filt, st));
     }
     if (b->timing) {
         HIP_TRY(hipEventRecord(b->ev[1], st));

@@ -189,7 +189,7 @@ hipError_t ddn_dev_p25_rx(const float* raw, const float* filt, const float* prev
                           uint8_t* flags, int32_t* counts, size_t max_sym, int channels_per_wave,
                           const int32_t* lock_cfg, DdnP25HState* hstate, float* hh_store, int32_t* events,
                           int32_t* n_events, hipStream_t st);
-hipError_t ddn_dev_fsk4_matched_filter(int nt, const float* in, long n, size_t stride, int n_channels, const float* hist,
+hipError_t ddn_dev_fsk4_matched_filter(int nt, int tap_set, const float* in, long n, size_t stride, int n_channels, const float* hist,
                                        float* out, hipStream_t st);
 hipError_t ddn_dev_fsk4_filter_hist_update(int nt, const float* in, long n, size_t stride, int n_channels, float* hist,
                                            hipStream_t st);

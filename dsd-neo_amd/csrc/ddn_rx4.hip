@@ -31,6 +31,7 @@
 #include "ddn_slicer_dev.h"
 #include "ddn_fsk4h_dev.h"
 #include "ddn_tables_fsk4.h"
+#include "ddn_tables_dpmr.h"
 #include "ddn_tables_ambe.h"
 
 namespace {
@@ -112,14 +113,18 @@ struct Fsk4Cfg {
     // PROTO 5 YSF (round 5): the 20-symbol FUSION_SYNC compared exactly in both polarities (frame_sync_try_ysf(),
     // src/dsp/dsd_frame_sync.c:770-797), 20-symbol warm start, the DMR matched filter (src/dsp/dsd_symbol.c:306-309), a fixed count
     // behind a sync (processYSF() reads 100 + 360 dibits for every frame type but FI = 3 with DT != 1, src/protocol/ysf/ysf.c)
-    static constexpr int sym_rate = PROTO == 2 ? 2400 : 4800;
-    static constexpr int win_len = PROTO == 1 ? 24 : (PROTO == 4 ? 8 : (PROTO == 5 ? 20 : 10)), t_max = PROTO == 2 ? 12 : 24;
-    static constexpr int warm_len = PROTO == 1 ? 24 : (PROTO == 4 ? 8 : (PROTO == 5 ? 20 : 10));
-    static constexpr int n_pat = PROTO == 1 ? 8 : (PROTO == 4 ? 12 : (PROTO == 5 ? 2 : 10));
-    static constexpr int confirm = (PROTO == 1 || PROTO == 4 || PROTO == 5) ? 0 : 1, dmr_window = PROTO == 1 ? 1 : 0, redigitize = PROTO == 1 ? 1 : 0;
+    // PROTO 6 dPMR (-fm): 2400 symbols/s on the 2400_4 hunt profile (level ring 12), the 12-symbol FS2 word compared exactly in the
+    // one polarity -xd selects (frame_sync_try_dpmr(), src/dsp/dsd_frame_sync.c:832-862), 12-symbol warm start, dpmr_filter
+    // (src/dsp/dsd_symbol.c:316-321), a fixed count behind a sync (processdPMRvoice() reads 372 dibits, dpmr_voice.c:397-425)
+    static constexpr int sym_rate = (PROTO == 2 || PROTO == 6) ? 2400 : 4800;
+    static constexpr int win_len = PROTO == 1 ? 24 : (PROTO == 4 ? 8 : (PROTO == 5 ? 20 : (PROTO == 6 ? 12 : 10)));
+    static constexpr int t_max = (PROTO == 2 || PROTO == 6) ? 12 : 24;
+    static constexpr int warm_len = PROTO == 1 ? 24 : (PROTO == 4 ? 8 : (PROTO == 5 ? 20 : (PROTO == 6 ? 12 : 10)));
+    static constexpr int n_pat = PROTO == 1 ? 8 : (PROTO == 4 ? 12 : (PROTO == 5 ? 2 : (PROTO == 6 ? 1 : 10)));
+    static constexpr int confirm = (PROTO == 1 || PROTO == 4 || PROTO == 5 || PROTO == 6) ? 0 : 1, dmr_window = PROTO == 1 ? 1 : 0, redigitize = PROTO == 1 ? 1 : 0;
     static constexpr bool m17 = PROTO == 4;
     static constexpr int slow_type = 0;
-    static constexpr int nt = PROTO == 2 ? DDN_NXDN48_FILTER_TAPS : DDN_DMR_FILTER_TAPS;
+    static constexpr int nt = PROTO == 2 ? DDN_NXDN48_FILTER_TAPS : (PROTO == 6 ? DDN_DPMR_FILTER_TAPS : DDN_DMR_FILTER_TAPS);
     int out_rate, rf_mod, use_filter, dbg;
 };
 
@@ -1649,7 +1654,7 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
 
 // always-on matched-filter stream (apply_sps_fir order: products added oldest first, mul and add rounded separately);
 // hist = the NT-1 samples before this call, rows of DDN_FSK4_MAX_TAPS-1 floats, right-aligned use as in ddn_slicer.hip
-template <int NT>
+template <int NT, int SET>
 __global__ __launch_bounds__(256) void
 k_fsk4_matched_filter(const float* __restrict__ in, long n, size_t stride, const float* __restrict__ hist,
                       float* __restrict__ out) {
@@ -1662,7 +1667,8 @@ k_fsk4_matched_filter(const float* __restrict__ in, long n, size_t stride, const
     typedef float mf2 __attribute__((ext_vector_type(2)));
     constexpr int T = 1024, NP = (T + NT + 3) / 2, NH = NP / 4 + 2;
     __shared__ mf2 E[4][NH], O[4][NH];
-    const unsigned int* bits = NT == DDN_DMR_FILTER_TAPS ? ddn_dmr_filter_bits : ddn_nxdn48_filter_bits;
+    // SET: the tap table (0 DMR, 1 NXDN48, 2 dPMR)
+    const unsigned int* bits = SET == 0 ? ddn_dmr_filter_bits : (SET == 1 ? ddn_nxdn48_filter_bits : ddn_dpmr_filter_bits);
     const int ch = blockIdx.y;
     const long t0 = (long)blockIdx.x * T;
     const int tid = threadIdx.x; // 128 threads
@@ -1966,11 +1972,11 @@ ddn_dev_fsk4_rx(const float* raw, const float* filt, const float* prev_tail, flo
     if (n_channels <= 0 || n <= 0) {
         return hipSuccess;
     }
-    if (protocol < 1 || protocol > 5) {
+    if (protocol < 1 || protocol > 6) {
         return hipErrorInvalidValue;
     }
-    if ((protocol == 4 || protocol == 5) && handlers) {
-        return hipErrorInvalidValue; // M17 / YSF frames are fixed counts: no handler family
+    if ((protocol == 4 || protocol == 5 || protocol == 6) && handlers) {
+        return hipErrorInvalidValue; // M17 / YSF / dPMR frames are fixed counts: no handler family
     }
     const DdnFec3Tables* htab = nullptr;
     if (handlers) {
@@ -2002,6 +2008,9 @@ ddn_dev_fsk4_rx(const float* raw, const float* filt, const float* prev_tail, flo
         }                                                                                                                  \
         if (protocol == 5) { /* YSF: 4800 symbols/s, fixed counts */                                                       \
             return launch<CPW_, 12, 5, false>(DDN_RX4_ARGS);                                                                \
+        }                                                                                                                  \
+        if (protocol == 6) { /* dPMR: 2400 symbols/s, fixed counts */                                                      \
+            return launch<CPW_, MAXW_, 6, false>(DDN_RX4_ARGS);                                                             \
         }                                                                                                                  \
         return handlers ? launch<CPW_, MAXW_, 2, true>(DDN_RX4_ARGS) : launch<CPW_, MAXW_, 2, false>(DDN_RX4_ARGS);         \
     } while (0)
@@ -2378,16 +2387,18 @@ ddn_dev_nxdn_crc(const uint8_t* bytes, int stride, int n, int kind, uint8_t* ok,
 }
 
 extern "C" hipError_t
-ddn_dev_fsk4_matched_filter(int nt, const float* in, long n, size_t stride, int n_channels, const float* hist, float* out,
+ddn_dev_fsk4_matched_filter(int nt, int tap_set, const float* in, long n, size_t stride, int n_channels, const float* hist, float* out,
                             hipStream_t st) {
     if (n_channels <= 0 || n <= 0) {
         return hipSuccess;
     }
     const dim3 grid((unsigned)((n + 1023) / 1024), (unsigned)n_channels);
-    if (nt == DDN_DMR_FILTER_TAPS) {
-        hipLaunchKernelGGL((k_fsk4_matched_filter<DDN_DMR_FILTER_TAPS>), grid, dim3(128), 0, st, in, n, stride, hist, out);
-    } else if (nt == DDN_NXDN48_FILTER_TAPS) {
-        hipLaunchKernelGGL((k_fsk4_matched_filter<DDN_NXDN48_FILTER_TAPS>), grid, dim3(128), 0, st, in, n, stride, hist, out);
+    if (nt == DDN_DMR_FILTER_TAPS && tap_set == 0) {
+        hipLaunchKernelGGL((k_fsk4_matched_filter<DDN_DMR_FILTER_TAPS, 0>), grid, dim3(128), 0, st, in, n, stride, hist, out);
+    } else if (nt == DDN_NXDN48_FILTER_TAPS && tap_set == 1) {
+        hipLaunchKernelGGL((k_fsk4_matched_filter<DDN_NXDN48_FILTER_TAPS, 1>), grid, dim3(128), 0, st, in, n, stride, hist, out);
+    } else if (nt == DDN_DPMR_FILTER_TAPS && tap_set == 2) {
+        hipLaunchKernelGGL((k_fsk4_matched_filter<DDN_DPMR_FILTER_TAPS, 2>), grid, dim3(128), 0, st, in, n, stride, hist, out);
     } else {
         return hipErrorInvalidValue;
     }

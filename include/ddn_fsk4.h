@@ -18,7 +18,12 @@
 extern "C" {
 #endif
 
-enum { DDN_FSK4_DMR = 1, DDN_FSK4_NXDN48 = 2, DDN_FSK4_NXDN96 = 3, DDN_FSK4_M17 = 4, DDN_FSK4_YSF = 5 };
+enum { DDN_FSK4_DMR = 1, DDN_FSK4_NXDN48 = 2, DDN_FSK4_NXDN96 = 3, DDN_FSK4_M17 = 4, DDN_FSK4_YSF = 5, DDN_FSK4_DPMR = 6 };
+/* dPMR (-fm): NXDN48's rate and hunt profile (2400 symbols/s, level ring 12), frame sync 2 compared exactly over 12 symbols in one
+ * polarity - the plain word, or with inverted = 1 (-xd) the inverted one (frame_sync_try_dpmr(), src/dsp/dsd_frame_sync.c:832-862;
+ * pattern index 0) -, 12-symbol warm start, dpmr_filter (RRC alpha 0.2, 135 taps at 20 samples per symbol, measured:
+ * tools/gen_tables_dpmr.py), lock_symbols[0] = 372 = the dibits processdPMRvoice() reads (CCH, 4 x 36 AMBE, colour code, CCH,
+ * 4 x 36 AMBE); no handler family.  Records hold the dibits as sliced: the -xd XOR with 2 belongs to the frame decoder. */
 /* YSF (-fy): the 20-symbol FUSION_SYNC compared exactly in both polarities (frame_sync_try_ysf(), src/dsp/dsd_frame_sync.c:770-797;
  * pattern index 0 = +YSF, 1 = -YSF), 20-symbol warm start, the DMR matched filter, lock_symbols[0] = 460 = the 100 FICH + 360 payload
  * dibits processYSF() reads (every frame type but FI = 3 with DT != 1, which reads the FICH alone); no handler family. */
@@ -40,7 +45,7 @@ typedef struct ddn_fsk4_rx_config {
     int protocol;           /* DDN_FSK4_* */
     int rf_mod;             /* 0 = C4FM window / slip / clip rules (-mc), 2 = GFSK rules (-mg; what an unlocked dsd-neo
                                switches to on a DMR sync, dsd_frame_sync.c:595-600) */
-    int inverted;           /* DMR only: opts->inverted_dmr */
+    int inverted;           /* DMR: opts->inverted_dmr; dPMR: opts->inverted_dpmr (which FS2 word is hunted); others 0 */
     int use_matched_filter; /* opts->use_cosine_filter (default 1 in the reference) */
     int lock_symbols[4];    /* per sync class; all zero = the defaults above (DMR voice default 54 + 6 * 288) */
 } ddn_fsk4_rx_config;
