@@ -380,9 +380,9 @@ fsk4_decode(ddn_fsk4_chain* c, int cur, int flush, hipStream_t st) {
         return DDN_OK;
     }
     if (c->dmr) {
-        // burst gather -> slot type Golay(20,8) -> BPTC(196,96)
-        DDN_TRY(ddn_dmr_burst_gather(rec, c->d_cnt_full, c->stride, c->d_spos, c->d_pre, c->d_ns, c->B, (size_t)c->myd, c->cfg.inverted,
-                                     c->d_st, c->d_info, c->d_cach, c->d_valid, st));
+        // burst gather -> slot type Golay(20,8) -> BPTC(196,96); an RC sync (pattern 8) carries no burst: its slot stays invalid
+        HIP_TRY(ddn_dev_dmr_burst_gather(rec, c->d_cnt_full, c->stride, c->d_spos, c->d_spat, c->d_pre, c->d_ns, c->B, (int)c->myd,
+                                         c->cfg.inverted, c->d_st, c->d_info, c->d_cach, c->d_valid, st));
         DDN_TRY(ddn_fec_block_code_batch(5 /* DDN_CODE_GOLAY_20_8 */, c->d_st, S, 1, nullptr, c->d_st_ok, st));
         DDN_TRY(ddn_fec_bptc_196x96_batch(c->d_info, 1, S, c->d_pdu, c->d_r3, c->d_errs, st));
         if (c->E && flush) { // no new records, no new decisions

@@ -33,11 +33,15 @@ struct Pat {
     int type, cls;
 };
 // type ids only need to be non-zero and distinct per family; these mirror synctype_ids.h + 1
-enum { T_BS_DATA = 11, T_BS_VOICE_NEG = 12, T_BS_VOICE = 13, T_BS_DATA_NEG = 14, T_MS_VOICE = 33, T_MS_DATA = 34, T_NX_POS = 29, T_NX_NEG = 30 };
+enum { T_BS_DATA = 11, T_BS_VOICE_NEG = 12, T_BS_VOICE = 13, T_BS_DATA_NEG = 14, T_MS_VOICE = 33, T_MS_DATA = 34, T_RC_DATA = 35, T_NX_POS = 29,
+       T_NX_NEG = 30 };
 const Pat kDmr[8] = {{"313333111331131131331131", T_BS_DATA, 0}, {"131111333113313313113313", T_BS_VOICE, 1},
                      {"311131133313133331131113", T_MS_DATA, 0}, {"133313311131311113313331", T_MS_VOICE, 1},
                      {"331333313111313133311111", T_MS_DATA, 0}, {"311311111333113333133311", T_MS_DATA, 0},
                      {"113111131333131311133333", T_MS_VOICE, 1}, {"133133333111331111311133", T_MS_VOICE, 1}};
+// the MS reverse-channel word and its complement (sync_patterns.h:74-75): frame_sync_try_dmr_rc_data(), src/dsp/dsd_frame_sync.c:1318-1334
+const char* const kDmrRc = "131331111133133133311313";
+const char* const kDmrRcInv = "313113333311311311133131";
 const char* const kNxPos[5] = {"3131331131", "3331331131", "3131331111", "3331331111", "3131311131"};
 const char* const kNxNeg[5] = {"1313113313", "1113113313", "1313113333", "1113113333", "1313133313"};
 
@@ -258,10 +262,18 @@ ddn_fsk4_rx_create(const ddn_fsk4_rx_config* cfg, ddn_fsk4_rx** out) {
             d.pat_class[k] = (uint8_t)cls;
             d.pat_neg[k] = (uint8_t)neg;
         }
+        // pattern 8, tried after the eight: the RC word has no voice / data partner (its complement is ETSI-reserved and claimed only
+        // under -xr), no digitize() polarity, and class 2 = the 12 dibits dmr_rc.c:39-44 reads beyond the 36 already behind the sync
+        d.n_pat = 9;
+        d.pat_bits[DDN_FSK4_DMR_RC_PAT] = sign_bits(cfg->inverted ? kDmrRcInv : kDmrRc);
+        d.pat_type[DDN_FSK4_DMR_RC_PAT] = T_RC_DATA;
+        d.pat_class[DDN_FSK4_DMR_RC_PAT] = DDN_FSK4_CLASS_RC;
+        d.pat_neg[DDN_FSK4_DMR_RC_PAT] = 0;
         d.nt = DDN_DMR_FILTER_TAPS;
         tap_bits = ddn_dmr_filter_bits;
         lock_default[0] = 120;
         lock_default[1] = 54 + 6 * 288;
+        lock_default[2] = 12;
     } else {
         const bool n96 = cfg->protocol == DDN_FSK4_NXDN96;
         d.sym_rate = n96 ? 4800 : 2400;
@@ -645,7 +657,7 @@ ddn_dmr_burst_gather(const uint8_t* d_records10, const int32_t* d_counts, size_t
         || n_channels <= 0) {
         return DDN_EINVAL;
     }
-    HIP_TRY(ddn_dev_dmr_burst_gather(d_records10, d_counts, max_symbols, d_sync_pos, d_pre, d_n_sync, n_channels, (int)max_syncs,
+    HIP_TRY(ddn_dev_dmr_burst_gather(d_records10, d_counts, max_symbols, d_sync_pos, nullptr, d_pre, d_n_sync, n_channels, (int)max_syncs,
                                      inverted, d_slot_type, d_info, d_cach, d_valid, (hipStream_t)hip_stream));
     return DDN_OK;
 }

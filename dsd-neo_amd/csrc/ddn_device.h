@@ -121,6 +121,9 @@ typedef struct DdnRxState { /* per-channel words of dsd_state / frame_sync_runti
 #define DDN_FSK4_MAX_TAPS 135
 #define DDN_FSK4_HIST     128 /* symbol / payload history kept per channel: 90 reachable + what the helper wave lags */
 #define DDN_FSK4_PRE      90
+#ifndef DDN_FSK4_DMR_RC_PAT
+#define DDN_FSK4_DMR_RC_PAT 8 /* == include/ddn_fsk4.h: the DMR table's MS reverse-channel row */
+#endif
 typedef struct DdnFsk4Config {
     int out_rate, sym_rate, rf_mod, win_len, t_max, warm_len, n_pat;
     uint32_t pat_bits[DDN_FSK4_MAX_PAT];
@@ -201,7 +204,7 @@ hipError_t ddn_dev_fsk4_rx(const float* raw, const float* filt, const float* pre
                            int max_sync, int channels_per_wave, int samples_per_symbol, int protocol, int handlers,
                            int32_t* hwords, uint8_t* hpay, int32_t* events, int32_t* n_events, hipStream_t st);
 hipError_t ddn_dev_dmr_burst_gather(const uint8_t* rec, const int32_t* counts, size_t max_sym, const int32_t* sync_pos,
-                                    const uint8_t* pre, const int32_t* n_sync, int n_channels, int max_sync, int inverted,
+                                    const uint8_t* sync_pat, const uint8_t* pre, const int32_t* n_sync, int n_channels, int max_sync, int inverted,
                                     uint8_t* slot_type, uint8_t* info, uint8_t* cach, uint8_t* valid, hipStream_t st);
 hipError_t ddn_dev_ambe2450_deinterleave(const uint8_t* dibits, const uint8_t* reliab, int n, uint8_t* fr, uint8_t* rl,
                                          hipStream_t st);

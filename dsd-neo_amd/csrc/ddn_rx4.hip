@@ -120,7 +120,7 @@ struct Fsk4Cfg {
     static constexpr int win_len = PROTO == 1 ? 24 : (PROTO == 4 ? 8 : (PROTO == 5 ? 20 : (PROTO == 6 ? 12 : 10)));
     static constexpr int t_max = (PROTO == 2 || PROTO == 6) ? 12 : 24;
     static constexpr int warm_len = PROTO == 1 ? 24 : (PROTO == 4 ? 8 : (PROTO == 5 ? 20 : (PROTO == 6 ? 12 : 10)));
-    static constexpr int n_pat = PROTO == 1 ? 8 : (PROTO == 4 ? 12 : (PROTO == 5 ? 2 : (PROTO == 6 ? 1 : 10)));
+    static constexpr int n_pat = PROTO == 1 ? 9 : (PROTO == 4 ? 12 : (PROTO == 5 ? 2 : (PROTO == 6 ? 1 : 10)));
     static constexpr int confirm = (PROTO == 1 || PROTO == 4 || PROTO == 5 || PROTO == 6) ? 0 : 1, dmr_window = PROTO == 1 ? 1 : 0, redigitize = PROTO == 1 ? 1 : 0;
     static constexpr bool m17 = PROTO == 4;
     static constexpr int slow_type = 0;
@@ -1558,7 +1558,7 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
                                             s.hidx = 90;
                                             s.lock_left = on ? next : 0;
                                         } else if (PROTO == 1) {
-                                            s.hmode = M_FIXED; // MS / direct-mode words: the configured count
+                                            s.hmode = M_FIXED; // MS / direct-mode / RC words: the configured count
                                         } else {
                                             s.hmode = M_NX_LICH;
                                             s.hidx = 0;
@@ -1775,12 +1775,13 @@ k_fsk4_filter_hist(int nt, const float* __restrict__ in, long n, size_t stride, 
 __constant__ uint8_t c_cach_il[24] = {0, 7, 8, 9, 1, 10, 11, 12, 2, 13, 14, 15, 3, 16, 4, 17, 18, 19, 5, 20, 21, 22, 6, 23};
 __global__ void
 k_dmr_burst_gather(const uint8_t* __restrict__ rec, const int32_t* __restrict__ counts, size_t max_sym,
-                   const int32_t* __restrict__ sync_pos, const uint8_t* __restrict__ pre, const int32_t* __restrict__ n_sync,
-                   int max_sync, int inverted, uint8_t* __restrict__ slot_type, uint8_t* __restrict__ info,
-                   uint8_t* __restrict__ cach, uint8_t* __restrict__ valid) {
+                   const int32_t* __restrict__ sync_pos, const uint8_t* __restrict__ sync_pat, const uint8_t* __restrict__ pre,
+                   const int32_t* __restrict__ n_sync, int max_sync, int inverted, uint8_t* __restrict__ slot_type,
+                   uint8_t* __restrict__ info, uint8_t* __restrict__ cach, uint8_t* __restrict__ valid) {
     const int k = blockIdx.x, ch = blockIdx.y, t = threadIdx.x; // 128 threads: t < 90 cached dibits, 90 <= t < 144 live
     const size_t so = (size_t)ch * max_sync + k;
-    const bool have = k < n_sync[ch] && k < max_sync;
+    // (sync_pat given: an RC sync - pattern 8 - carries no burst, its slot stays empty and invalid)
+    const bool have = k < n_sync[ch] && k < max_sync && !(sync_pat && sync_pat[so] == DDN_FSK4_DMR_RC_PAT);
     const long pos = have ? sync_pos[so] : 0;
     const bool live_ok = have && (pos + 54 < (long)counts[ch]) && ((size_t)(pos + 54) < max_sym);
     if (t == 0) {
@@ -2053,14 +2054,14 @@ ddn_dev_fsk4_rx(const float* raw, const float* filt, const float* prev_tail, flo
 }
 
 extern "C" hipError_t
-ddn_dev_dmr_burst_gather(const uint8_t* rec, const int32_t* counts, size_t max_sym, const int32_t* sync_pos, const uint8_t* pre,
-                         const int32_t* n_sync, int n_channels, int max_sync, int inverted, uint8_t* slot_type, uint8_t* info,
-                         uint8_t* cach, uint8_t* valid, hipStream_t st) {
+ddn_dev_dmr_burst_gather(const uint8_t* rec, const int32_t* counts, size_t max_sym, const int32_t* sync_pos, const uint8_t* sync_pat,
+                         const uint8_t* pre, const int32_t* n_sync, int n_channels, int max_sync, int inverted, uint8_t* slot_type,
+                         uint8_t* info, uint8_t* cach, uint8_t* valid, hipStream_t st) {
     if (n_channels <= 0 || max_sync <= 0) {
         return hipSuccess;
     }
     hipLaunchKernelGGL(k_dmr_burst_gather, dim3((unsigned)max_sync, (unsigned)n_channels), dim3(64), 0, st, rec, counts, max_sym,
-                       sync_pos, pre, n_sync, max_sync, inverted, slot_type, info, cach, valid);
+                       sync_pos, sync_pat, pre, n_sync, max_sync, inverted, slot_type, info, cach, valid);
     return hipGetLastError();
 }
 

@@ -33,10 +33,14 @@ enum { DDN_FSK4_DMR = 1, DDN_FSK4_NXDN48 = 2, DDN_FSK4_NXDN96 = 3, DDN_FSK4_M17 
  * it, polarity learnt from the preamble and cleared by EOT / carrier loss), fixed counts behind a sync (dispatch_m17.c:25-68):
  * lock_symbols[0] = 184 for every frame type and the EOT marker, lock_symbols[1] = 8 for the preamble; no handler family.
  * Sync pattern index: 0 / 1 preamble + / -, 2 / 3 EOT, 4 / 5 LSF, 6 / 7 BERT, 8 / 9 stream, 10 / 11 packet. */
-enum { DDN_FSK4_CLASS_DATA = 0, DDN_FSK4_CLASS_VOICE = 1 }; /* index into lock_symbols[] */
+enum { DDN_FSK4_CLASS_DATA = 0, DDN_FSK4_CLASS_VOICE = 1, DDN_FSK4_CLASS_RC = 2 }; /* index into lock_symbols[] */
 /* sync pattern index reported in flags bits 3..6 / d_sync_pat.  DMR: 0 BS data word, 1 BS voice word, 2 MS data, 3 MS voice,
  * 4 / 5 direct-mode TS1 / TS2 data, 6 / 7 direct-mode TS1 / TS2 voice (with inverted = 1 the data words mark voice bursts and
- * vice versa, as with -xr).  NXDN48: 0..4 FSW variants positive, 5..9 inverted. */
+ * vice versa, as with -xr), 8 the MS reverse-channel word (DMR_MS_RC_SYNC; with inverted = 1 its complement DMR_MS_RC_SYNC_INV,
+ * which is never claimed at normal polarity - src/dsp/dsd_frame_sync.c:1318-1334): lock class 2, default 12 symbols (dmr_rc.c:39-44
+ * reads 48 dibits, 36 of them already behind the sync).  The RC PDU is not decoded: the DMR burst consumers skip pattern 8.
+ * NXDN48: 0..4 FSW variants positive, 5..9 inverted. */
+#define DDN_FSK4_DMR_RC_PAT 8
 #define DDN_FSK4_PRE 90 /* payload dibits handed over with every accepted sync */
 
 typedef struct ddn_fsk4_rx_config {
@@ -47,7 +51,7 @@ typedef struct ddn_fsk4_rx_config {
                                switches to on a DMR sync, dsd_frame_sync.c:595-600) */
     int inverted;           /* DMR: opts->inverted_dmr; dPMR: opts->inverted_dpmr (which FS2 word is hunted); others 0 */
     int use_matched_filter; /* opts->use_cosine_filter (default 1 in the reference) */
-    int lock_symbols[4];    /* per sync class; all zero = the defaults above (DMR voice default 54 + 6 * 288) */
+    int lock_symbols[4];    /* per sync class; all zero = the defaults above (DMR voice default 54 + 6 * 288, DMR RC 12) */
 } ddn_fsk4_rx_config;
 typedef struct ddn_fsk4_rx ddn_fsk4_rx;
 

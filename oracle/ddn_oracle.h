@@ -303,6 +303,7 @@ long orc_cqrx_run(orc_cqrx* r, const float* sym, long n, int* rec4, uint8_t* fla
 size_t orc_cqrx_sizeof(void);
 size_t orc_cqrx_slicer_offset(void);
 void orc_cqrx_get_state(const orc_cqrx* r, float out8[8]);
+void orc_cqrx_prime(orc_cqrx* r, float center, float min, float max);
 int orc_cq_reliability(float sym_c, double snr_db);
 void orc_cq_digitize(const orc_slicer* s, float sym, int map_idx, int negative, double snr_db, int rec4[4]);
 void orc_cq_inframe_step(orc_slicer* s, float sym, int map_idx, int negative, double snr_db, int rec4[4]);
@@ -361,6 +362,8 @@ typedef struct orc_fsk4rx {
     int sync_thr_max, sync_thr_n;
 } orc_fsk4rx;
 void orc_fsk4rx_set_sync_thresholds(orc_fsk4rx* r, float* buf, int max_syncs);
+void orc_fsk4rx_prime(orc_fsk4rx* r, int lastsync, int m17_pol, const float thr7[7]);
+void orc_fsk4rx_get_levels(const orc_fsk4rx* r, float out2[2]);
 void orc_fsk4rx_set_events(orc_fsk4rx* r, orc_hevents* ev);
 void orc_p25rx_set_events(orc_p25rx* r, orc_hevents* ev);
 void orc_fsk4rx_init(orc_fsk4rx* r, const orc_fsk4_profile* p);

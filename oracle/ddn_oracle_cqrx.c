@@ -522,3 +522,20 @@ orc_cqrx_get_state(const orc_cqrx* r, float out8[8]) {
     out8[6] = (float)r->hunt_pos;
     out8[7] = (float)r->sl.midx;
 }
+
+/* Test hook for the reference's frame-sync known answers (tests/test_oracle_framesync_kat.py): the slicer's centre / min / max as
+ * those tests set them, the extrema average holding min / max alone. */
+void
+orc_cqrx_prime(orc_cqrx* r, float center, float min, float max) {
+    orc_slicer* s = &r->sl;
+    s->center = center;
+    s->min = min;
+    s->max = max;
+    for (int i = 0; i < ORC_SLICER_MSIZE; i++) {
+        s->minbuf[i] = min;
+        s->maxbuf[i] = max;
+    }
+    s->sums_valid = 0;
+    r->lmin = min;
+    r->lmax = max;
+}

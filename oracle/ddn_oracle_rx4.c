@@ -13,7 +13,7 @@
  *                                  2400-baud profile); sign dibit :2110-2127; 4-level payload dibit + reliability stored
  *                                  while hunting :2161-2189; level window :2316-2336; timeouts :2753-2760,3037-3053
  *       P25p1 accept               :603-625,698-716 (as ddn_oracle_rx.c)
- *       DMR accept                 :1102-1106,1150-1260 (+ MS / direct-mode :1108-1314): basic lock :385-392, then
+ *       DMR accept                 :1102-1106,1150-1260 (+ MS / direct-mode :1108-1314, RC :1318-1334): basic lock :385-392, then
  *                                  dmr_resample_on_sync() src/dsp/dmr_sync.c:109-131 = warm start over the 24 sync
  *                                  symbols + re-digitisation of the 66 payload dibits before the sync :63-103
  *       NXDN accept                :1507-1556: 10-symbol window, five patterns per polarity, a match first only becomes
@@ -618,4 +618,29 @@ orc_fsk4rx_get_thresholds(const orc_fsk4rx* r, float out7[7]) {
     out7[4] = r->sl.min;
     out7[5] = r->sl.maxref;
     out7[6] = r->sl.minref;
+}
+
+/* Test hooks for the reference's frame-sync known answers (tests/test_oracle_framesync_kat.py): start the loop from a primed state as
+ * those tests do - state->lastsynctype (this project's id, 0 = none), state->m17_polarity, and the slicer words thr7 = {center, umid,
+ * lmid, max, min, maxref, minref} (the hunt's level window starts from min / max, as hunt_enter() does) - and read the hunting level
+ * window's last estimate out2 = {lmin, lmax}. */
+void
+orc_fsk4rx_prime(orc_fsk4rx* r, int lastsync, int m17_pol, const float thr7[7]) {
+    r->lastsync = lastsync;
+    r->m17_pol = m17_pol;
+    r->sl.center = thr7[0];
+    r->sl.umid = thr7[1];
+    r->sl.lmid = thr7[2];
+    r->sl.max = thr7[3];
+    r->sl.min = thr7[4];
+    r->sl.maxref = thr7[5];
+    r->sl.minref = thr7[6];
+    r->lmin = r->sl.min;
+    r->lmax = r->sl.max;
+}
+
+void
+orc_fsk4rx_get_levels(const orc_fsk4rx* r, float out2[2]) {
+    out2[0] = r->lmin;
+    out2[1] = r->lmax;
 }

@@ -18,6 +18,7 @@ DMR_BS_DATA, DMR_BS_VOICE = "313333111331131131331131", "13111133311331331311331
 DMR_MS_DATA, DMR_MS_VOICE = "311131133313133331131113", "133313311131311113313331"
 DMR_DM1_DATA, DMR_DM1_VOICE = "331333313111313133311111", "113111131333131311133333"
 DMR_DM2_DATA, DMR_DM2_VOICE = "311311111333113333133311", "133133333111331111311133"
+DMR_MS_RC, DMR_MS_RC_INV = "131331111133133133311313", "313113333311311311133131"   # sync_patterns.h:74-75
 NXDN_POS = ["3131331131", "3331331131", "3131331111", "3331331111", "3131311131"]
 NXDN_NEG = ["1313113313", "1113113313", "1313113333", "1113113333", "1313133313"]
 
@@ -26,7 +27,7 @@ YSF_SYNC = "31111311313113131131"      # FUSION_SYNC, include/dsd-neo/core/sync_
 T_YSF_POS, T_YSF_NEG = 31, 32
 # sync type ids carried in lastsync (any non-zero numbering works; these mirror synctype_ids.h + 1 so 0 stays "none")
 T_P25_POS, T_P25_NEG = 1, 2
-T_DMR_BS_DATA, T_DMR_BS_VOICE, T_DMR_MS_VOICE, T_DMR_MS_DATA = 11, 13, 33, 34
+T_DMR_BS_DATA, T_DMR_BS_VOICE, T_DMR_MS_VOICE, T_DMR_MS_DATA, T_DMR_RC_DATA = 11, 13, 33, 34, 35
 T_NXDN_POS, T_NXDN_NEG = 29, 30
 # M17: the twelve outcomes of frame_sync_try_m17() in the order the loops number them (flags pattern index / sync_pat)
 M17_PRE_POS, M17_PRE_NEG, M17_EOT_POS, M17_EOT_NEG, M17_LSF_POS, M17_LSF_NEG = 0, 1, 2, 3, 4, 5
@@ -34,7 +35,8 @@ M17_BRT_POS, M17_BRT_NEG, M17_STR_POS, M17_STR_NEG, M17_PKT_POS, M17_PKT_NEG = 6
 M17_TYPES = [99, 100, 101, 102, 17, 18, 77, 78, 9, 10, 87, 88]      # synctype_ids.h:52-63, + 1
 M17_WORDS = {"LSF": "11113313", "STR": "33331131", "PRE": "31313131", "PIV": "13131313", "BRT": "31331111", "PKT": "13113333",
              "EOT": "11111131", "EOT_INV": "33333313"}                # include/dsd-neo/core/sync_patterns.h:18-28
-CLASS_DATA, CLASS_VOICE = 0, 1
+CLASS_DATA, CLASS_VOICE, CLASS_RC = 0, 1, 2
+DMR_PAT_RC = 8      # the MS reverse-channel word's row in the DMR table
 
 
 def bits_of(pattern):
@@ -86,8 +88,12 @@ def profile(proto, rf_mod=0, use_filter=1, lock=None, out_rate=48000, inverted=0
             swap = {T_DMR_BS_DATA: (T_BS_VOICE_NEG, 1), T_DMR_BS_VOICE: (T_BS_DATA_NEG, 1), T_DMR_MS_DATA: (T_DMR_MS_VOICE, 0),
                     T_DMR_MS_VOICE: (T_DMR_MS_DATA, 0)}
             pats = [(s_, swap[t][0], swap[t][1], cl ^ 1) for (s_, t, neg, cl) in pats]
+        # frame_sync_try_dmr_rc_data() (src/dsp/dsd_frame_sync.c:1318-1334), tried after the eight: the RC word has no voice / data
+        # partner - its complement is ETSI-reserved, claimed only under -xr - and no digitize() polarity; class 2 = the 12 dibits
+        # dmr_rc.c:39-44 still reads behind the sync (48 in all, 36 of them already behind it)
+        pats.append((DMR_MS_RC_INV if inverted else DMR_MS_RC, T_DMR_RC_DATA, 0, CLASS_RC))
         taps = _taps("dmr")
-        lock = lock or [120, 54 + 288 * 6, 0, 0]
+        lock = lock or [120, 54 + 288 * 6, 12, 0]
     elif proto == PROTO_M17:
         # -fz: C4FM lock at 4800 symbols/s, no matched filter (decode_mode_apply_m17: use_cosine_filter = 0), 8-symbol words matched
         # with one error allowed by frame_sync_try_m17() (the pattern table only names the twelve outcomes: type, polarity, class);
