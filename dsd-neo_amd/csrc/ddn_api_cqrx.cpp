@@ -151,9 +151,13 @@ ddn_cq_rx_get_state(ddn_cq_rx* b, int channel, float out8[8]) {
     HIP_TRY(hipDeviceSynchronize());
     static DdnCqState h; // (10 KB: not on the stack)
     HIP_TRY(hipMemcpy(&h, b->d_state + channel, sizeof(h), hipMemcpyDeviceToHost));
-    out8[0] = (h.max + h.min) / 2.0f;
-    out8[1] = h.max;
-    out8[2] = h.min;
+    // the slicer's words as the reference's state holds them: a hunting symbol's fast path puts max / min at +-3 (and the centre at
+    // 0), and only the level estimate - from the eighth symbol after the hunt began - moves them again; the kernel keeps the
+    // extrema average's values instead, which nothing reads in between
+    const bool fast_path = !h.have_sync && h.hist_count > 0 && h.hist_count < 8;
+    out8[1] = fast_path ? 3.0f : h.max;
+    out8[2] = fast_path ? -3.0f : h.min;
+    out8[0] = (out8[1] + out8[2]) / 2.0f;
     out8[3] = (float)h.map_idx;
     out8[4] = (float)h.lastsync;
     out8[5] = (float)h.have_sync;

@@ -34,6 +34,7 @@ struct Lds {
     // recurrence - and one written per in-frame symbol): 8 KB less LDS per channel, sixteen channels per CU instead of nine
     float sbuf[SSZ];
     float lbuf[24], shist[24];
+    float lsort[24]; // the level ring sorted in the reference's order, when it holds a NaN
     Scratch sc;
 };
 
@@ -99,7 +100,52 @@ bit_magnitude(float sym, const float ideal[4], int bit_index) { // soft_metric_f
         spacing = 2.0f;
     }
     const float scale = 255.0f / (spacing * spacing);
-    return clamp255(__float2int_rn(fabsf(best0 - best1) * scale));
+    // (int)lrintf(): a 64-bit long cut to int (x86-64), not a saturating conversion.  Below 2^31 the two agree and the 32-bit one is
+    // a single instruction; from 2^31 on (and for a NaN) the low 32 bits of the 64-bit conversion
+    const float v = fabsf(best0 - best1) * scale;
+    return clamp255(v < 2147483648.0f ? __float2int_rn(v) : (int)__float2ll_rn(v));
+}
+
+// the reference's scan of the slicer window in slot order (window_extrema128): only for a window holding a NaN, out of line so the
+// per-symbol path keeps its registers
+__device__ __noinline__ void
+window_extrema_in_order(const float* w, float& lo1, float& lo2, float& hi1, float& hi2) {
+    lo1 = w[0], lo2 = w[1], hi1 = lo1, hi2 = lo2;
+    if (lo2 < lo1) {
+        const float t = lo1;
+        lo1 = lo2, lo2 = t;
+    }
+    if (hi2 > hi1) {
+        const float t = hi1;
+        hi1 = hi2, hi2 = t;
+    }
+    for (int i = 2; i < SSZ; i++) {
+        const float v = w[i];
+        if (v < lo1) {
+            lo2 = lo1, lo1 = v;
+        } else if (v < lo2) {
+            lo2 = v;
+        }
+        if (v > hi1) {
+            hi2 = hi1, hi1 = v;
+        } else if (v > hi2) {
+            hi2 = v;
+        }
+    }
+}
+
+// the reference's insertion sort of the level ring (frame_sync_window_levels): only for a ring holding a NaN, out of line as above
+__device__ __noinline__ void
+sort_in_order(const float* ring, float* out, int n) {
+    for (int i = 0; i < n; i++) {
+        const float x = ring[i];
+        int q = i - 1;
+        while (q >= 0 && out[q] > x) {
+            out[q + 1] = out[q];
+            q--;
+        }
+        out[q + 1] = x;
+    }
 }
 
 // the nominal level of each corrected dibit under the lock's dibit map and polarity: what the soft metrics measure against.  It only
@@ -444,23 +490,30 @@ k_cq_rx(const float* __restrict__ symbols, const int32_t* __restrict__ counts_in
                     L.sbuf[sidx] = x;
                 }
                 float lo1 = w_lo1, lo2 = w_lo2, hi1 = w_hi1, hi2 = w_hi2;
-                if (!win_ok || !(old > w_lo2 && old < w_hi2) || !(x != 0.0f)) {
+                if (!win_ok || !(old > w_lo2 && old < w_hi2) || !(x == x) || x == 0.0f) {
                     wave_sync();
                     const float a = L.sbuf[lane], b = L.sbuf[lane + 64];
-                    lo1 = a < b ? a : b, lo2 = a < b ? b : a, hi1 = lo2, hi2 = lo1;
+                    if (__ballot(!(a == a) || !(b == b))) {
+                        // a NaN in the window: the reference's scan in slot order (window_extrema128), whose result depends on where
+                        // the NaN sits - in slot 0 or 1 it seeds the extrema and comes out, further on every compare with it is false.
+                        // Every lane runs it on the same LDS words; the butterfly below follows neither rule.
+                        window_extrema_in_order(L.sbuf, lo1, lo2, hi1, hi2);
+                        win_ok = false; // (not carried: the next symbol scans again until the NaN has left the window)
+                    } else {
+                        lo1 = a < b ? a : b, lo2 = a < b ? b : a, hi1 = lo2, hi2 = lo1;
 #pragma unroll
-                    for (int off = 32; off >= 1; off >>= 1) {
-                        const float o1 = __shfl_xor(lo1, off), o2 = __shfl_xor(lo2, off);
-                        const float n1 = lo1 < o1 ? lo1 : o1, mx = lo1 < o1 ? o1 : lo1, m2 = lo2 < o2 ? lo2 : o2;
-                        lo2 = mx < m2 ? mx : m2;
-                        lo1 = n1;
-                        const float p1 = __shfl_xor(hi1, off), p2 = __shfl_xor(hi2, off);
-                        const float g1 = hi1 > p1 ? hi1 : p1, mn = hi1 > p1 ? p1 : hi1, g2 = hi2 > p2 ? hi2 : p2;
-                        hi2 = mn > g2 ? mn : g2;
-                        hi1 = g1;
+                        for (int off = 32; off >= 1; off >>= 1) {
+                            const float o1 = __shfl_xor(lo1, off), o2 = __shfl_xor(lo2, off);
+                            const float n1 = lo1 < o1 ? lo1 : o1, mx = lo1 < o1 ? o1 : lo1, m2 = lo2 < o2 ? lo2 : o2;
+                            lo2 = mx < m2 ? mx : m2;
+                            lo1 = n1;
+                            const float p1 = __shfl_xor(hi1, off), p2 = __shfl_xor(hi2, off);
+                            const float g1 = hi1 > p1 ? hi1 : p1, mn = hi1 > p1 ? p1 : hi1, g2 = hi2 > p2 ? hi2 : p2;
+                            hi2 = mn > g2 ? mn : g2;
+                            hi1 = g1;
+                        }
+                        win_ok = true; // (ordered values: the two smallest / largest do not depend on the order of the scan)
                     }
-                    // (a scan that met a NaN is not carried: its compares have no order to update from)
-                    win_ok = (lo1 == lo1) && (lo2 == lo2) && (hi1 == hi1) && (hi2 == hi2);
                 } else {
                     if (x < lo1) {
                         lo2 = lo1;
@@ -520,7 +573,18 @@ k_cq_rx(const float* __restrict__ symbols, const int32_t* __restrict__ counts_in
                         const float vq = L.lbuf[q];
                         rank += (vq < v || (vq == v && q < lane)) ? 1 : 0;
                     }
+                    // a NaN in the ring has no rank: the reference's insertion sort (by one lane, into LDS) decides where it sits
+                    const bool nan_ring = __ballot(act && !(v == v)) != 0;
+                    if (nan_ring) {
+                        if (lane == 0) {
+                            sort_in_order(L.lbuf, L.lsort, level_count);
+                        }
+                        wave_sync();
+                    }
                     auto sorted_at = [&](int k) {
+                        if (nan_ring) {
+                            return L.lsort[k];
+                        }
                         const unsigned long long m = __ballot(act && rank == k);
                         return bcast(v, __ffsll((long long)m) - 1);
                     };

@@ -568,7 +568,8 @@ int ddn_cq_rx_create(const ddn_cq_rx_config* cfg, ddn_cq_rx** out);
 void ddn_cq_rx_destroy(ddn_cq_rx* b);
 int ddn_cq_rx_reset(ddn_cq_rx* b, void* hip_stream);
 /* d_events i32 [B][max_events][4] {record index in this call, kind, a, b}, d_n_events i32 [B] (per call), d_event_data i32
- * [B][max_events][4] or NULL: kinds and words as ddn_p25_rx_set_events / ddn_p25_rx_set_event_data */
+ * [B][max_events][4] or NULL: kinds and words as ddn_p25_rx_set_events / ddn_p25_rx_set_event_data.  A call keeps its first
+ * max_events events; d_n_events counts all it produced, so a value above max_events says the rest were dropped */
 int ddn_cq_rx_set_events(ddn_cq_rx* b, int32_t* d_events, int32_t* d_n_events, int32_t* d_event_data, size_t max_events);
 int ddn_cq_rx_run(ddn_cq_rx* b, const float* d_symbols, const int32_t* d_counts_in, size_t n, size_t sym_stride, uint8_t* d_records10,
                   uint8_t* d_flags, int32_t* d_counts, size_t max_symbols, void* hip_stream);

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import cqrx_edge
 import orc
 from conftest import golden
 
@@ -32,15 +33,29 @@ def test_in_frame_path_equals_the_compiled_dsd_dibit(synctype, map_idx, snr):
     # symbols with a DC offset (the centre has to follow), outliers and exact threshold hits
     sym = _symbols(synctype * 7 + map_idx, 2600, offset=0.2)
     sym[100:110] = [2.0, -2.0, 0.0, 7.5, -9.0, 1.9999999, -2.0000002, 4.0, 0.5, -0.5]
-    h = r.refh_cq_slicer_create(synctype, map_idx, snr)
-    want = np.zeros((len(sym), 4), np.int32)
-    thr = np.zeros((len(sym), 5), np.float32)
-    r.refh_cq_slicer_run(h, sym.ctypes.data, len(sym), want.ctypes.data, thr.ctypes.data)
-    r.refh_cq_slicer_destroy(h)
-    got, gthr = orc.oracle_cq_inframe(sym, map_idx, 1 if synctype in (P25P1_NEG, P25P2_NEG) else 0, snr)
+    negative = 1 if synctype in (P25P1_NEG, P25P2_NEG) else 0
+
+    def both(x):
+        h = r.refh_cq_slicer_create(synctype, map_idx, snr)
+        want = np.zeros((len(x), 4), np.int32)
+        thr = np.zeros((len(x), 5), np.float32)
+        r.refh_cq_slicer_run(h, x.ctypes.data, len(x), want.ctypes.data, thr.ctypes.data)
+        r.refh_cq_slicer_destroy(h)
+        got, gthr = orc.oracle_cq_inframe(x, map_idx, negative, snr)
+        return got, gthr, want, thr
+
+    got, gthr, want, thr = both(sym)
     assert np.array_equal(got, want), np.flatnonzero((got != want).any(axis=1))[:5]
     assert np.array_equal(gthr.view(np.uint32), thr.view(np.uint32))
     assert len(np.unique(want[:, 0])) == 4 and want[:, 1].min() < 100 < want[:, 1].max()
+    # the edges (tests/cqrx_edge.py: NaN by window slot, infinities, signed-zero runs, denormals, ties, exact thresholds, magnitudes up
+    # to 3e38) on a shorter carrier: records and thresholds bit for bit, NaN payloads included
+    carrier = _symbols(synctype * 11 + map_idx + 1, 1100, offset=0.2)
+    for k, name in enumerate(cqrx_edge.edge_names()):
+        x = cqrx_edge.edge_stream(name, carrier, 300 + 7 * k, seed=k)
+        got, gthr, want, thr = both(x)
+        assert np.array_equal(got, want), (name, np.flatnonzero((got != want).any(axis=1))[:5])
+        assert np.array_equal(gthr.view(np.uint32), thr.view(np.uint32)), (name, np.flatnonzero((gthr.view(np.uint32) != thr.view(np.uint32)).any(axis=1))[:5])
 
 
 def _capture_symbols(name):
