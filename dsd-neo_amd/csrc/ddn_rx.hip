@@ -2097,6 +2097,7 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
     long long dbg_blk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dbg_bt = 0; // bulk hunting pass, by section
 #define DBG_BLK(k) do { if (DDN_RX_CYCLES && (cfg.dbg & 8192)) { const long long n_ = (long long)clock64(); dbg_blk[k] += n_ - dbg_bt; dbg_bt = n_; } } while (0)
     long long dbg_run[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // lean runs: count, trips, -, -, -, runs polling a mailbox, cycles inside the run, phases
+    long long dbg_ent[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // a lean run's entry, by part: queue hand-over, lean tests + entry proof, run length
     if (HM && loader) {
         // Handler mode, staging wave: job j of recurrence wave h's channels (stage tile j + 1, drain tile j - 1's queue, the
         // window summaries of checkpoint j) falls due when that wave has finished tile j - 1, and lets it into tile j + 1; job
@@ -2780,6 +2781,13 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                 if (DDN_RX_CYCLES && (cfg.dbg & 8192)) {
                     dbg_p1 = (long long)clock64();
                 }
+                // The first lean trip's operands - the five window samples of this lane's next symbol and the suffix summary its
+                // window push asks for - fetched before the queue hand-over and the lean tests, so that the two LDS round trips run
+                // under those instead of in front of the run's first trip.  A lane that enters no run leaves them unread; for a
+                // lane that does, the addresses are the ones the run's first trip read before (sp + whole <= tn, npp + npc < WMW).
+                const float* pw0 = (s.filter_on ? frow : rrow) + base + (live ? sp : 0) + ((whole - 1) / 2 - 2);
+                const float e0 = pw0[0], e1 = pw0[1], e2 = pw0[2], e3 = pw0[3], e4 = pw0[4];
+                const float4 esf = *reinterpret_cast<const float4*>(&L.sfx[sbuf_sel][min(npp + npc, WMW - 1)][ln][0]);
                 // hand the previous trip's symbols (one per lane at most) to wave 1: one 16-byte LDS write at a wave-uniform slot
                 if (!respin) {
                     if (offload && tk > 0 && tk <= QTW && lane < LPR) {
@@ -2789,6 +2797,10 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                     tk++;
                 }
                 respin = false;
+                long long dbg_h1 = 0;
+                if (DDN_RX_CYCLES && (cfg.dbg & 8192)) {
+                    dbg_h1 = (long long)clock64();
+                }
                 if (DDN_RX_CYCLES && (cfg.dbg & 8192)) {
                     const long long now = (long long)clock64();
                     if (dbg_kind >= 0) {
@@ -2840,6 +2852,10 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                     const bool lean_wait = lean_state & !(sp + whole <= tn) & more;
                     const bool all_lean = !__any(alive & !(lean | lean_wait | hunt_wait));
                     if (all_lean && __any(lean)) {
+                        long long dbg_h2 = 0;
+                        if (DDN_RX_CYCLES && (cfg.dbg & 8192)) {
+                            dbg_h2 = (long long)clock64();
+                        }
                         dbg_kind = 2;
                         const int k0 = (whole - 1) / 2 - 2;
                         // A lean run: K trips back to back, K known before the first one - the fewest symbols any lean lane still has
@@ -2861,15 +2877,26 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                             kl = min(kl, MS - s.midx);
                             kl = hp ? min(kl, ddn_p25h::HN - s.hw) : kl;
                         }
-                        int K = 0x7fffffff;
-                        {
-                            const unsigned long long lm = __ballot(lean);
-                            for (int c = 0; c < LPR; c++) {
-                                if ((lm >> c) & 1) {
-                                    K = min(K, __builtin_amdgcn_readlane(kl, c));
-                                }
-                            }
+                        // K = the smallest kl of lanes 0 .. LPR - 1 (a lane that is not lean holds INT_MAX): a DPP min tree inside each
+                        // group of LPR lanes, read from lane 0 - no per-lane readlane and scalar branch
+                        int kr = kl;
+                        if constexpr (LPR > 1) {
+                            kr = min(kr, __builtin_amdgcn_update_dpp(0x7fffffff, kr, 0xB1, 0xF, 0xF, false));  // quad_perm [1,0,3,2]
                         }
+                        if constexpr (LPR > 2) {
+                            kr = min(kr, __builtin_amdgcn_update_dpp(0x7fffffff, kr, 0x4E, 0xF, 0xF, false));  // quad_perm [2,3,0,1]
+                        }
+                        if constexpr (LPR > 4) {
+                            kr = min(kr, __builtin_amdgcn_update_dpp(0x7fffffff, kr, 0x141, 0xF, 0xF, false)); // row_half_mirror
+                        }
+                        if constexpr (LPR > 8) {
+                            kr = min(kr, __builtin_amdgcn_update_dpp(0x7fffffff, kr, 0x140, 0xF, 0xF, false)); // row_mirror
+                        }
+                        int K = __builtin_amdgcn_readlane(kr, 0);
+                        if constexpr (LPR > 16) {
+                            K = min(K, __builtin_amdgcn_readlane(kr, 16));
+                        }
+                        static_assert(LPR >= 1 && LPR <= 32, "the run length's min tree covers up to 32 lanes");
                         K = min(K, QTW - tk + 1);
                         if (HM && __any(hwait)) { // an answer may arrive: look again soon
                             K = min(K, 2);
@@ -2887,6 +2914,9 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                             dbg_l0 = (long long)clock64();
                             dbg_run[2] += dbg_p1 - dbg_p0;  // pass top: handler answers, bulk-pass test
                             dbg_run[3] += dbg_l0 - dbg_p1;  // queue hand-over, lean tests, entry proof, run length
+                            dbg_ent[0] += dbg_h1 - dbg_p1;  // the first trip's operand fetch issued, queue hand-over
+                            dbg_ent[1] += dbg_h2 - dbg_h1;  // lean tests, entry proof
+                            dbg_ent[2] += dbg_l0 - dbg_h2;  // run length
                         }
                         if (lean) {
                             const float* pw = (s.filter_on ? frow : rrow) + base + sp + k0;
@@ -2902,8 +2932,8 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                             uint32_t rof = ro;
                             float mn = s.min, mx = s.max;
                             double smin = s.min_sum, smax = s.max_sum;
-                            float x0 = pw[0], x1 = pw[1], x2 = pw[2], x3 = pw[3], x4 = pw[4];
-                            float4 sf4 = *psp;
+                            float x0 = e0, x1 = e1, x2 = e2, x3 = e3, x4 = e4; // (= pw[0 .. 4] and *psp, fetched at the pass's top)
+                            float4 sf4 = esf;
                             float sym = 0.0f;
                             int fw = (1 | (s.lastsync == 2 ? 4 : 0)) | ((o - o_tile) << 8);
                             for (int j = 0; j < K; j++) {
@@ -3434,6 +3464,7 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                 d2[k] = reinterpret_cast<const uint8_t*>(dbg_sec)[k];
                 d2[k - 64] = reinterpret_cast<const uint8_t*>(dbg_run)[k];
                 d2[k - 128] = reinterpret_cast<const uint8_t*>(dbg_blk)[k];
+                d2[k - 256] = reinterpret_cast<const uint8_t*>(dbg_ent)[k];
             }
         }
     }

@@ -112,6 +112,9 @@ for mode, cpw in [(m, int(c)) for m, c in (x.split(":") for x in os.environ.get(
             run[0] / (len(sec) * tiles), run[1] / max(1, run[0]), run[7] / max(1, run[0]), run[5] / max(1, run[0]), run[6] / max(1, run[1]))
         extra += "\n   a lean run's pass: %.0f cycles from the pass's top to the bulk test's end, %.0f from there to the run's first trip" % (
             run[2] / max(1, run[0]), run[3] / max(1, run[0]))
+        ent = np.stack([r[c, -512:-448] for c in range(0, B, cpw)]).copy().view(np.int64).sum(axis=0)
+        extra += "\n   that entry by part: queue hand-over %.0f, lean tests + entry proof %.0f, run length %.0f cycles" % tuple(
+            ent[k] / max(1, run[0]) for k in range(3))
     if mode == "handlers" and int(os.environ.get("DDN_RX_DBG", "0"), 0) & 8192:
         hm = np.stack([r[c, -448:-384] for c in range(0, B, cpw)]).copy().view(np.int64).sum(axis=0)
         extra += "\n   handler wave per tile: filter passes %.2f at %.0f cycles, decisions %.2f at %.0f cycles, idle polls %.1f" % (
