@@ -413,6 +413,11 @@ PROTOTYPES.update({
     "ddn_m17_str_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 4 + [C.c_int, C.c_size_t] + [C.c_void_p] * 5),
     "ddn_m17_lich_assemble_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 9),
     "ddn_ysf_fich_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3 + [C.c_int, C.c_size_t] + [C.c_void_p] * 4),
+    "ddn_dpmr_superframe_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3 + [C.c_int, C.c_size_t, C.c_int]
+                                         + [C.c_void_p] * 8),
+    "ddn_dpmr_identity_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 11),
+    "ddn_dpmr_voice_gather": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_int] + [C.c_void_p] * 6),
+    "ddn_dpmr_air_interface_id": (None, [C.c_uint32, C.c_char_p]),
     "ddn_ysf_payload_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3 + [C.c_int, C.c_size_t] + [C.c_void_p] * 12),
     "ddn_fsk4_rx_get_timing": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_mode_config": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
@@ -536,6 +541,20 @@ class Fsk4ChainResults(C.Structure):  # == ddn_fsk4_chain_results
                                   "d_ysf_imbe_voice_slot", "d_ysf_imbe_voice_skip", "d_ysf_imbe_voice_result", "d_ysf_imbe_pcm")]
 
 
+class DpmrChainResults(C.Structure):  # == ddn_dpmr_chain_results
+    _fields_ = [("max_syncs", C.c_size_t), ("voice_frames", C.c_int)] + [
+        (k, C.c_void_p) for k in ("d_n_sync", "d_sync_pos", "d_valid", "d_cch_bits2x48", "d_ham_ok2x6", "d_crc_ok2", "d_fields2x8", "d_id",
+                                  "d_color", "d_kind", "d_strong", "d_tg", "d_src", "d_ambe_fr", "d_voiced2", "d_muted2", "d_n_voice",
+                                  "d_voice_slot", "d_voice_half", "d_voice_muted", "d_voice_skip", "d_voice_result", "d_pcm")]
+
+
+def dpmr_air_interface_id(v):
+    """ddn_dpmr_air_interface_id: the seven characters the reference prints for a raw 24-bit dPMR ID"""
+    out = C.create_string_buffer(8)
+    lib().ddn_dpmr_air_interface_id(int(v) & 0xFFFFFFFF, out)
+    return out.value.decode("latin-1")
+
+
 class MixedChainConfig(C.Structure):  # == ddn_mixed_chain_config
     _fields_ = [("n_p25", C.c_int), ("n_dmr", C.c_int), ("n_nxdn48", C.c_int), ("samples_per_call", C.c_int), ("block_len", C.c_int),
                 ("input_format", C.c_int), ("vocoder", C.c_int), ("overlap", C.c_int)]
@@ -576,6 +595,7 @@ PROTOTYPES.update({
     "ddn_fsk4_chain_destroy": (None, [C.c_void_p]),
     "ddn_fsk4_chain_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ddn_fsk4_chain_get_results": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ddn_fsk4_chain_get_dpmr_results": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_fsk4_chain_flush": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_fsk4_chain_front_end": (C.c_void_p, [C.c_void_p]),
     "ddn_fsk4_chain_rx": (C.c_void_p, [C.c_void_p]),
@@ -630,6 +650,12 @@ class Fsk4ChainC:
     def results(self):
         r = Fsk4ChainResults()
         _check(lib().ddn_fsk4_chain_get_results(self.h, C.byref(r)), "ddn_fsk4_chain_get_results")
+        return r
+
+    def dpmr_results(self):
+        """ddn_fsk4_chain_get_dpmr_results (DDN_FSK4_DPMR chains only)"""
+        r = DpmrChainResults()
+        _check(lib().ddn_fsk4_chain_get_dpmr_results(self.h, C.byref(r)), "ddn_fsk4_chain_get_dpmr_results")
         return r
 
     @property

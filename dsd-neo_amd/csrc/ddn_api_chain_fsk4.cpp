@@ -96,6 +96,13 @@ struct ddn_fsk4_chain {
     uint8_t *y_f96, *y_b49, *y_b88, *yi_bits, *yi_skip;
     int32_t *y_r49, *y_r88, *yi_res, *yi_res_out, *yi_vn, *yi_vslot;
     float* yi_pcm;
+    // dPMR (protocol DDN_FSK4_DPMR): the superframe behind every decoded sync (ddn_dpmr.hip), the identity state per channel, and with
+    // vocoder = 1 the eight TCH frames per slot, the voiced halves filed by channel (pvf frames each) -> d_ambe_d, d_ambe_res, d_skip,
+    // d_pcm, d_res_out, d_vn as for NXDN48
+    bool dpmr;
+    int pvf;
+    uint8_t *p_bits, *p_ham, *p_crc, *p_valid, *p_kind, *p_strong, *p_fr, *p_voiced, *p_muted, *p_vfr, *p_vhalf, *p_vmuted;
+    int32_t *p_fields, *p_id, *p_color, *p_tg, *p_src, *p_state, *p_vslot;
     long step;
     int last_set;
 };
@@ -136,7 +143,8 @@ ddn_fsk4_chain_destroy(ddn_fsk4_chain* c) {
     ddn_fsk4_rx_destroy(c->rx);
     ddn_mbe_batch_destroy(c->mbe);
     ddn_mbe_batch_destroy(c->mbe_i);
-    void* all[] = {c->y_f96, c->y_b49, c->y_b88, c->yi_bits, c->yi_skip, c->y_r49, c->y_r88, c->yi_res, c->yi_res_out, c->yi_vn, c->yi_vslot, c->yi_pcm, c->y_fr, c->y_nfr, c->y_vslot, c->y_fich4, c->y_st, c->y_ve, c->y_last, c->y_info, c->y_dch, c->y_dst, c->y_ambe, c->y_errs, c->y_dcost, c->s_thr, c->c_thr[0], c->c_thr[1], c->d_thr, c->m_lsf, c->m_lsf_st, c->m_l6, c->m_cnt, c->m_fp, c->m_st, c->m_asm, c->m_ll,
+    void* all[] = {c->p_bits, c->p_ham, c->p_crc, c->p_valid, c->p_kind, c->p_strong, c->p_fr, c->p_voiced, c->p_muted, c->p_vfr, c->p_vhalf,
+                   c->p_vmuted, c->p_fields, c->p_id, c->p_color, c->p_tg, c->p_src, c->p_state, c->p_vslot, c->y_f96, c->y_b49, c->y_b88, c->yi_bits, c->yi_skip, c->y_r49, c->y_r88, c->yi_res, c->yi_res_out, c->yi_vn, c->yi_vslot, c->yi_pcm, c->y_fr, c->y_nfr, c->y_vslot, c->y_fich4, c->y_st, c->y_ve, c->y_last, c->y_info, c->y_dch, c->y_dst, c->y_ambe, c->y_errs, c->y_dcost, c->s_thr, c->c_thr[0], c->c_thr[1], c->d_thr, c->m_lsf, c->m_lsf_st, c->m_l6, c->m_cnt, c->m_fp, c->m_st, c->m_asm, c->m_ll,
                    c->m_ll_st, c->m_cost, c->d_disc, c->d_disc2, c->d_rec[0], c->d_rec[1], c->d_fl[0], c->d_fl[1], c->d_pay, c->d_new[0], c->d_new[1], c->d_cnt_full,
                    c->d_cnt_scan, c->d_dropped, c->s_pos, c->s_n, c->c_pos[0], c->c_pos[1], c->c_n[0], c->c_n[1], c->d_spos, c->d_ns, c->s_pat, c->s_pre,
                    c->s_prel, c->c_pat[0], c->c_pat[1], c->c_pre[0], c->c_pre[1], c->c_prel[0], c->c_prel[1], c->d_spat, c->d_pre,
@@ -157,14 +165,19 @@ extern "C" hipError_t ddn_dev_ysf_voice_file(const int32_t* n_sync, int n_channe
                                              const uint8_t* errs2, const uint8_t* bits_fd, const int32_t* res_fd, const uint8_t* n_frames,
                                              int mode, int vf, uint8_t* bits, int32_t* res, uint8_t* skip, int32_t* v_n, int32_t* v_slot,
                                              hipStream_t st);
+extern "C" hipError_t ddn_dev_dpmr_voice_file(const int32_t* n_sync, int n_channels, int max_syncs, const uint8_t* fr_slot,
+                                              const uint8_t* voiced2, const uint8_t* muted2, int vf, uint8_t* fr, int32_t* v_n, int32_t* v_slot,
+                                              uint8_t* v_half, uint8_t* v_muted, uint8_t* v_skip, hipStream_t st);
 extern "C" hipError_t ddn_dev_ysf_pack96(const uint8_t* frames184, size_t n, uint8_t* frames96, hipStream_t st);
 
 extern "C" int
 ddn_fsk4_chain_create(const ddn_fsk4_chain_config* cfg, ddn_fsk4_chain** out) {
     if (!cfg || !out || cfg->n_channels <= 0 || cfg->samples_per_call <= 0 || cfg->block_len <= 0
         || (cfg->protocol != DDN_FSK4_DMR && cfg->protocol != DDN_FSK4_NXDN48 && cfg->protocol != DDN_FSK4_NXDN96 && cfg->protocol != DDN_FSK4_M17
-            && cfg->protocol != DDN_FSK4_YSF)
-        || ((cfg->protocol == DDN_FSK4_M17 || cfg->protocol == DDN_FSK4_YSF) && (cfg->handlers || cfg->inverted))) {
+            && cfg->protocol != DDN_FSK4_YSF && cfg->protocol != DDN_FSK4_DPMR)
+        || ((cfg->protocol == DDN_FSK4_M17 || cfg->protocol == DDN_FSK4_YSF) && (cfg->handlers || cfg->inverted))
+        || (cfg->protocol == DDN_FSK4_DPMR
+            && (cfg->handlers || (cfg->inverted != 0 && cfg->inverted != 1) || (cfg->rf_mod != 0 && cfg->rf_mod != 2)))) {
         ddn_set_error("ddn_fsk4_chain_create: bad configuration");
         return DDN_EINVAL;
     }
@@ -182,8 +195,9 @@ ddn_fsk4_chain_create(const ddn_fsk4_chain_config* cfg, ddn_fsk4_chain** out) {
     c->ysf = cfg->protocol == DDN_FSK4_YSF; // (the FICH ends 100 symbols after its sync)
     c->T = 256;  // a DMR burst ends 54 symbols after its sync, an NXDN frame 182: the tail kept back for the next call
     c->myc = 16; // syncs that can lie inside that tail (a new sync needs 24 / 10 fresh symbols)
-    if (c->ysf) {
-        c->T = 480; // (a YSF frame's payload ends 460 symbols after its sync)
+    c->dpmr = cfg->protocol == DDN_FSK4_DPMR;
+    if (c->ysf || c->dpmr) {
+        c->T = 480; // (a YSF frame's payload ends 460 symbols after its sync, a dPMR superframe 372)
     }
     int rc = DDN_OK;
     do {
@@ -221,6 +235,12 @@ ddn_fsk4_chain_create(const ddn_fsk4_chain_config* cfg, ddn_fsk4_chain** out) {
         {
             const size_t dense = c->ms / 64 + 24 + (size_t)c->myc, loop_bound = c->my + (size_t)c->myc;
             c->myd = (int)(cfg->handlers && dense < loop_bound ? dense : loop_bound);
+            // dPMR: the loop holds 372 symbols behind every sync and then hunts a fresh 12-symbol window, so accepted syncs lie at least
+            // 384 symbols apart and the ones a call decodes (positions below its new-record count) number ms / 384 + 1 at most
+            const size_t sf = c->ms / 384 + 4;
+            if (c->dpmr && sf < (size_t)c->myd) {
+                c->myd = (int)sf;
+            }
         }
         c->S = (size_t)c->B * (size_t)c->myd;
         const size_t B = (size_t)c->B, S = c->S, my = c->my, myc = (size_t)c->myc;
@@ -249,6 +269,31 @@ ddn_fsk4_chain_create(const ddn_fsk4_chain_config* cfg, ddn_fsk4_chain** out) {
                     break;
                 }
                 if (ok && (rc = ddn_mbe_batch_create(DDN_MBE_IMBE_7200X4400, c->B, &c->mbe_i)) != DDN_OK) {
+                    break;
+                }
+            }
+        } else if (ok && c->dpmr) {
+            ok = dalloc(&c->p_bits, S * 96) && dalloc(&c->p_ham, S * 12) && dalloc(&c->p_crc, S * 2) && dalloc(&c->p_fields, S * 16)
+                 && dalloc(&c->p_id, S) && dalloc(&c->p_color, S) && dalloc(&c->p_valid, S) && dalloc(&c->p_kind, S) && dalloc(&c->p_strong, S)
+                 && dalloc(&c->p_tg, S) && dalloc(&c->p_src, S) && dalloc(&c->p_state, B * 3);
+            if (ok) { // {tg, src, next part} = {none, none, 0}
+                int32_t* h = new (std::nothrow) int32_t[B * 3];
+                ok = h != nullptr;
+                for (size_t i = 0; ok && i < B; i++) {
+                    h[3 * i] = -1, h[3 * i + 1] = -1, h[3 * i + 2] = 0;
+                }
+                ok = ok && hipMemcpy(c->p_state, h, sizeof(int32_t) * B * 3, hipMemcpyHostToDevice) == hipSuccess;
+                delete[] h;
+            }
+            if (ok && cfg->vocoder) {
+                // two halves of four frames per superframe; the superframes a call decodes: see myd (a carried one included)
+                c->pvf = 8 * (int)(c->ms / 384 + 2);
+                const size_t V = B * (size_t)c->pvf;
+                ok = dalloc(&c->p_fr, S * 8 * 96) && dalloc(&c->p_voiced, S * 2) && dalloc(&c->p_muted, S * 2) && dalloc(&c->p_vfr, V * 96)
+                     && dalloc(&c->p_vslot, V) && dalloc(&c->p_vhalf, V) && dalloc(&c->p_vmuted, V) && dalloc(&c->d_vn, B)
+                     && dalloc(&c->d_ambe_d, V * 49) && dalloc(&c->d_ambe_res, V * 5) && dalloc(&c->d_skip, V) && dalloc(&c->d_pcm, V * 160)
+                     && dalloc(&c->d_res_out, V * 5);
+                if (ok && (rc = ddn_mbe_batch_create(DDN_MBE_AMBE_3600X2450, c->B, &c->mbe)) != DDN_OK) {
                     break;
                 }
             }
@@ -365,6 +410,28 @@ fsk4_decode(ddn_fsk4_chain* c, int cur, int flush, hipStream_t st) {
             DDN_TRY(ddn_mbe_synth_batch(c->mbe_i, c->yi_bits, c->yi_res, (size_t)c->yvf * 5, c->yi_pcm, c->yi_res_out, st));
         }
         HIP_TRY(hipEventRecord(c->ev_reads, st));
+        return DDN_OK;
+    }
+    if (c->dpmr) {
+        // every superframe of the decode list (each whole inside the row): CCHs, colour code, ID -> the identity rules in sync order
+        DDN_TRY(ddn_dpmr_superframe_decode_batch(rec, c->stride, c->d_cnt_full, c->d_spos, c->d_ns, c->B, (size_t)c->myd, c->cfg.inverted,
+                                                 c->p_bits, c->p_ham, c->p_crc, c->p_fields, c->p_id, c->p_color, c->p_valid, st));
+        if (c->mbe) {
+            DDN_TRY(ddn_dpmr_voice_gather(rec, c->stride, c->d_spos, c->d_ns, c->B, (size_t)c->myd, c->cfg.inverted, c->p_fields, c->p_valid,
+                                          c->p_fr, c->p_voiced, c->p_muted, st));
+        }
+        HIP_TRY(hipEventRecord(c->ev_reads, st)); // (everything below works on the decoded fields and the gathered frames)
+        DDN_TRY(ddn_dpmr_identity_batch(c->d_ns, c->B, (size_t)c->myd, c->p_valid, c->p_fields, c->p_ham, c->p_crc, c->p_id, c->p_state,
+                                        c->p_kind, c->p_strong, c->p_tg, c->p_src, st));
+        if (c->mbe) {
+            // voice (dpmr_play_voice_frames): the voiced halves in air order, talk path = channel -> frame FEC (hard bits) -> synthesis
+            const size_t V = (size_t)c->B * (size_t)c->pvf;
+            HIP_TRY(ddn_dev_dpmr_voice_file(c->d_ns, c->B, c->myd, c->p_fr, c->p_voiced, c->p_muted, c->pvf, c->p_vfr, c->d_vn, c->p_vslot,
+                                            c->p_vhalf, c->p_vmuted, c->d_skip, st));
+            DDN_TRY(ddn_mbe_frame_decode_batch(DDN_MBE_AMBE_3600X2450, c->p_vfr, nullptr, V, c->d_ambe_d, c->d_ambe_res, st));
+            DDN_TRY(ddn_mbe_result_skip_batch(c->d_skip, V, c->d_ambe_res, st));
+            DDN_TRY(ddn_mbe_synth_batch(c->mbe, c->d_ambe_d, c->d_ambe_res, (size_t)c->pvf, c->d_pcm, c->d_res_out, st));
+        }
         return DDN_OK;
     }
     if (c->m17) {
@@ -606,7 +673,7 @@ ddn_fsk4_chain_get_results(ddn_fsk4_chain* c, ddn_fsk4_chain_results* r) {
         r->d_events = c->d_ev;
         r->d_n_events = c->d_nev;
         r->max_events = c->E;
-    } else {
+    } else if (!c->dpmr) {
         r->d_nxdn_voice_skip = c->d_skip;
         r->d_nxdn_ambe_bits = c->d_ambe_d;
         r->d_nxdn_pcm = c->d_pcm;
@@ -646,6 +713,43 @@ ddn_fsk4_chain_get_results(ddn_fsk4_chain* c, ddn_fsk4_chain_results* r) {
         r->d_m17_str_status = c->m_st;
         r->d_m17_lich_lsf30 = c->m_ll;
         r->d_m17_lich_status = c->m_ll_st;
+    }
+    return DDN_OK;
+}
+
+extern "C" int
+ddn_fsk4_chain_get_dpmr_results(ddn_fsk4_chain* c, ddn_dpmr_chain_results* r) {
+    if (!c || !r || !c->dpmr) {
+        ddn_set_error("ddn_fsk4_chain_get_dpmr_results: not a dPMR chain");
+        return DDN_EINVAL;
+    }
+    memset(r, 0, sizeof(*r));
+    r->max_syncs = (size_t)c->myd;
+    r->voice_frames = c->mbe ? c->pvf : 0;
+    r->d_n_sync = c->d_ns;
+    r->d_sync_pos = c->d_spos;
+    r->d_valid = c->p_valid;
+    r->d_cch_bits2x48 = c->p_bits;
+    r->d_ham_ok2x6 = c->p_ham;
+    r->d_crc_ok2 = c->p_crc;
+    r->d_fields2x8 = c->p_fields;
+    r->d_id = c->p_id;
+    r->d_color = c->p_color;
+    r->d_kind = c->p_kind;
+    r->d_strong = c->p_strong;
+    r->d_tg = c->p_tg;
+    r->d_src = c->p_src;
+    if (c->mbe) {
+        r->d_ambe_fr = c->p_fr;
+        r->d_voiced2 = c->p_voiced;
+        r->d_muted2 = c->p_muted;
+        r->d_n_voice = c->d_vn;
+        r->d_voice_slot = c->p_vslot;
+        r->d_voice_half = c->p_vhalf;
+        r->d_voice_muted = c->p_vmuted;
+        r->d_voice_skip = c->d_skip;
+        r->d_voice_result = c->d_res_out;
+        r->d_pcm = c->d_pcm;
     }
     return DDN_OK;
 }

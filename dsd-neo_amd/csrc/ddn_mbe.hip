@@ -347,8 +347,9 @@ k_mbe_params(const uint8_t* __restrict__ bits, const int32_t* __restrict__ res_i
         unsigned flags = (unsigned)r[0];
         const int errs2 = r[3];
         DdnMbeFrameRec* rec = recs + fi;
-        // the frame's bits as two ballots (bit p of m0 = d[p], bit p - 64 of m1 = d[p])
-        const uint32_t v0 = d[l], v1 = (l + 64 < NB) ? d[l + 64] : 0u;
+        // the frame's bits as two ballots (bit p of m0 = d[p], bit p - 64 of m1 = d[p]); AMBE's 49 bits end inside the first wave: a
+        // lane past them reads nothing (past the last frame of a tightly sized array there is no byte to read)
+        const uint32_t v0 = (l < NB) ? d[l] : 0u, v1 = (l + 64 < NB) ? d[l + 64] : 0u;
         const unsigned long long m0 = __ballot(v0 & 1u), m1 = __ballot(v1 & 1u);
         const bool invalid = __any((v0 > 1u) || (v1 > 1u)) || (flags & DDN_MBE_RESULT_INVALID);
         auto bit = [&](int p) -> uint32_t { return (uint32_t)(((p < 64 ? m0 >> p : m1 >> (p - 64))) & 1ull); };

@@ -287,9 +287,9 @@ typedef struct ddn_fsk4_chain_config {
     int samples_per_call;
     int block_len;
     int input_format; /* DDN_IN_CU8 / DDN_IN_CF32 */
-    int protocol;     /* DDN_FSK4_DMR / DDN_FSK4_NXDN48 (include/ddn_fsk4.h) */
+    int protocol;     /* DDN_FSK4_DMR / DDN_FSK4_NXDN48 / _NXDN96 / _M17 / _YSF / _DPMR (include/ddn_fsk4.h) */
     int rf_mod;       /* 0 = C4FM rules, 2 = GFSK rules (what dsd-neo runs DMR with) */
-    int inverted;     /* DMR: opts->inverted_dmr (handlers need 0) */
+    int inverted;     /* DMR: opts->inverted_dmr (handlers need 0); dPMR: opts->inverted_dpmr (-xd) */
     int handlers;     /* 1 = the reference's handlers decide the in-frame lengths (ddn_fsk4_rx_set_handlers) */
     int vocoder;      /* 1 = AMBE synthesis to PCM (NXDN48 voice frames; DMR voice bursts when handlers = 1) */
 } ddn_fsk4_chain_config;
@@ -432,6 +432,42 @@ int ddn_fsk4_chain_stage(ddn_fsk4_chain* c, int stage, const void* d_iq, void* h
 int ddn_fsk4_chain_get_results(ddn_fsk4_chain* c, ddn_fsk4_chain_results* out);
 void* ddn_fsk4_chain_front_end(ddn_fsk4_chain* c); /* ddn_batch* */
 void* ddn_fsk4_chain_rx(ddn_fsk4_chain* c);        /* ddn_fsk4_rx* */
+
+/* ---- dPMR (protocol DDN_FSK4_DPMR, -fm): the fsk4 chain with the narrow front end (6.25 kHz, 2400 symbols/s, as NXDN48), handlers = 0,
+ * inverted 0 / 1 (-xd), rf_mod 0 / 2 and a 480-symbol carry: a voice superframe ends 372 symbols behind its sync and is decoded once,
+ * whole, in the call that holds its last symbol (flush decodes the tail).  Per call: ddn_dpmr_superframe_decode_batch ->
+ * ddn_dpmr_identity_batch (the {TG, Src, next part} state carried per channel across calls and through flush) -> with vocoder = 1
+ * ddn_dpmr_voice_gather -> the voiced halves filed by channel in air order -> AMBE 3600x2450 frame FEC -> synthesis (talk path =
+ * channel).  The results live in a struct of their own (ddn_fsk4_chain_results keeps its size: a caller's older copy of it stays
+ * valid); ddn_fsk4_chain_get_dpmr_results refuses any other protocol (DDN_EINVAL). */
+typedef struct ddn_dpmr_chain_results { /* device pointers valid until the next run; S = n_channels * max_syncs sync slots */
+    size_t max_syncs;                /* sync slots per channel (the d_sync_pos / d_n_sync of ddn_fsk4_chain_results) */
+    int voice_frames;                /* F4: AMBE frames per channel and call the voice arrays hold (0 without the vocoder) */
+    const int32_t* d_n_sync;         /* [n_channels] superframes (syncs) decoded in this call */
+    const int32_t* d_sync_pos;       /* [S] record index of each sync's last symbol in this call's rows */
+    const uint8_t* d_valid;          /* [S] 1 = all 372 dibits inside the records (always, except at flush past the stream's end) */
+    const uint8_t* d_cch_bits2x48;   /* [S][2][48] decoded CCH bits */
+    const uint8_t* d_ham_ok2x6;      /* [S][2][6] Hamming(12,8) status per code word */
+    const uint8_t* d_crc_ok2;        /* [S][2] CRC7 status per CCH */
+    const int32_t* d_fields2x8;      /* [S][2][8] frame number, ID half, mode, version, format, emergency, reserved, slow data */
+    const int32_t* d_id;             /* [S] 24-bit ID */
+    const int32_t* d_color;          /* [S] colour (channel) code, -1 = none */
+    const uint8_t* d_kind;           /* [S] 0 none, 1 called, 2 calling */
+    const uint8_t* d_strong;         /* [S] */
+    const int32_t* d_tg;             /* [S] TG (raw 24-bit ID) after this superframe, -1 = none yet */
+    const int32_t* d_src;            /* [S] Src, the same */
+    const uint8_t* d_ambe_fr;        /* [S][8][4][24] the eight TCH frames (vocoder = 1) */
+    const uint8_t* d_voiced2;        /* [S][2] half synthesised (communication mode 0, 1, 5) */
+    const uint8_t* d_muted2;         /* [S][2] half scrambled (version 3): synthesised, audio not permitted */
+    const int32_t* d_n_voice;        /* [n_channels] frames synthesised in this call (4 per voiced half) */
+    const int32_t* d_voice_slot;     /* [n_channels][F4] the sync slot (k of c * max_syncs + k) each frame came from, -1 behind the last */
+    const uint8_t* d_voice_half;     /* [n_channels][F4] 0 / 1 */
+    const uint8_t* d_voice_muted;    /* [n_channels][F4] 1 = scrambled half (the host plays silence) */
+    const uint8_t* d_voice_skip;     /* [n_channels][F4] 1 = no frame at this position */
+    const int32_t* d_voice_result;   /* [n_channels][F4][5] mbe_process_result rows after synthesis */
+    const float* d_pcm;              /* [n_channels][F4][160] 8 kHz PCM (silence behind the last frame) */
+} ddn_dpmr_chain_results;
+int ddn_fsk4_chain_get_dpmr_results(ddn_fsk4_chain* c, ddn_dpmr_chain_results* out);
 
 /* ---- a mixed batch (BASELINE configs[3]): P25 Phase 1 + DMR + NXDN48 channel groups of one GPU, every receive loop with the
  * reference's handlers inside it; one stream per group inside the object, the groups' stages lined up (the three front ends, then the

@@ -217,6 +217,42 @@ int ddn_dmr_voice_burst_gather(const uint8_t* d_records10, const int32_t* d_coun
                                uint8_t* d_ambe_fr, uint8_t* d_ambe_rel, uint8_t* d_sync48, uint8_t* d_cach24, uint8_t* d_valid,
                                void* hip_stream);
 
+/* ---- dPMR voice superframe behind the loop's FS2 syncs (DDN_FSK4_DPMR, -fm; ddn_dpmr.hip) -------------------------------------
+ * ddn_dpmr_superframe_decode_batch == processdPMRvoice()'s control part (src/protocol/dpmr/dpmr_voice.c:397-425) for every accepted sync:
+ * the 372 dibits behind it (record byte 0 & 3 from sync_pos + 1; inverted = 1 applies dpmr_read_dibit()'s ^ 2, :67-73), then per CCH
+ * (dibit offsets 0 and 192; dpmr_voice.c:139-178): descramble x^9 + x^5 + 1 seeded 0x1FF (dpmr_data.c:80-117), 6 x 12 de-interleave
+ * (:431-452), six Hamming(12,8) words (the generic entry's matrix and correction table), CRC7 over 41 bits against bits 41..47 (:455-474).
+ * Per slot c * max_syncs + k (as d_sync_pos):
+ *   d_cch_bits2x48 u8 [S][2][48]  decoded CCH bits         d_ham_ok2x6 u8 [S][2][6]  1 = Hamming word j corrected / clean
+ *   d_crc_ok2      u8 [S][2]      1 = CRC7 good            d_fields2x8 i32 [S][2][8] {frame number, 12-bit ID half, communication
+ *     mode, version, format, emergency, reserved, 18 bits of slow data} (dpmr_extract_superframe_part(), :180-195)
+ *   d_id i32 [S]  24-bit ID (first CCH's half high)         d_color i32 [S] colour code: the 12 dibits at offset 180 | 0x555555
+ *     looked up in the 64-entry table (tests/golden/dpmr_vectors.json -> ddn_tables_dpmr.h), -1 = no match
+ *   d_valid u8 [S] 1 = all 372 dibits lie inside this call's records (d_counts); a slot that is not valid is written as zeros, colour -1.
+ * ddn_dpmr_identity_batch == dpmr_update_superframe_part() (:197-274) over each channel's valid slots in sync order: kind (0 none,
+ *   1 called: frame number 0 / 1 in CCH 0 / 1, 2 calling: 2 / 3) and strong (both CCHs pass CRC7 or their first two Hamming words); a
+ *   strong called ID publishes TG, a strong calling ID Src.  d_state3 i32 [B][3] = {tg, src, next part} carried from call to call
+ *   (initialise to {-1, -1, 0}); d_tg / d_src i32 [S] = raw 24-bit values as they stand after the slot's superframe, -1 = none
+ *   (ddn_dpmr_air_interface_id turns them into the digits the reference prints).
+ * ddn_dpmr_voice_gather == the eight TCH frames (dibit offsets 36, 72, 108, 144, 228, 264, 300, 336) through the AMBE 3600x2450
+ *   schedule, hard bits as processMbeFrame(opts, state, NULL, ambe_fr[i], NULL) takes them: d_ambe_fr u8 [S][8][4][24]; per half
+ *   (dpmr_play_voice_frames(), :354-395) d_voiced2 [S][2] = 1 where the half's communication mode is 0, 1 or 5 (its four frames go
+ *   to the vocoder), d_muted2 [S][2] = 1 where its version is 3 (scrambled: synthesised, audio not permitted without a key).
+ *   d_fields2x8 / d_valid = the superframe decode's. */
+int ddn_dpmr_superframe_decode_batch(const uint8_t* d_records10, size_t stride_symbols, const int32_t* d_counts, const int32_t* d_sync_pos,
+                                     const int32_t* d_n_sync, int n_channels, size_t max_syncs, int inverted, uint8_t* d_cch_bits2x48,
+                                     uint8_t* d_ham_ok2x6, uint8_t* d_crc_ok2, int32_t* d_fields2x8, int32_t* d_id, int32_t* d_color,
+                                     uint8_t* d_valid, void* hip_stream);
+int ddn_dpmr_identity_batch(const int32_t* d_n_sync, int n_channels, size_t max_syncs, const uint8_t* d_valid, const int32_t* d_fields2x8,
+                            const uint8_t* d_ham_ok2x6, const uint8_t* d_crc_ok2, const int32_t* d_id, int32_t* d_state3, uint8_t* d_kind,
+                            uint8_t* d_strong, int32_t* d_tg, int32_t* d_src, void* hip_stream);
+int ddn_dpmr_voice_gather(const uint8_t* d_records10, size_t stride_symbols, const int32_t* d_sync_pos, const int32_t* d_n_sync, int n_channels,
+                          size_t max_syncs, int inverted, const int32_t* d_fields2x8, const uint8_t* d_valid, uint8_t* d_ambe_fr,
+                          uint8_t* d_voiced2, uint8_t* d_muted2, void* hip_stream);
+/* (host) dpmr_convert_air_interface_id() (dpmr_voice.c:477-546): the seven base-11 digits the reference prints for a raw 24-bit ID
+ * ("1601621"), '*' for ten, NUL-terminated.  Like the reference, a first digit of 11 (IDs >= 11 x 1464100) is written as '0' + 11. */
+void ddn_dpmr_air_interface_id(uint32_t id, char out[8]);
+
 /* CRC of decoded NXDN fields, rows = ddn_fec_nxdn_conv_batch output: kind 0 = SACCH (26 bits + CRC6, nxdn_deperm.c:1246-1261),
  * kind 1 = FACCH1 (80 bits + CRC12, nxdn_dcr_utils.c:21-42); kind + 2 = the same on rows of one bit per byte (what
  * ddn_fec_trellis_decode_batch writes); d_ok [n] = 1 when the field's CRC matches */
