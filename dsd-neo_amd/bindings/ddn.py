@@ -391,6 +391,7 @@ FSK4_NXDN96 = 3
 FSK4_M17 = 4
 FSK4_YSF = 5
 FSK4_DPMR = 6
+FSK4_DSTAR = 7
 PROTOTYPES.update({
     "ddn_fsk4_rx_create": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_fsk4_rx_destroy": (None, [C.c_void_p]),
@@ -418,6 +419,8 @@ PROTOTYPES.update({
     "ddn_dpmr_identity_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 11),
     "ddn_dpmr_voice_gather": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_int] + [C.c_void_p] * 6),
     "ddn_dpmr_air_interface_id": (None, [C.c_uint32, C.c_char_p]),
+    "ddn_dstar_header_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5 + [C.c_int, C.c_size_t] + [C.c_void_p] * 4),
+    "ddn_dstar_voice_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5 + [C.c_int, C.c_size_t] + [C.c_void_p] * 8),
     "ddn_ysf_payload_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3 + [C.c_int, C.c_size_t] + [C.c_void_p] * 12),
     "ddn_fsk4_rx_get_timing": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_mode_config": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
@@ -548,6 +551,12 @@ class DpmrChainResults(C.Structure):  # == ddn_dpmr_chain_results
                                   "d_voice_slot", "d_voice_half", "d_voice_muted", "d_voice_skip", "d_voice_result", "d_pcm")]
 
 
+class DstarChainResults(C.Structure):  # == ddn_dstar_chain_results
+    _fields_ = [("max_syncs", C.c_size_t)] + [
+        (k, C.c_void_p) for k in ("d_n_sync", "d_sync_pos", "d_sync_pat", "d_sync_thr5", "d_hdr41", "d_hdr_crc_ok", "d_hdr_valid", "d_ambe_fr",
+                                  "d_sd_bytes", "d_sd_kind", "d_sd_hdr41", "d_sd_crc_ok", "d_sd_text", "d_valid")]
+
+
 def dpmr_air_interface_id(v):
     """ddn_dpmr_air_interface_id: the seven characters the reference prints for a raw 24-bit dPMR ID"""
     out = C.create_string_buffer(8)
@@ -596,6 +605,7 @@ PROTOTYPES.update({
     "ddn_fsk4_chain_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ddn_fsk4_chain_get_results": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_fsk4_chain_get_dpmr_results": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ddn_fsk4_chain_get_dstar_results": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_fsk4_chain_flush": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_fsk4_chain_front_end": (C.c_void_p, [C.c_void_p]),
     "ddn_fsk4_chain_rx": (C.c_void_p, [C.c_void_p]),
@@ -656,6 +666,12 @@ class Fsk4ChainC:
         """ddn_fsk4_chain_get_dpmr_results (DDN_FSK4_DPMR chains only)"""
         r = DpmrChainResults()
         _check(lib().ddn_fsk4_chain_get_dpmr_results(self.h, C.byref(r)), "ddn_fsk4_chain_get_dpmr_results")
+        return r
+
+    def dstar_results(self):
+        """ddn_fsk4_chain_get_dstar_results (DDN_FSK4_DSTAR chains only)"""
+        r = DstarChainResults()
+        _check(lib().ddn_fsk4_chain_get_dstar_results(self.h, C.byref(r)), "ddn_fsk4_chain_get_dstar_results")
         return r
 
     @property

@@ -103,6 +103,10 @@ struct ddn_fsk4_chain {
     int pvf;
     uint8_t *p_bits, *p_ham, *p_crc, *p_valid, *p_kind, *p_strong, *p_fr, *p_voiced, *p_muted, *p_vfr, *p_vhalf, *p_vmuted;
     int32_t *p_fields, *p_id, *p_color, *p_tg, *p_src, *p_state, *p_vslot;
+    // D-STAR (protocol DDN_FSK4_DSTAR): the radio header and the voice superframe behind every decoded sync (ddn_dstar.hip), read
+    // against the thresholds each sync left (s_thr / c_thr / d_thr, filed as for M17)
+    bool dstar;
+    uint8_t *t_h41, *t_hok, *t_hv, *t_ambe, *t_sdb, *t_kind, *t_sh41, *t_sok, *t_text, *t_vv;
     long step;
     int last_set;
 };
@@ -143,7 +147,7 @@ ddn_fsk4_chain_destroy(ddn_fsk4_chain* c) {
     ddn_fsk4_rx_destroy(c->rx);
     ddn_mbe_batch_destroy(c->mbe);
     ddn_mbe_batch_destroy(c->mbe_i);
-    void* all[] = {c->p_bits, c->p_ham, c->p_crc, c->p_valid, c->p_kind, c->p_strong, c->p_fr, c->p_voiced, c->p_muted, c->p_vfr, c->p_vhalf,
+    void* all[] = {c->t_h41, c->t_hok, c->t_hv, c->t_ambe, c->t_sdb, c->t_kind, c->t_sh41, c->t_sok, c->t_text, c->t_vv, c->p_bits, c->p_ham, c->p_crc, c->p_valid, c->p_kind, c->p_strong, c->p_fr, c->p_voiced, c->p_muted, c->p_vfr, c->p_vhalf,
                    c->p_vmuted, c->p_fields, c->p_id, c->p_color, c->p_tg, c->p_src, c->p_state, c->p_vslot, c->y_f96, c->y_b49, c->y_b88, c->yi_bits, c->yi_skip, c->y_r49, c->y_r88, c->yi_res, c->yi_res_out, c->yi_vn, c->yi_vslot, c->yi_pcm, c->y_fr, c->y_nfr, c->y_vslot, c->y_fich4, c->y_st, c->y_ve, c->y_last, c->y_info, c->y_dch, c->y_dst, c->y_ambe, c->y_errs, c->y_dcost, c->s_thr, c->c_thr[0], c->c_thr[1], c->d_thr, c->m_lsf, c->m_lsf_st, c->m_l6, c->m_cnt, c->m_fp, c->m_st, c->m_asm, c->m_ll,
                    c->m_ll_st, c->m_cost, c->d_disc, c->d_disc2, c->d_rec[0], c->d_rec[1], c->d_fl[0], c->d_fl[1], c->d_pay, c->d_new[0], c->d_new[1], c->d_cnt_full,
                    c->d_cnt_scan, c->d_dropped, c->s_pos, c->s_n, c->c_pos[0], c->c_pos[1], c->c_n[0], c->c_n[1], c->d_spos, c->d_ns, c->s_pat, c->s_pre,
@@ -174,10 +178,11 @@ extern "C" int
 ddn_fsk4_chain_create(const ddn_fsk4_chain_config* cfg, ddn_fsk4_chain** out) {
     if (!cfg || !out || cfg->n_channels <= 0 || cfg->samples_per_call <= 0 || cfg->block_len <= 0
         || (cfg->protocol != DDN_FSK4_DMR && cfg->protocol != DDN_FSK4_NXDN48 && cfg->protocol != DDN_FSK4_NXDN96 && cfg->protocol != DDN_FSK4_M17
-            && cfg->protocol != DDN_FSK4_YSF && cfg->protocol != DDN_FSK4_DPMR)
+            && cfg->protocol != DDN_FSK4_YSF && cfg->protocol != DDN_FSK4_DPMR && cfg->protocol != DDN_FSK4_DSTAR)
         || ((cfg->protocol == DDN_FSK4_M17 || cfg->protocol == DDN_FSK4_YSF) && (cfg->handlers || cfg->inverted))
         || (cfg->protocol == DDN_FSK4_DPMR
-            && (cfg->handlers || (cfg->inverted != 0 && cfg->inverted != 1) || (cfg->rf_mod != 0 && cfg->rf_mod != 2)))) {
+            && (cfg->handlers || (cfg->inverted != 0 && cfg->inverted != 1) || (cfg->rf_mod != 0 && cfg->rf_mod != 2)))
+        || (cfg->protocol == DDN_FSK4_DSTAR && (cfg->handlers || cfg->inverted || cfg->vocoder || (cfg->rf_mod != 0 && cfg->rf_mod != 2)))) {
         ddn_set_error("ddn_fsk4_chain_create: bad configuration");
         return DDN_EINVAL;
     }
@@ -199,11 +204,16 @@ ddn_fsk4_chain_create(const ddn_fsk4_chain_config* cfg, ddn_fsk4_chain** out) {
     if (c->ysf || c->dpmr) {
         c->T = 480; // (a YSF frame's payload ends 460 symbols after its sync, a dPMR superframe 372)
     }
+    c->dstar = cfg->protocol == DDN_FSK4_DSTAR;
+    if (c->dstar) {
+        c->T = 2688; // (a header unit ends 660 + 1992 = 2652 symbols after its sync)
+    }
     int rc = DDN_OK;
     do {
         // (NXDN96: a 12.5 kHz channel at 4800 symbols/s)
         const bool wide = c->dmr || cfg->protocol == DDN_FSK4_NXDN96 || c->m17 || c->ysf;
-        ddn_front_end_config fc = {c->B, 48000, wide ? 4800 : 2400, 4, wide ? DDN_LPF_12K5 : DDN_LPF_6K25, cfg->input_format,
+        // (D-STAR: 4800 symbols/s behind the 6.25 kHz filter the reference picks for -fd, as ddn_host_mode.c does)
+        ddn_front_end_config fc = {c->B, 48000, (wide || c->dstar) ? 4800 : 2400, 4, wide ? DDN_LPF_12K5 : DDN_LPF_6K25, cfg->input_format,
                                    cfg->block_len, 0.0f};
         if ((rc = ddn_batch_create(&fc, &c->fe)) != DDN_OK) {
             break;
@@ -240,6 +250,11 @@ ddn_fsk4_chain_create(const ddn_fsk4_chain_config* cfg, ddn_fsk4_chain** out) {
             const size_t sf = c->ms / 384 + 4;
             if (c->dpmr && sf < (size_t)c->myd) {
                 c->myd = (int)sf;
+            }
+            // D-STAR: 1992 / 2652 symbols behind every sync, then a fresh 24-symbol window: syncs at least 2016 symbols apart
+            const size_t du = c->ms / 2016 + 4;
+            if (c->dstar && du < (size_t)c->myd) {
+                c->myd = (int)du;
             }
         }
         c->S = (size_t)c->B * (size_t)c->myd;
@@ -296,6 +311,14 @@ ddn_fsk4_chain_create(const ddn_fsk4_chain_config* cfg, ddn_fsk4_chain** out) {
                 if (ok && (rc = ddn_mbe_batch_create(DDN_MBE_AMBE_3600X2450, c->B, &c->mbe)) != DDN_OK) {
                     break;
                 }
+            }
+        } else if (ok && c->dstar) {
+            ok = dalloc(&c->s_thr, B * my * 5) && dalloc(&c->c_thr[0], B * myc * 5) && dalloc(&c->c_thr[1], B * myc * 5) && dalloc(&c->d_thr, S * 5)
+                 && dalloc(&c->t_h41, S * 41) && dalloc(&c->t_hok, S) && dalloc(&c->t_hv, S) && dalloc(&c->t_ambe, S * 21 * 96)
+                 && dalloc(&c->t_sdb, S * 60) && dalloc(&c->t_kind, S) && dalloc(&c->t_sh41, S * 41) && dalloc(&c->t_sok, S)
+                 && dalloc(&c->t_text, S * 60) && dalloc(&c->t_vv, S);
+            if (ok && (rc = ddn_fsk4_rx_set_sync_thresholds(c->rx, c->s_thr)) != DDN_OK) {
+                break;
             }
         } else if (ok && c->m17) {
             ok = dalloc(&c->s_thr, B * my * 5) && dalloc(&c->c_thr[0], B * myc * 5) && dalloc(&c->c_thr[1], B * myc * 5) && dalloc(&c->d_thr, S * 5)
@@ -387,8 +410,8 @@ fsk4_decode(ddn_fsk4_chain* c, int cur, int flush, hipStream_t st) {
     HIP_TRY(ddn_dev_fsk4_chain_syncs_thr(c->c_pos[prev], c->c_pat[prev], c->c_pre[prev], c->c_prel[prev], c->c_n[prev], c->myc, c->s_pos,
                                          c->s_pat, c->s_pre, c->s_prel, c->s_n, (int)c->my, c->d_new[cur], c->T, flush, c->d_spos, c->d_spat,
                                          c->d_pre, c->d_prel, c->d_ns, c->myd, c->c_pos[cur], c->c_pat[cur], c->c_pre[cur], c->c_prel[cur],
-                                         c->c_n[cur], c->d_dropped, c->B, c->m17 ? c->c_thr[prev] : nullptr, c->m17 ? c->s_thr : nullptr,
-                                         c->d_thr, c->m17 ? c->c_thr[cur] : nullptr, st));
+                                         c->c_n[cur], c->d_dropped, c->B, c->s_thr ? c->c_thr[prev] : nullptr, c->s_thr, c->d_thr,
+                                         c->s_thr ? c->c_thr[cur] : nullptr, st));
     if (c->ysf) { // the frame information channel behind every sync of the decode list (row a17's second consumer)
         DDN_TRY(ddn_ysf_fich_decode_batch(rec, c->stride, c->d_cnt_full, c->d_spos, c->d_ns, c->B, (size_t)c->myd, c->y_fich4, c->y_st, c->y_ve, st));
         // ... and the payload of every frame: V/D mode 2 voice bits + DCH2, the DCH blocks of V/D mode 1 and of the full-rate data frames
@@ -409,6 +432,16 @@ fsk4_decode(ddn_fsk4_chain* c, int cur, int flush, hipStream_t st) {
             DDN_TRY(ddn_mbe_result_skip_batch(c->yi_skip, V5, c->yi_res, st));
             DDN_TRY(ddn_mbe_synth_batch(c->mbe_i, c->yi_bits, c->yi_res, (size_t)c->yvf * 5, c->yi_pcm, c->yi_res_out, st));
         }
+        HIP_TRY(hipEventRecord(c->ev_reads, st));
+        return DDN_OK;
+    }
+    if (c->dstar) {
+        // every unit of the decode list (each whole inside the row): the radio header behind a header sync, the voice superframe and
+        // its slow data behind every sync
+        DDN_TRY(ddn_dstar_header_decode_batch(rec, c->stride, c->d_cnt_full, c->d_spos, c->d_spat, c->d_ns, c->d_thr, c->B, (size_t)c->myd,
+                                              c->t_h41, c->t_hok, c->t_hv, st));
+        DDN_TRY(ddn_dstar_voice_decode_batch(rec, c->stride, c->d_cnt_full, c->d_spos, c->d_spat, c->d_ns, c->d_thr, c->B, (size_t)c->myd,
+                                             c->t_ambe, c->t_sdb, c->t_kind, c->t_sh41, c->t_sok, c->t_text, c->t_vv, st));
         HIP_TRY(hipEventRecord(c->ev_reads, st));
         return DDN_OK;
     }
@@ -751,6 +784,31 @@ ddn_fsk4_chain_get_dpmr_results(ddn_fsk4_chain* c, ddn_dpmr_chain_results* r) {
         r->d_voice_result = c->d_res_out;
         r->d_pcm = c->d_pcm;
     }
+    return DDN_OK;
+}
+
+extern "C" int
+ddn_fsk4_chain_get_dstar_results(ddn_fsk4_chain* c, ddn_dstar_chain_results* r) {
+    if (!c || !r || !c->dstar) {
+        ddn_set_error("ddn_fsk4_chain_get_dstar_results: not a D-STAR chain");
+        return DDN_EINVAL;
+    }
+    memset(r, 0, sizeof(*r));
+    r->max_syncs = (size_t)c->myd;
+    r->d_n_sync = c->d_ns;
+    r->d_sync_pos = c->d_spos;
+    r->d_sync_pat = c->d_spat;
+    r->d_sync_thr5 = c->d_thr;
+    r->d_hdr41 = c->t_h41;
+    r->d_hdr_crc_ok = c->t_hok;
+    r->d_hdr_valid = c->t_hv;
+    r->d_ambe_fr = c->t_ambe;
+    r->d_sd_bytes = c->t_sdb;
+    r->d_sd_kind = c->t_kind;
+    r->d_sd_hdr41 = c->t_sh41;
+    r->d_sd_crc_ok = c->t_sok;
+    r->d_sd_text = c->t_text;
+    r->d_valid = c->t_vv;
     return DDN_OK;
 }
 

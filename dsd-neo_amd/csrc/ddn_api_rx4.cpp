@@ -146,10 +146,10 @@ ddn_fsk4_rx_create(const ddn_fsk4_rx_config* cfg, ddn_fsk4_rx** out) {
     *out = nullptr;
     if (cfg->n_channels <= 0 || cfg->out_rate_hz <= 0
         || (cfg->protocol != DDN_FSK4_DMR && cfg->protocol != DDN_FSK4_NXDN48 && cfg->protocol != DDN_FSK4_NXDN96 && cfg->protocol != DDN_FSK4_M17
-            && cfg->protocol != DDN_FSK4_YSF && cfg->protocol != DDN_FSK4_DPMR)
+            && cfg->protocol != DDN_FSK4_YSF && cfg->protocol != DDN_FSK4_DPMR && cfg->protocol != DDN_FSK4_DSTAR)
         || (cfg->rf_mod != 0 && cfg->rf_mod != 2) || (cfg->inverted && cfg->protocol != DDN_FSK4_DMR && cfg->protocol != DDN_FSK4_DPMR)) {
-        ddn_set_error("ddn_fsk4_rx_create: bad configuration (protocol DMR | NXDN48 | NXDN96 | M17 | YSF | DPMR, rf_mod 0 | 2, inverted only "
-                      "for DMR and DPMR)");
+        ddn_set_error("ddn_fsk4_rx_create: bad configuration (protocol DMR | NXDN48 | NXDN96 | M17 | YSF | DPMR | DSTAR, rf_mod 0 | 2, "
+                      "inverted only for DMR and DPMR)");
         return DDN_EINVAL;
     }
     {
@@ -221,6 +221,36 @@ ddn_fsk4_rx_create(const ddn_fsk4_rx_config* cfg, ddn_fsk4_rx** out) {
         d.nt = DDN_DMR_FILTER_TAPS;
         tap_bits = ddn_dmr_filter_bits;
         lock_default[0] = 460;
+    } else if (cfg->protocol == DDN_FSK4_DSTAR) {
+        // -fd: 4800 symbols/s on the 4800_2 hunt profile, no matched filter (symbol_apply_matched_filter() has no D-STAR branch,
+        // src/dsp/dsd_symbol.c:300-336), the four 24-symbol words compared exactly (frame_sync_try_dstar(), dsd_frame_sync.c:1452-1503;
+        // include/dsd-neo/core/sync_patterns.h:44-47; types = synctype_ids.h:44-47 + 1) with the same basic lock and outer-only warm
+        // start as YSF.  The two-level slice (digitize(), src/core/frames/dsd_dibit.c:892-948,1019-1029) belongs to the frame decoders
+        // (ddn_dstar.hip), which read the records' symbols against the thresholds the sync left; pat_neg marks the negative words.
+        // Class 1 = a voice sync (processDSTAR(): 21 x 72 + 20 x 24 symbols), class 0 = a header sync (660 more, processDSTAR_HD()).
+        static const char kVoice[] = "313131313133131113313111", kHeader[] = "131313131333133113131111";
+        char inv_v[25], inv_h[25];
+        for (int k = 0; k < 24; k++) {
+            inv_v[k] = kVoice[k] == '3' ? '1' : '3';
+            inv_h[k] = kHeader[k] == '3' ? '1' : '3';
+        }
+        inv_v[24] = inv_h[24] = 0;
+        d.sym_rate = 4800;
+        d.win_len = d.t_max = d.warm_len = 24;
+        d.n_pat = 4;
+        d.use_filter = 0;
+        const char* words[4] = {kVoice, inv_v, kHeader, inv_h};
+        static const uint8_t kTypes[4] = {7, 8, 19, 20};
+        for (int k = 0; k < 4; k++) {
+            d.pat_bits[k] = sign_bits(words[k]);
+            d.pat_type[k] = kTypes[k];
+            d.pat_neg[k] = (uint8_t)(k & 1);
+            d.pat_class[k] = (uint8_t)(k < 2 ? DDN_FSK4_CLASS_VOICE : DDN_FSK4_CLASS_DATA);
+        }
+        d.nt = DDN_DMR_FILTER_TAPS; // (unused)
+        tap_bits = ddn_dmr_filter_bits;
+        lock_default[DDN_FSK4_CLASS_DATA] = DDN_DSTAR_HEADER_SYMBOLS;
+        lock_default[DDN_FSK4_CLASS_VOICE] = DDN_DSTAR_VOICE_SYMBOLS;
     } else if (cfg->protocol == DDN_FSK4_DPMR) {
         // -fm: FS2 only, exact over 12 symbols, the plain word or - under -xd (inverted) - the inverted one
         // (frame_sync_try_dpmr(), src/dsp/dsd_frame_sync.c:832-862; include/dsd-neo/core/sync_patterns.h:123-132; types =
@@ -368,6 +398,10 @@ ddn_fsk4_rx_set_handlers(ddn_fsk4_rx* b, int enable) {
     }
     if (enable && b->cfg.inverted) {
         ddn_set_error("ddn_fsk4_rx_set_handlers: the handlers are the reference's plain -fs ones (inverted = 0)");
+        return DDN_EINVAL;
+    }
+    if (enable && b->cfg.protocol == DDN_FSK4_DSTAR) {
+        ddn_set_error("ddn_fsk4_rx_set_handlers: D-STAR frames are fixed counts (no handler family)");
         return DDN_EINVAL;
     }
     if (enable && b->cfg.protocol == DDN_FSK4_DPMR) {

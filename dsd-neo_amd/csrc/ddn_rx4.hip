@@ -116,12 +116,15 @@ struct Fsk4Cfg {
     // PROTO 6 dPMR (-fm): 2400 symbols/s on the 2400_4 hunt profile (level ring 12), the 12-symbol FS2 word compared exactly in the
     // one polarity -xd selects (frame_sync_try_dpmr(), src/dsp/dsd_frame_sync.c:832-862), 12-symbol warm start, dpmr_filter
     // (src/dsp/dsd_symbol.c:316-321), a fixed count behind a sync (processdPMRvoice() reads 372 dibits, dpmr_voice.c:397-425)
+    // PROTO 7 D-STAR (-fd): 4800 symbols/s on the 4800_2 hunt profile (level ring 24), the four 24-symbol words compared exactly
+    // (frame_sync_try_dstar(), src/dsp/dsd_frame_sync.c:1452-1503), 24-symbol warm start, no matched filter (dsd_symbol.c:300-336),
+    // fixed counts behind a sync (processDSTAR() 1992 symbols, processDSTAR_HD() 660 more)
     static constexpr int sym_rate = (PROTO == 2 || PROTO == 6) ? 2400 : 4800;
-    static constexpr int win_len = PROTO == 1 ? 24 : (PROTO == 4 ? 8 : (PROTO == 5 ? 20 : (PROTO == 6 ? 12 : 10)));
+    static constexpr int win_len = (PROTO == 1 || PROTO == 7) ? 24 : (PROTO == 4 ? 8 : (PROTO == 5 ? 20 : (PROTO == 6 ? 12 : 10)));
     static constexpr int t_max = (PROTO == 2 || PROTO == 6) ? 12 : 24;
-    static constexpr int warm_len = PROTO == 1 ? 24 : (PROTO == 4 ? 8 : (PROTO == 5 ? 20 : (PROTO == 6 ? 12 : 10)));
-    static constexpr int n_pat = PROTO == 1 ? 9 : (PROTO == 4 ? 12 : (PROTO == 5 ? 2 : (PROTO == 6 ? 1 : 10)));
-    static constexpr int confirm = (PROTO == 1 || PROTO == 4 || PROTO == 5 || PROTO == 6) ? 0 : 1, dmr_window = PROTO == 1 ? 1 : 0, redigitize = PROTO == 1 ? 1 : 0;
+    static constexpr int warm_len = (PROTO == 1 || PROTO == 7) ? 24 : (PROTO == 4 ? 8 : (PROTO == 5 ? 20 : (PROTO == 6 ? 12 : 10)));
+    static constexpr int n_pat = PROTO == 1 ? 9 : (PROTO == 4 ? 12 : (PROTO == 5 ? 2 : (PROTO == 6 ? 1 : (PROTO == 7 ? 4 : 10))));
+    static constexpr int confirm = (PROTO == 1 || PROTO == 4 || PROTO == 5 || PROTO == 6 || PROTO == 7) ? 0 : 1, dmr_window = PROTO == 1 ? 1 : 0, redigitize = PROTO == 1 ? 1 : 0;
     static constexpr bool m17 = PROTO == 4;
     static constexpr int slow_type = 0;
     static constexpr int nt = PROTO == 2 ? DDN_NXDN48_FILTER_TAPS : (PROTO == 6 ? DDN_DPMR_FILTER_TAPS : DDN_DMR_FILTER_TAPS);
@@ -1973,11 +1976,11 @@ ddn_dev_fsk4_rx(const float* raw, const float* filt, const float* prev_tail, flo
     if (n_channels <= 0 || n <= 0) {
         return hipSuccess;
     }
-    if (protocol < 1 || protocol > 6) {
+    if (protocol < 1 || protocol > 7) {
         return hipErrorInvalidValue;
     }
-    if ((protocol == 4 || protocol == 5 || protocol == 6) && handlers) {
-        return hipErrorInvalidValue; // M17 / YSF / dPMR frames are fixed counts: no handler family
+    if ((protocol == 4 || protocol == 5 || protocol == 6 || protocol == 7) && handlers) {
+        return hipErrorInvalidValue; // M17 / YSF / dPMR / D-STAR frames are fixed counts: no handler family
     }
     const DdnFec3Tables* htab = nullptr;
     if (handlers) {
@@ -2012,6 +2015,9 @@ ddn_dev_fsk4_rx(const float* raw, const float* filt, const float* prev_tail, flo
         }                                                                                                                  \
         if (protocol == 6) { /* dPMR: 2400 symbols/s, fixed counts */                                                      \
             return launch<CPW_, MAXW_, 6, false>(DDN_RX4_ARGS);                                                             \
+        }                                                                                                                  \
+        if (protocol == 7) { /* D-STAR: 4800 symbols/s, fixed counts */                                                    \
+            return launch<CPW_, 12, 7, false>(DDN_RX4_ARGS);                                                                \
         }                                                                                                                  \
         return handlers ? launch<CPW_, MAXW_, 2, true>(DDN_RX4_ARGS) : launch<CPW_, MAXW_, 2, false>(DDN_RX4_ARGS);         \
     } while (0)

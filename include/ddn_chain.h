@@ -287,7 +287,7 @@ typedef struct ddn_fsk4_chain_config {
     int samples_per_call;
     int block_len;
     int input_format; /* DDN_IN_CU8 / DDN_IN_CF32 */
-    int protocol;     /* DDN_FSK4_DMR / DDN_FSK4_NXDN48 / _NXDN96 / _M17 / _YSF / _DPMR (include/ddn_fsk4.h) */
+    int protocol;     /* DDN_FSK4_DMR / DDN_FSK4_NXDN48 / _NXDN96 / _M17 / _YSF / _DPMR / _DSTAR (include/ddn_fsk4.h) */
     int rf_mod;       /* 0 = C4FM rules, 2 = GFSK rules (what dsd-neo runs DMR with) */
     int inverted;     /* DMR: opts->inverted_dmr (handlers need 0); dPMR: opts->inverted_dpmr (-xd) */
     int handlers;     /* 1 = the reference's handlers decide the in-frame lengths (ddn_fsk4_rx_set_handlers) */
@@ -468,6 +468,32 @@ typedef struct ddn_dpmr_chain_results { /* device pointers valid until the next 
     const float* d_pcm;              /* [n_channels][F4][160] 8 kHz PCM (silence behind the last frame) */
 } ddn_dpmr_chain_results;
 int ddn_fsk4_chain_get_dpmr_results(ddn_fsk4_chain* c, ddn_dpmr_chain_results* out);
+
+/* ---- D-STAR (protocol DDN_FSK4_DSTAR, -fd): the fsk4 chain at 4800 symbols/s behind the 6.25 kHz channel filter the reference picks for
+ * -fd, handlers = 0, inverted = 0, rf_mod 0 / 2, vocoder = 0, and a 2688-symbol carry: a header unit ends 660 + 1992 = 2652 symbols behind
+ * its sync, a voice unit 1992.  Every unit is decoded once, whole, in the first call whose records hold its last symbol and the carry
+ * behind its sync (flush decodes the tail).  Per call: ddn_dstar_header_decode_batch -> ddn_dstar_voice_decode_batch (include/ddn_fsk4.h)
+ * against the thresholds each sync left.  The voice frames are AMBE 3600x2400 frames handed back as frames: mbe_processAmbe3600x2400Framef
+ * stays refused (include/ddn_mbe.h - the 2400 rate's layout and tables are not in the reference tree), so vocoder = 1 is refused.
+ * ddn_fsk4_chain_get_dstar_results refuses any other protocol (DDN_EINVAL); ddn_fsk4_chain_results keeps its size. */
+typedef struct ddn_dstar_chain_results { /* device pointers valid until the next run; S = n_channels * max_syncs sync slots */
+    size_t max_syncs;             /* sync slots per channel */
+    const int32_t* d_n_sync;      /* [n_channels] units (syncs) decoded in this call */
+    const int32_t* d_sync_pos;    /* [S] record index of each sync's last symbol in this call's rows (ddn_fsk4_chain_results) */
+    const uint8_t* d_sync_pat;    /* [S] pattern index: 0 / 1 voice +/-, 2 / 3 header +/- */
+    const float* d_sync_thr5;     /* [S][5] {center, umid, lmid, max, min} the sync left */
+    const uint8_t* d_hdr41;       /* [S][41] radio header octets (header syncs) */
+    const uint8_t* d_hdr_crc_ok;  /* [S] */
+    const uint8_t* d_hdr_valid;   /* [S] 1 = a header sync whose 660 symbols were inside the records */
+    const uint8_t* d_ambe_fr;     /* [S][21][4][24] the voice frames */
+    const uint8_t* d_sd_bytes;    /* [S][60] slow-data bytes */
+    const uint8_t* d_sd_kind;     /* [S] 0 unknown, 1 header, 2 text, 3 fixed form */
+    const uint8_t* d_sd_hdr41;    /* [S][41] the slow data's header (kind 1) */
+    const uint8_t* d_sd_crc_ok;   /* [S] its CRC in wire order */
+    const uint8_t* d_sd_text;     /* [S][60] dstar_txt as the text handler leaves it, zeros when no text is stored */
+    const uint8_t* d_valid;       /* [S] 1 = the 1992 voice symbols were inside the records (always, except at flush past the end) */
+} ddn_dstar_chain_results;
+int ddn_fsk4_chain_get_dstar_results(ddn_fsk4_chain* c, ddn_dstar_chain_results* out);
 
 /* ---- a mixed batch (BASELINE configs[3]): P25 Phase 1 + DMR + NXDN48 channel groups of one GPU, every receive loop with the
  * reference's handlers inside it; one stream per group inside the object, the groups' stages lined up (the three front ends, then the

@@ -18,7 +18,20 @@
 extern "C" {
 #endif
 
-enum { DDN_FSK4_DMR = 1, DDN_FSK4_NXDN48 = 2, DDN_FSK4_NXDN96 = 3, DDN_FSK4_M17 = 4, DDN_FSK4_YSF = 5, DDN_FSK4_DPMR = 6 };
+enum { DDN_FSK4_DMR = 1, DDN_FSK4_NXDN48 = 2, DDN_FSK4_NXDN96 = 3, DDN_FSK4_M17 = 4, DDN_FSK4_YSF = 5, DDN_FSK4_DPMR = 6, DDN_FSK4_DSTAR = 7 };
+/* D-STAR (-fd): the first two-level protocol.  4800 symbols/s on the 4800_2 hunt profile (level ring 24), no matched filter
+ * (use_matched_filter is ignored, as for M17), rf_mod 2 (decode_mode_apply_dstar()) or 0, inverted refused.  The four 24-symbol words
+ * are compared exactly (frame_sync_try_dstar(), src/dsp/dsd_frame_sync.c:1452-1503) with a 24-symbol outer-only warm start.
+ * Sync pattern index: 0 +voice (DSTAR_SYNC), 1 -voice, 2 +header (DSTAR_HD), 3 -header; odd rows are negative polarity (flags bit 4).
+ * Sync class: voice = DDN_FSK4_CLASS_VOICE, lock_symbols[1] = 1992 = 21 x 72 voice + 20 x 24 slow-data symbols (processDSTAR());
+ * header = DDN_FSK4_CLASS_DATA, lock_symbols[0] = 2652 = the 660 header symbols + 1992 (processDSTAR_HD()).  No handler family.
+ * Thresholds stay static inside a frame under both rf_mod values (use_symbol(), dsd_dibit.c:264-275), so the records' symbols and the
+ * thresholds the sync left (ddn_fsk4_rx_set_sync_thresholds) are all the frame decoders need: the two-level bit of a symbol is
+ * (symbol > center ? 0 : 1) after a positive word and its complement after a negative one (dsd_dibit.c:935-946,1019-1029).  The
+ * records' four-level dibits are those of the four-level slicer and are not what the reference's two-level digitize() stores. */
+#define DDN_DSTAR_VOICE_SYMBOLS 1992
+#define DDN_DSTAR_HEADER_SYMBOLS 2652
+#define DDN_DSTAR_HEADER_CODED 660
 /* dPMR (-fm): NXDN48's rate and hunt profile (2400 symbols/s, level ring 12), frame sync 2 compared exactly over 12 symbols in one
  * polarity - the plain word, or with inverted = 1 (-xd) the inverted one (frame_sync_try_dpmr(), src/dsp/dsd_frame_sync.c:832-862;
  * pattern index 0) -, 12-symbol warm start, dpmr_filter (RRC alpha 0.2, 135 taps at 20 samples per symbol, measured:
@@ -49,7 +62,8 @@ typedef struct ddn_fsk4_rx_config {
     int protocol;           /* DDN_FSK4_* */
     int rf_mod;             /* 0 = C4FM window / slip / clip rules (-mc), 2 = GFSK rules (-mg; what an unlocked dsd-neo
                                switches to on a DMR sync, dsd_frame_sync.c:595-600) */
-    int inverted;           /* DMR: opts->inverted_dmr; dPMR: opts->inverted_dpmr (which FS2 word is hunted); others 0 */
+    int inverted;           /* DMR: opts->inverted_dmr; dPMR: opts->inverted_dpmr (which FS2 word is hunted); others 0 (D-STAR
+                               hunts both polarities) */
     int use_matched_filter; /* opts->use_cosine_filter (default 1 in the reference) */
     int lock_symbols[4];    /* per sync class; all zero = the defaults above (DMR voice default 54 + 6 * 288, DMR RC 12) */
 } ddn_fsk4_rx_config;
@@ -252,6 +266,31 @@ int ddn_dpmr_voice_gather(const uint8_t* d_records10, size_t stride_symbols, con
 /* (host) dpmr_convert_air_interface_id() (dpmr_voice.c:477-546): the seven base-11 digits the reference prints for a raw 24-bit ID
  * ("1601621"), '*' for ten, NUL-terminated.  Like the reference, a first digit of 11 (IDs >= 11 x 1464100) is written as '0' + 11. */
 void ddn_dpmr_air_interface_id(uint32_t id, char out[8]);
+
+/* ---- D-STAR frames behind the loop's syncs (DDN_FSK4_DSTAR, -fd; ddn_dstar.hip) ------------------------------------------------
+ * Inputs are the loop's outputs: d_records10 [B][stride_symbols][10], d_counts, d_sync_pos / d_sync_pat [B][max_syncs], d_n_sync and the
+ * thresholds each sync left (d_sync_thr5, ddn_fsk4_rx_set_sync_thresholds).  One wavefront per slot c * max_syncs + k.
+ * ddn_dstar_header_decode_batch == dstar_header_decode_soft() for every header sync (pattern 2 / 3) whose 660 symbols lie inside the
+ *   records: gmsk_soft_symbol_to_viterbi_cost() per symbol against the sync's {center, max, min} (whatever the sync's polarity: a high
+ *   symbol costs towards 1), PN descramble (x^7 + x^4 + 1 seeded 0x07), the 24-stride de-interleave, the 4-state soft Viterbi
+ *   (K = 3, G = 7, 5) over 330 steps, 328 bits packed LSB first: d_hdr41 [S][41] (flags 0..2, RPT2 3..10, RPT1 11..18, DST 19..26,
+ *   SRC 27..38, CRC 39..40), d_hdr_crc_ok [S] (dstar_crc16 over 39 bytes == bytes 39..40), d_valid [S].
+ * ddn_dstar_voice_decode_batch == processDSTAR() for every sync whose 1992 voice symbols (for a header sync: 660 symbols later) lie inside
+ *   the records: the two-level slice against the sync's center, the 21 voice frames as processMbeFrame receives them, d_ambe_fr
+ *   [S][21][4][24] (one bit per byte, the 24 cells the schedule never writes are 0), and processDSTAR_SD() on the 480 slow-data bits
+ *   except APRS: d_sd_bytes [S][60] (the packed bytes as the reference prints them), d_sd_kind [S] (0 unknown, 1 header format 0x55,
+ *   2 text 0x40, 3 fixed form 0x35), d_sd_hdr41 [S][41] (the truncated-payload reload), d_sd_crc_ok [S] (its CRC in wire order),
+ *   d_sd_text [S][60] (dstar_txt as the text handler leaves it - 0x20 fill, characters at their byte positions, byte 59 = 0 - for a text
+ *   message or a fixed form that is not "$$CRC", zeros otherwise), d_valid [S].
+ * The voice frames are AMBE 3600x2400 frames.  They are handed back, not synthesised: mbe_processAmbe3600x2400Framef stays refused
+ * (include/ddn_mbe.h - the 2400 rate's layout and tables are not in the reference tree).  A slot that is not valid is written as zeros. */
+int ddn_dstar_header_decode_batch(const uint8_t* d_records10, size_t stride_symbols, const int32_t* d_counts, const int32_t* d_sync_pos,
+                                  const uint8_t* d_sync_pat, const int32_t* d_n_sync, const float* d_sync_thr5, int n_channels,
+                                  size_t max_syncs, uint8_t* d_hdr41, uint8_t* d_hdr_crc_ok, uint8_t* d_valid, void* hip_stream);
+int ddn_dstar_voice_decode_batch(const uint8_t* d_records10, size_t stride_symbols, const int32_t* d_counts, const int32_t* d_sync_pos,
+                                 const uint8_t* d_sync_pat, const int32_t* d_n_sync, const float* d_sync_thr5, int n_channels,
+                                 size_t max_syncs, uint8_t* d_ambe_fr, uint8_t* d_sd_bytes, uint8_t* d_sd_kind, uint8_t* d_sd_hdr41,
+                                 uint8_t* d_sd_crc_ok, uint8_t* d_sd_text, uint8_t* d_valid, void* hip_stream);
 
 /* CRC of decoded NXDN fields, rows = ddn_fec_nxdn_conv_batch output: kind 0 = SACCH (26 bits + CRC6, nxdn_deperm.c:1246-1261),
  * kind 1 = FACCH1 (80 bits + CRC12, nxdn_dcr_utils.c:21-42); kind + 2 = the same on rows of one bit per byte (what
