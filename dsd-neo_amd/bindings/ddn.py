@@ -392,6 +392,7 @@ FSK4_M17 = 4
 FSK4_YSF = 5
 FSK4_DPMR = 6
 FSK4_DSTAR = 7
+FSK4_EDACS = 8
 PROTOTYPES.update({
     "ddn_fsk4_rx_create": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_fsk4_rx_destroy": (None, [C.c_void_p]),
@@ -421,6 +422,8 @@ PROTOTYPES.update({
     "ddn_dpmr_air_interface_id": (None, [C.c_uint32, C.c_char_p]),
     "ddn_dstar_header_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5 + [C.c_int, C.c_size_t] + [C.c_void_p] * 4),
     "ddn_dstar_voice_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5 + [C.c_int, C.c_size_t] + [C.c_void_p] * 8),
+    "ddn_edacs_frame_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5 + [C.c_int, C.c_size_t, C.c_int, C.c_int]
+                                     + [C.c_void_p] * 10),
     "ddn_ysf_payload_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3 + [C.c_int, C.c_size_t] + [C.c_void_p] * 12),
     "ddn_fsk4_rx_get_timing": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_mode_config": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
@@ -557,6 +560,12 @@ class DstarChainResults(C.Structure):  # == ddn_dstar_chain_results
                                   "d_sd_bytes", "d_sd_kind", "d_sd_hdr41", "d_sd_crc_ok", "d_sd_text", "d_valid")]
 
 
+class EdacsChainResults(C.Structure):  # == ddn_edacs_chain_results
+    _fields_ = [("max_syncs", C.c_size_t), ("ea_mode", C.c_int), ("esk_mask", C.c_int)] + [
+        (k, C.c_void_p) for k in ("d_n_sync", "d_sync_pos", "d_sync_pat", "d_sync_thr5", "d_raw40", "d_vote40", "d_bch_ok", "d_frame_ok",
+                                  "d_msg28", "d_kind", "d_types", "d_site6", "d_valid")]
+
+
 def dpmr_air_interface_id(v):
     """ddn_dpmr_air_interface_id: the seven characters the reference prints for a raw 24-bit dPMR ID"""
     out = C.create_string_buffer(8)
@@ -606,6 +615,8 @@ PROTOTYPES.update({
     "ddn_fsk4_chain_get_results": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_fsk4_chain_get_dpmr_results": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_fsk4_chain_get_dstar_results": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ddn_fsk4_chain_get_edacs_results": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ddn_fsk4_chain_set_edacs_mode": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "ddn_fsk4_chain_flush": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_fsk4_chain_front_end": (C.c_void_p, [C.c_void_p]),
     "ddn_fsk4_chain_rx": (C.c_void_p, [C.c_void_p]),
@@ -673,6 +684,16 @@ class Fsk4ChainC:
         r = DstarChainResults()
         _check(lib().ddn_fsk4_chain_get_dstar_results(self.h, C.byref(r)), "ddn_fsk4_chain_get_dstar_results")
         return r
+
+    def edacs_results(self):
+        """ddn_fsk4_chain_get_edacs_results (DDN_FSK4_EDACS chains only)"""
+        r = EdacsChainResults()
+        _check(lib().ddn_fsk4_chain_get_edacs_results(self.h, C.byref(r)), "ddn_fsk4_chain_get_edacs_results")
+        return r
+
+    def set_edacs_mode(self, ea_mode, esk_mask):
+        """ddn_fsk4_chain_set_edacs_mode: -fh (0, 0), -fH (0, 0xA0), -fe (1, 0), -fE (1, 0xA0)"""
+        _check(lib().ddn_fsk4_chain_set_edacs_mode(self.h, ea_mode, esk_mask), "ddn_fsk4_chain_set_edacs_mode")
 
     @property
     def rx(self):

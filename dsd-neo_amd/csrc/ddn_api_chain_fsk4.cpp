@@ -107,6 +107,14 @@ struct ddn_fsk4_chain {
     // against the thresholds each sync left (s_thr / c_thr / d_thr, filed as for M17)
     bool dstar;
     uint8_t *t_h41, *t_hok, *t_hv, *t_ambe, *t_sdb, *t_kind, *t_sh41, *t_sok, *t_text, *t_vv;
+    // EDACS (protocol DDN_FSK4_EDACS): the control-channel frame behind every decoded sync (ddn_edacs.hip), read against the thresholds
+    // each sync left (s_thr / c_thr / d_thr, filed as for M17), under the mode ddn_fsk4_chain_set_edacs_mode selects
+    bool edacs;
+    int ea_mode, esk_mask;
+    uint64_t *e_raw, *e_vote;
+    uint32_t* e_msg;
+    int32_t* e_site;
+    uint8_t *e_bok, *e_fok, *e_kind, *e_types, *e_valid;
     long step;
     int last_set;
 };
@@ -147,7 +155,7 @@ ddn_fsk4_chain_destroy(ddn_fsk4_chain* c) {
     ddn_fsk4_rx_destroy(c->rx);
     ddn_mbe_batch_destroy(c->mbe);
     ddn_mbe_batch_destroy(c->mbe_i);
-    void* all[] = {c->t_h41, c->t_hok, c->t_hv, c->t_ambe, c->t_sdb, c->t_kind, c->t_sh41, c->t_sok, c->t_text, c->t_vv, c->p_bits, c->p_ham, c->p_crc, c->p_valid, c->p_kind, c->p_strong, c->p_fr, c->p_voiced, c->p_muted, c->p_vfr, c->p_vhalf,
+    void* all[] = {c->e_raw, c->e_vote, c->e_msg, c->e_site, c->e_bok, c->e_fok, c->e_kind, c->e_types, c->e_valid, c->t_h41, c->t_hok, c->t_hv, c->t_ambe, c->t_sdb, c->t_kind, c->t_sh41, c->t_sok, c->t_text, c->t_vv, c->p_bits, c->p_ham, c->p_crc, c->p_valid, c->p_kind, c->p_strong, c->p_fr, c->p_voiced, c->p_muted, c->p_vfr, c->p_vhalf,
                    c->p_vmuted, c->p_fields, c->p_id, c->p_color, c->p_tg, c->p_src, c->p_state, c->p_vslot, c->y_f96, c->y_b49, c->y_b88, c->yi_bits, c->yi_skip, c->y_r49, c->y_r88, c->yi_res, c->yi_res_out, c->yi_vn, c->yi_vslot, c->yi_pcm, c->y_fr, c->y_nfr, c->y_vslot, c->y_fich4, c->y_st, c->y_ve, c->y_last, c->y_info, c->y_dch, c->y_dst, c->y_ambe, c->y_errs, c->y_dcost, c->s_thr, c->c_thr[0], c->c_thr[1], c->d_thr, c->m_lsf, c->m_lsf_st, c->m_l6, c->m_cnt, c->m_fp, c->m_st, c->m_asm, c->m_ll,
                    c->m_ll_st, c->m_cost, c->d_disc, c->d_disc2, c->d_rec[0], c->d_rec[1], c->d_fl[0], c->d_fl[1], c->d_pay, c->d_new[0], c->d_new[1], c->d_cnt_full,
                    c->d_cnt_scan, c->d_dropped, c->s_pos, c->s_n, c->c_pos[0], c->c_pos[1], c->c_n[0], c->c_n[1], c->d_spos, c->d_ns, c->s_pat, c->s_pre,
@@ -178,11 +186,13 @@ extern "C" int
 ddn_fsk4_chain_create(const ddn_fsk4_chain_config* cfg, ddn_fsk4_chain** out) {
     if (!cfg || !out || cfg->n_channels <= 0 || cfg->samples_per_call <= 0 || cfg->block_len <= 0
         || (cfg->protocol != DDN_FSK4_DMR && cfg->protocol != DDN_FSK4_NXDN48 && cfg->protocol != DDN_FSK4_NXDN96 && cfg->protocol != DDN_FSK4_M17
-            && cfg->protocol != DDN_FSK4_YSF && cfg->protocol != DDN_FSK4_DPMR && cfg->protocol != DDN_FSK4_DSTAR)
+            && cfg->protocol != DDN_FSK4_YSF && cfg->protocol != DDN_FSK4_DPMR && cfg->protocol != DDN_FSK4_DSTAR
+            && cfg->protocol != DDN_FSK4_EDACS)
         || ((cfg->protocol == DDN_FSK4_M17 || cfg->protocol == DDN_FSK4_YSF) && (cfg->handlers || cfg->inverted))
         || (cfg->protocol == DDN_FSK4_DPMR
             && (cfg->handlers || (cfg->inverted != 0 && cfg->inverted != 1) || (cfg->rf_mod != 0 && cfg->rf_mod != 2)))
-        || (cfg->protocol == DDN_FSK4_DSTAR && (cfg->handlers || cfg->inverted || cfg->vocoder || (cfg->rf_mod != 0 && cfg->rf_mod != 2)))) {
+        || ((cfg->protocol == DDN_FSK4_DSTAR || cfg->protocol == DDN_FSK4_EDACS)
+            && (cfg->handlers || cfg->inverted || cfg->vocoder || (cfg->rf_mod != 0 && cfg->rf_mod != 2)))) {
         ddn_set_error("ddn_fsk4_chain_create: bad configuration");
         return DDN_EINVAL;
     }
@@ -208,13 +218,19 @@ ddn_fsk4_chain_create(const ddn_fsk4_chain_config* cfg, ddn_fsk4_chain** out) {
     if (c->dstar) {
         c->T = 2688; // (a header unit ends 660 + 1992 = 2652 symbols after its sync)
     }
+    c->edacs = cfg->protocol == DDN_FSK4_EDACS;
+    if (c->edacs) {
+        c->T = 320; // (a frame ends 240 symbols after its 48-symbol sync)
+    }
     int rc = DDN_OK;
     do {
         // (NXDN96: a 12.5 kHz channel at 4800 symbols/s)
         const bool wide = c->dmr || cfg->protocol == DDN_FSK4_NXDN96 || c->m17 || c->ysf;
         // (D-STAR: 4800 symbols/s behind the 6.25 kHz filter the reference picks for -fd, as ddn_host_mode.c does)
-        ddn_front_end_config fc = {c->B, 48000, (wide || c->dstar) ? 4800 : 2400, 4, wide ? DDN_LPF_12K5 : DDN_LPF_6K25, cfg->input_format,
-                                   cfg->block_len, 0.0f};
+        // (EDACS: 9600 symbols/s, two levels, behind the ProVoice channel profile dsd_rtl_channel_profile_for(9600, 2, ..) picks,
+        // src/runtime/decode_mode.c:83-99)
+        ddn_front_end_config fc = {c->B, 48000, c->edacs ? 9600 : ((wide || c->dstar) ? 4800 : 2400), c->edacs ? 2 : 4,
+                                   c->edacs ? DDN_LPF_PROVOICE : (wide ? DDN_LPF_12K5 : DDN_LPF_6K25), cfg->input_format, cfg->block_len, 0.0f};
         if ((rc = ddn_batch_create(&fc, &c->fe)) != DDN_OK) {
             break;
         }
@@ -255,6 +271,11 @@ ddn_fsk4_chain_create(const ddn_fsk4_chain_config* cfg, ddn_fsk4_chain** out) {
             const size_t du = c->ms / 2016 + 4;
             if (c->dstar && du < (size_t)c->myd) {
                 c->myd = (int)du;
+            }
+            // EDACS: 240 symbols behind every sync, then a fresh 48-symbol window: syncs at least 288 symbols apart
+            const size_t ef = c->ms / 288 + 4;
+            if (c->edacs && ef < (size_t)c->myd) {
+                c->myd = (int)ef;
             }
         }
         c->S = (size_t)c->B * (size_t)c->myd;
@@ -317,6 +338,13 @@ ddn_fsk4_chain_create(const ddn_fsk4_chain_config* cfg, ddn_fsk4_chain** out) {
                  && dalloc(&c->t_h41, S * 41) && dalloc(&c->t_hok, S) && dalloc(&c->t_hv, S) && dalloc(&c->t_ambe, S * 21 * 96)
                  && dalloc(&c->t_sdb, S * 60) && dalloc(&c->t_kind, S) && dalloc(&c->t_sh41, S * 41) && dalloc(&c->t_sok, S)
                  && dalloc(&c->t_text, S * 60) && dalloc(&c->t_vv, S);
+            if (ok && (rc = ddn_fsk4_rx_set_sync_thresholds(c->rx, c->s_thr)) != DDN_OK) {
+                break;
+            }
+        } else if (ok && c->edacs) {
+            ok = dalloc(&c->s_thr, B * my * 5) && dalloc(&c->c_thr[0], B * myc * 5) && dalloc(&c->c_thr[1], B * myc * 5) && dalloc(&c->d_thr, S * 5)
+                 && dalloc(&c->e_raw, S * 6) && dalloc(&c->e_vote, S * 2) && dalloc(&c->e_msg, S * 2) && dalloc(&c->e_site, S * 6)
+                 && dalloc(&c->e_bok, S * 2) && dalloc(&c->e_fok, S) && dalloc(&c->e_kind, S) && dalloc(&c->e_types, S * 3) && dalloc(&c->e_valid, S);
             if (ok && (rc = ddn_fsk4_rx_set_sync_thresholds(c->rx, c->s_thr)) != DDN_OK) {
                 break;
             }
@@ -432,6 +460,14 @@ fsk4_decode(ddn_fsk4_chain* c, int cur, int flush, hipStream_t st) {
             DDN_TRY(ddn_mbe_result_skip_batch(c->yi_skip, V5, c->yi_res, st));
             DDN_TRY(ddn_mbe_synth_batch(c->mbe_i, c->yi_bits, c->yi_res, (size_t)c->yvf * 5, c->yi_pcm, c->yi_res_out, st));
         }
+        HIP_TRY(hipEventRecord(c->ev_reads, st));
+        return DDN_OK;
+    }
+    if (c->edacs) {
+        // every frame of the decode list (each whole inside the row): bits, vote, BCH re-encode, ESK, message types, site ID
+        DDN_TRY(ddn_edacs_frame_decode_batch(rec, c->stride, c->d_cnt_full, c->d_spos, c->d_spat, c->d_ns, c->d_thr, c->B, (size_t)c->myd,
+                                             c->ea_mode, c->esk_mask, c->e_raw, c->e_vote, c->e_bok, c->e_fok, c->e_msg, c->e_kind, c->e_types,
+                                             c->e_site, c->e_valid, st));
         HIP_TRY(hipEventRecord(c->ev_reads, st));
         return DDN_OK;
     }
@@ -809,6 +845,43 @@ ddn_fsk4_chain_get_dstar_results(ddn_fsk4_chain* c, ddn_dstar_chain_results* r) 
     r->d_sd_crc_ok = c->t_sok;
     r->d_sd_text = c->t_text;
     r->d_valid = c->t_vv;
+    return DDN_OK;
+}
+
+extern "C" int
+ddn_fsk4_chain_set_edacs_mode(ddn_fsk4_chain* c, int ea_mode, int esk_mask) {
+    if (!c || !c->edacs || (ea_mode != 0 && ea_mode != 1) || (esk_mask != 0 && esk_mask != 0xA0)) {
+        ddn_set_error("ddn_fsk4_chain_set_edacs_mode: an EDACS chain, ea_mode 0 / 1 and esk_mask 0 / 0xA0 (-fh, -fH, -fe, -fE)");
+        return DDN_EINVAL;
+    }
+    c->ea_mode = ea_mode;
+    c->esk_mask = esk_mask;
+    return DDN_OK;
+}
+
+extern "C" int
+ddn_fsk4_chain_get_edacs_results(ddn_fsk4_chain* c, ddn_edacs_chain_results* r) {
+    if (!c || !r || !c->edacs) {
+        ddn_set_error("ddn_fsk4_chain_get_edacs_results: not an EDACS chain");
+        return DDN_EINVAL;
+    }
+    memset(r, 0, sizeof(*r));
+    r->max_syncs = (size_t)c->myd;
+    r->ea_mode = c->ea_mode;
+    r->esk_mask = c->esk_mask;
+    r->d_n_sync = c->d_ns;
+    r->d_sync_pos = c->d_spos;
+    r->d_sync_pat = c->d_spat;
+    r->d_sync_thr5 = c->d_thr;
+    r->d_raw40 = c->e_raw;
+    r->d_vote40 = c->e_vote;
+    r->d_bch_ok = c->e_bok;
+    r->d_frame_ok = c->e_fok;
+    r->d_msg28 = c->e_msg;
+    r->d_kind = c->e_kind;
+    r->d_types = c->e_types;
+    r->d_site6 = c->e_site;
+    r->d_valid = c->e_valid;
     return DDN_OK;
 }
 

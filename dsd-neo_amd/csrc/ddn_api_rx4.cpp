@@ -53,6 +53,14 @@ sign_bits(const char* s) {
     }
     return v;
 }
+uint32_t
+sign_bits_n(const char* s, int n) { // the first n symbols of a longer word
+    uint32_t v = 0;
+    for (int k = 0; k < n; k++) {
+        v = (v << 1) | (s[k] == '1' ? 1u : 0u);
+    }
+    return v;
+}
 } // namespace
 
 struct ddn_fsk4_rx {
@@ -146,13 +154,21 @@ ddn_fsk4_rx_create(const ddn_fsk4_rx_config* cfg, ddn_fsk4_rx** out) {
     *out = nullptr;
     if (cfg->n_channels <= 0 || cfg->out_rate_hz <= 0
         || (cfg->protocol != DDN_FSK4_DMR && cfg->protocol != DDN_FSK4_NXDN48 && cfg->protocol != DDN_FSK4_NXDN96 && cfg->protocol != DDN_FSK4_M17
-            && cfg->protocol != DDN_FSK4_YSF && cfg->protocol != DDN_FSK4_DPMR && cfg->protocol != DDN_FSK4_DSTAR)
+            && cfg->protocol != DDN_FSK4_YSF && cfg->protocol != DDN_FSK4_DPMR && cfg->protocol != DDN_FSK4_DSTAR
+            && cfg->protocol != DDN_FSK4_EDACS)
         || (cfg->rf_mod != 0 && cfg->rf_mod != 2) || (cfg->inverted && cfg->protocol != DDN_FSK4_DMR && cfg->protocol != DDN_FSK4_DPMR)) {
-        ddn_set_error("ddn_fsk4_rx_create: bad configuration (protocol DMR | NXDN48 | NXDN96 | M17 | YSF | DPMR | DSTAR, rf_mod 0 | 2, "
-                      "inverted only for DMR and DPMR)");
+        ddn_set_error("ddn_fsk4_rx_create: bad configuration (protocol DMR | NXDN48 | NXDN96 | M17 | YSF | DPMR | DSTAR | EDACS, "
+                      "rf_mod 0 | 2, inverted only for DMR and DPMR)");
         return DDN_EINVAL;
     }
-    {
+    if (cfg->protocol == DDN_FSK4_EDACS) {
+        // the 9600_2 profile is 5 samples per symbol (decode_mode_apply_edacs_pv(): samplesPerSymbol = 5 at 48 ksps); the kernel's
+        // longer hand-off queue for it holds 4-sample symbols, its straight pass at most 11
+        if (cfg->out_rate_hz % 9600 != 0 || cfg->out_rate_hz / 9600 < 5 || cfg->out_rate_hz / 9600 > 10) {
+            ddn_set_error("ddn_fsk4_rx_create: EDACS needs out_rate_hz = 9600 x 5..10 (48 ksps: 5 samples per symbol)");
+            return DDN_ERANGE;
+        }
+    } else {
         const int sym_rate = (cfg->protocol == DDN_FSK4_NXDN48 || cfg->protocol == DDN_FSK4_DPMR) ? 2400 : 4800;
         if (cfg->out_rate_hz / sym_rate < 8 || cfg->out_rate_hz / sym_rate > 21) {
             // the kernel's per-round hand-off queue and its whole-symbol pass are sized for 8..21 samples per symbol
@@ -251,6 +267,35 @@ ddn_fsk4_rx_create(const ddn_fsk4_rx_config* cfg, ddn_fsk4_rx** out) {
         tap_bits = ddn_dmr_filter_bits;
         lock_default[DDN_FSK4_CLASS_DATA] = DDN_DSTAR_HEADER_SYMBOLS;
         lock_default[DDN_FSK4_CLASS_VOICE] = DDN_DSTAR_VOICE_SYMBOLS;
+    } else if (cfg->protocol == DDN_FSK4_EDACS) {
+        // -fh / -fH / -fe / -fE: 9600 symbols/s on the 9600_2 hunt profile, no matched filter (symbol_apply_matched_filter() has no
+        // EDACS branch, src/dsp/dsd_symbol.c:300-336), level ring 24 (frame_sync_select_t_max(), default branch).  The two 48-symbol
+        // words are compared exactly (frame_sync_try_provoice(), dsd_frame_sync.c:1421-1450; include/dsd-neo/core/sync_patterns.h:
+        // 107-108): EDACS_SYNC is accepted as DSD_SYNC_EDACS_NEG, INV_EDACS_SYNC as DSD_SYNC_EDACS_POS (types = synctype_ids.h:85-86
+        // + 1), with the basic lock and a 48-symbol outer-only warm start (frame_sync_accept_edacs(), :1399-1409).  Bits 0..23 of a
+        // word go to pat_bits, 24..47 to pat_hi.  240 symbols behind a sync (edacs_collect_bits()); the two-level slice
+        // (store_two_level_dibit(), src/core/frames/dsd_dibit.c:938-948) belongs to ddn_edacs.hip.
+        static const char kEdacs[] = "313131313131313131313111333133133131313131313131";
+        char inv[49];
+        for (int k = 0; k < 48; k++) {
+            inv[k] = kEdacs[k] == '3' ? '1' : '3';
+        }
+        inv[48] = 0;
+        d.sym_rate = 9600;
+        d.win_len = d.warm_len = 48;
+        d.t_max = 24;
+        d.n_pat = 2;
+        d.use_filter = 0;
+        const char* words[2] = {kEdacs, inv};
+        for (int k = 0; k < 2; k++) {
+            d.pat_hi[k] = sign_bits_n(words[k], 24);
+            d.pat_bits[k] = sign_bits_n(words[k] + 24, 24);
+            d.pat_type[k] = (uint8_t)(k == 0 ? DDN_EDACS_TYPE_NEG : DDN_EDACS_TYPE_POS);
+            d.pat_neg[k] = (uint8_t)(k == 0 ? 1 : 0);
+        }
+        d.nt = DDN_DMR_FILTER_TAPS; // (unused)
+        tap_bits = ddn_dmr_filter_bits;
+        lock_default[0] = DDN_EDACS_FRAME_SYMBOLS;
     } else if (cfg->protocol == DDN_FSK4_DPMR) {
         // -fm: FS2 only, exact over 12 symbols, the plain word or - under -xd (inverted) - the inverted one
         // (frame_sync_try_dpmr(), src/dsp/dsd_frame_sync.c:832-862; include/dsd-neo/core/sync_patterns.h:123-132; types =
@@ -398,6 +443,10 @@ ddn_fsk4_rx_set_handlers(ddn_fsk4_rx* b, int enable) {
     }
     if (enable && b->cfg.inverted) {
         ddn_set_error("ddn_fsk4_rx_set_handlers: the handlers are the reference's plain -fs ones (inverted = 0)");
+        return DDN_EINVAL;
+    }
+    if (enable && b->cfg.protocol == DDN_FSK4_EDACS) {
+        ddn_set_error("ddn_fsk4_rx_set_handlers: EDACS frames are a fixed count (no handler family)");
         return DDN_EINVAL;
     }
     if (enable && b->cfg.protocol == DDN_FSK4_DSTAR) {

@@ -134,6 +134,7 @@ typedef struct DdnFsk4Config {
     int max_events; /* capacity of the per-channel event list */
     float* sync_thr; /* optional [B][max_sync][5]: {center, umid, lmid, max, min} as every accepted sync leaves them (after the warm
                         start) - what a frame decoder that works on soft symbols needs (M17 LSF: thresholds are static inside a frame) */
+    uint32_t pat_hi[DDN_FSK4_MAX_PAT]; /* win_len > 24 (EDACS): sign bits 24..47 of each pattern, pat_bits holding bits 0..23 */
 } DdnFsk4Config;
 typedef struct DdnFsk4State {
     long long filt_start, n_abs;
@@ -145,7 +146,10 @@ typedef struct DdnFsk4State {
     uint32_t hist_bits;
     int hunt_pos, need_reset;
     int hmode, hidx; /* handler mode: phase (ddn_fsk4h_dev.h) and the index of the next dibit inside the burst / frame */
-    int hlich;       /* NXDN: the LICH's high bits so far */
+    union {
+        int hlich;        /* NXDN: the LICH's high bits so far (M17: the polarity) */
+        uint32_t hist_hi; /* win_len > 24 (EDACS, no handlers): sign history bits 24..47, hist_bits holding bits 0..23 */
+    };
 } DdnFsk4State;
 
 typedef struct DdnCqpskState { /* per-channel words of demod_state the CQPSK chain carries besides ted_state_t */

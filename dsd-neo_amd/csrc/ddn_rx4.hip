@@ -38,12 +38,14 @@ namespace {
 constexpr int RTILES = 4;               // staged tiles per channel (power of two: ring index = sample index & RMASK)
 constexpr int HN = DDN_FSK4_HIST;
 
-template <int CPW>
+template <int CPW, bool SHORT = false>
 struct Lds4 {
     // tile shape: 128-sample tiles where the rows are few (half the round overhead per symbol: a 64-sample tile holds only
     // 3.2 NXDN48 symbols), 64 from 16 lanes per wave on (LDS)
     static constexpr int TSW = CPW <= 8 ? 128 : 64, RMASKW = RTILES * TSW - 1;
-    static constexpr int QCAPW = CPW <= 8 ? 24 : 12; // symbols a lane can finish in one round (TSW / 7 + 1) + sync entries + slack
+    // symbols a lane can finish in one round (TSW / 7 + 1) + sync entries + slack; SHORT = 5 samples per symbol (EDACS at 48 ksps:
+    // a symbol that slips early is 4 samples long, TSW / 4 + 1)
+    static constexpr int QCAPW = SHORT ? (CPW <= 8 ? 40 : 24) : (CPW <= 8 ? 24 : 12);
     float lb[24][CPW];
     float sh[HN][CPW];
     uint8_t ph[HN][CPW];
@@ -119,12 +121,19 @@ struct Fsk4Cfg {
     // PROTO 7 D-STAR (-fd): 4800 symbols/s on the 4800_2 hunt profile (level ring 24), the four 24-symbol words compared exactly
     // (frame_sync_try_dstar(), src/dsp/dsd_frame_sync.c:1452-1503), 24-symbol warm start, no matched filter (dsd_symbol.c:300-336),
     // fixed counts behind a sync (processDSTAR() 1992 symbols, processDSTAR_HD() 660 more)
-    static constexpr int sym_rate = (PROTO == 2 || PROTO == 6) ? 2400 : 4800;
-    static constexpr int win_len = (PROTO == 1 || PROTO == 7) ? 24 : (PROTO == 4 ? 8 : (PROTO == 5 ? 20 : (PROTO == 6 ? 12 : 10)));
+    // PROTO 8 EDACS (-fh / -fH / -fe / -fE): 9600 symbols/s on the 9600_2 hunt profile (5 samples per symbol at 48 ksps, level ring
+    // 24), the two 48-symbol words compared exactly (frame_sync_try_provoice(), src/dsp/dsd_frame_sync.c:1421-1450), 48-symbol warm
+    // start (frame_sync_accept_edacs(), :1399-1409), no matched filter, a fixed count behind a sync (edacs() reads 240 bits).  The
+    // sign history is 48 symbols long: bits 0..23 in hist_bits, 24..47 in hist_hi (`wide`); the patterns' high halves are in pat_hi.
+    static constexpr int sym_rate = (PROTO == 2 || PROTO == 6) ? 2400 : (PROTO == 8 ? 9600 : 4800);
+    static constexpr int win_len = (PROTO == 1 || PROTO == 7) ? 24 : (PROTO == 4 ? 8 : (PROTO == 5 ? 20 : (PROTO == 6 ? 12 : (PROTO == 8 ? 48 : 10))));
     static constexpr int t_max = (PROTO == 2 || PROTO == 6) ? 12 : 24;
-    static constexpr int warm_len = (PROTO == 1 || PROTO == 7) ? 24 : (PROTO == 4 ? 8 : (PROTO == 5 ? 20 : (PROTO == 6 ? 12 : 10)));
-    static constexpr int n_pat = PROTO == 1 ? 9 : (PROTO == 4 ? 12 : (PROTO == 5 ? 2 : (PROTO == 6 ? 1 : (PROTO == 7 ? 4 : 10))));
-    static constexpr int confirm = (PROTO == 1 || PROTO == 4 || PROTO == 5 || PROTO == 6 || PROTO == 7) ? 0 : 1, dmr_window = PROTO == 1 ? 1 : 0, redigitize = PROTO == 1 ? 1 : 0;
+    static constexpr int warm_len = (PROTO == 1 || PROTO == 7) ? 24 : (PROTO == 4 ? 8 : (PROTO == 5 ? 20 : (PROTO == 6 ? 12 : (PROTO == 8 ? 48 : 10))));
+    static constexpr int n_pat = PROTO == 1 ? 9 : (PROTO == 4 ? 12 : (PROTO == 5 || PROTO == 8 ? 2 : (PROTO == 6 ? 1 : (PROTO == 7 ? 4 : 10))));
+    static constexpr int confirm = (PROTO == 1 || PROTO == 4 || PROTO == 5 || PROTO == 6 || PROTO == 7 || PROTO == 8) ? 0 : 1, dmr_window = PROTO == 1 ? 1 : 0, redigitize = PROTO == 1 ? 1 : 0;
+    static constexpr bool wide = win_len > 24;      // sign history of more than 24 symbols (hist_bits + hist_hi)
+    static constexpr int hcap = wide ? win_len : 24; // symbols the sign history counts up to
+    static constexpr bool short_sym = PROTO == 8;   // 5-sample symbols: the longer hand-off queue (Lds4 SHORT)
     static constexpr bool m17 = PROTO == 4;
     static constexpr int slow_type = 0;
     static constexpr int nt = PROTO == 2 ? DDN_NXDN48_FILTER_TAPS : (PROTO == 6 ? DDN_DPMR_FILTER_TAPS : DDN_DMR_FILTER_TAPS);
@@ -215,10 +224,11 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
           uint8_t* __restrict__ pre, uint8_t* __restrict__ pre_rel, int32_t* __restrict__ n_sync, int max_sync,
           int32_t* __restrict__ hwords, uint8_t* __restrict__ hpay_store, const DdnFec3Tables* __restrict__ htab,
           int32_t* __restrict__ events, int32_t* __restrict__ n_events) {
-    constexpr int TSW = Lds4<CPW>::TSW, RMASKW = Lds4<CPW>::RMASKW, QCAPW = Lds4<CPW>::QCAPW;
+    using LdsT = Lds4<CPW, Fsk4Cfg<PROTO>::short_sym>;
+    constexpr int TSW = LdsT::TSW, RMASKW = LdsT::RMASKW, QCAPW = LdsT::QCAPW;
     extern __shared__ unsigned char smem_raw[];
-    Lds4<CPW>& L = *reinterpret_cast<Lds4<CPW>*>(smem_raw);
-    Lds4H<CPW>& LH = *reinterpret_cast<Lds4H<CPW>*>(smem_raw + ((sizeof(Lds4<CPW>) + 15) & ~(size_t)15));
+    LdsT& L = *reinterpret_cast<LdsT*>(smem_raw);
+    Lds4H<CPW>& LH = *reinterpret_cast<Lds4H<CPW>*>(smem_raw + ((sizeof(LdsT) + 15) & ~(size_t)15));
     const int n = (int)n_long; // the C-ABI keeps a call below 2^31 samples
     const int lane = threadIdx.x & 63;
     const bool loader = threadIdx.x >= 64;
@@ -241,6 +251,14 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
     }
     const bool use_flt = cfg.use_filter != 0;
     float* const sync_thr_out = cfgp->sync_thr;
+    // wide sign history (EDACS): the 48-symbol patterns, uniform for the whole batch
+    unsigned long long wpat[Cfg::wide ? Cfg::n_pat : 1] = {};
+    if constexpr (Cfg::wide) {
+        for (int k = 0; k < Cfg::n_pat; k++) {
+            wpat[k] = (unsigned long long)cfgp->pat_bits[k] | ((unsigned long long)cfgp->pat_hi[k] << 24);
+        }
+    }
+    constexpr unsigned long long WMASK48 = 0xFFFFFFFFFFFFull;
     constexpr int NT = Cfg::nt;
 
     DdnFsk4State s;
@@ -645,6 +663,10 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
                         const int sp0 = __shfl(pos, g), c0 = __shfl(s.hist_count, g), flt_o = __shfl(s.filter_on, g);
                         int jit = __shfl(s.jitter, g);
                         const uint32_t h0 = (uint32_t)__shfl((int)s.hist_bits, g);
+                        uint32_t h0h = 0;
+                        if constexpr (Cfg::wide) {
+                            h0h = (uint32_t)__shfl((int)s.hist_hi, g);
+                        }
                         const int sh_o = __shfl(s.shead, g), li_o = __shfl(s.lidx, g), qk_o = __shfl(qk, g), ls_type = __shfl(s.lastsync, g);
                         const int m17_pol_o = Cfg::m17 ? __shfl(s.hlich, g) : 0;
                         const float cen_o = __shfl(s.center, g), ls_o = __shfl(s.lastsample, g);
@@ -760,11 +782,22 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
                         }
                         const uint32_t sw = (uint32_t)((__ballot(gact && l < m && sym > 0.0f) >> (g * OW)) & GM);
                         const int lj = l < 31 ? l : 31;
-                        const uint32_t hj = ((h0 << (lj + 1)) | __brev(sw << (31 - lj))) & 0xFFFFFFu;
+                        uint32_t hj;
+                        unsigned long long hjw = 0; // (wide: the 48-bit history after symbol l)
+                        if constexpr (Cfg::wide) {
+                            hjw = (((((unsigned long long)h0h << 24) | h0) << (lj + 1)) | __brev(sw << (31 - lj))) & WMASK48;
+                            hj = (uint32_t)hjw & 0xFFFFFFu;
+                        } else {
+                            hj = ((h0 << (lj + 1)) | __brev(sw << (31 - lj))) & 0xFFFFFFu;
+                        }
                         bool syn = false;
                         if (gact && l < m && (c0 + l + 1 >= cfg.win_len) && !(cfg.dbg & 8)) {
                             const uint32_t w = hj & wmask;
-                            if (Cfg::m17) {
+                            if constexpr (Cfg::wide) {
+                                for (int k = 0; k < Cfg::n_pat; k++) {
+                                    syn |= (hjw == wpat[k]);
+                                }
+                            } else if (Cfg::m17) {
                                 int pa;
                                 syn = m17_hit(w, ls_type, m17_pol_o, L.pat_meta, pa) >= 0;
                             } else {
@@ -785,6 +818,10 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
                         const float sumf = __shfl(wsum, src1);
                         const int cntf = __shfl(wc, src1);
                         const uint32_t hf = (uint32_t)__shfl((int)hj, src1);
+                        uint32_t hfh = 0;
+                        if constexpr (Cfg::wide) {
+                            hfh = (uint32_t)__shfl((int)(uint32_t)(hjw >> 24), src1);
+                        }
                         if (gact && l < m) { // symbol history, level window, the queue entry the helper wave slices and stores
                             const int slot = (sh_o + l) & (HN - 1);
                             L.sh[slot][g] = sym;
@@ -811,8 +848,11 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
                                 int k = s.lidx + m_own;
                                 s.lidx = k >= cfg.t_max ? k - cfg.t_max : k;
                                 s.level_count = s.level_count + m_own < cfg.t_max ? s.level_count + m_own : cfg.t_max;
-                                s.hist_count = s.hist_count + m_own < 24 ? s.hist_count + m_own : 24;
+                                s.hist_count = s.hist_count + m_own < Cfg::hcap ? s.hist_count + m_own : Cfg::hcap;
                                 s.hist_bits = hf;
+                                if constexpr (Cfg::wide) {
+                                    s.hist_hi = hfh;
+                                }
                                 if (s.hist_count >= 8) {
                                     s.maxref = s.max;
                                     s.minref = s.min;
@@ -843,6 +883,10 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
                             const int flt_o = __builtin_amdgcn_readlane(s.filter_on, ow);
                             int jit = __builtin_amdgcn_readlane(s.jitter, ow);
                             const uint32_t h0 = (uint32_t)__builtin_amdgcn_readlane((int)s.hist_bits, ow);
+                            uint32_t h0h = 0;
+                            if constexpr (Cfg::wide) {
+                                h0h = (uint32_t)__builtin_amdgcn_readlane((int)s.hist_hi, ow);
+                            }
                             const int sh_o = __builtin_amdgcn_readlane(s.shead, ow), li_o = __builtin_amdgcn_readlane(s.lidx, ow);
                             const int qk_o = __builtin_amdgcn_readlane(qk, ow), ls_type = __builtin_amdgcn_readlane(s.lastsync, ow);
                             const int m17_pol_o = Cfg::m17 ? __builtin_amdgcn_readlane(s.hlich, ow) : 0; // (M17 keeps its polarity in hlich)
@@ -944,11 +988,22 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
                             }
                             const uint32_t sw = (uint32_t)__ballot(lane < m && sym > 0.0f);
                             const int lj = lane < 31 ? lane : 31;
-                            const uint32_t hj = ((h0 << (lj + 1)) | __brev(sw << (31 - lj))) & 0xFFFFFFu;
+                            uint32_t hj;
+                            unsigned long long hjw = 0; // (wide: the 48-bit history after symbol `lane`)
+                            if constexpr (Cfg::wide) {
+                                hjw = (((((unsigned long long)h0h << 24) | h0) << (lj + 1)) | __brev(sw << (31 - lj))) & WMASK48;
+                                hj = (uint32_t)hjw & 0xFFFFFFu;
+                            } else {
+                                hj = ((h0 << (lj + 1)) | __brev(sw << (31 - lj))) & 0xFFFFFFu;
+                            }
                             bool syn = false;
                             if (lane < m && (c0 + lane + 1 >= cfg.win_len) && !(cfg.dbg & 8)) {
                                 const uint32_t w = hj & wmask;
-                                if (Cfg::m17) { // (the owner's sync type and polarity stand still while it hunts)
+                                if constexpr (Cfg::wide) {
+                                    for (int k = 0; k < Cfg::n_pat; k++) {
+                                        syn |= (hjw == wpat[k]);
+                                    }
+                                } else if (Cfg::m17) { // (the owner's sync type and polarity stand still while it hunts)
                                     int pa;
                                     syn = m17_hit(w, ls_type, m17_pol_o, L.pat_meta, pa) >= 0;
                                 } else {
@@ -971,6 +1026,10 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
                             const float sumf = __shfl(wsum, m - 1);
                             const int cntf = __builtin_amdgcn_readlane(wc, m - 1);
                             const uint32_t hf = (uint32_t)__builtin_amdgcn_readlane((int)hj, m - 1);
+                            uint32_t hfh = 0;
+                            if constexpr (Cfg::wide) {
+                                hfh = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(hjw >> 24), m - 1);
+                            }
                             if (lane < m) { // symbol history, level window, the queue entry the helper wave slices and stores
                                 const int slot = (sh_o + lane) & (HN - 1);
                                 L.sh[slot][ow] = sym;
@@ -994,7 +1053,10 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
                                 s.lidx = k >= cfg.t_max ? k - cfg.t_max : k;
                                 s.level_count = s.level_count + m < cfg.t_max ? s.level_count + m : cfg.t_max;
                                 s.hist_bits = hf;
-                                s.hist_count = c0 + m < 24 ? c0 + m : 24;
+                                if constexpr (Cfg::wide) {
+                                    s.hist_hi = hfh;
+                                }
+                                s.hist_count = c0 + m < Cfg::hcap ? c0 + m : Cfg::hcap;
                                 if (s.hist_count >= 8) {
                                     s.maxref = s.max;
                                     s.minref = s.min;
@@ -1436,8 +1498,14 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
                         s.level_count = s.level_count < cfg.t_max ? s.level_count + 1 : cfg.t_max;
                         s.lidx = (s.lidx == cfg.t_max - 1) ? 0 : s.lidx + 1;
                         const uint32_t bit = sym > 0.0f ? 1u : 0u;
-                        s.hist_bits = ((s.hist_bits << 1) | bit) & 0xFFFFFFu;
-                        s.hist_count = s.hist_count < 24 ? s.hist_count + 1 : 24;
+                        if constexpr (Cfg::wide) {
+                            const unsigned long long h = (((((unsigned long long)s.hist_hi << 24) | s.hist_bits) << 1) | bit) & WMASK48;
+                            s.hist_bits = (uint32_t)h & 0xFFFFFFu;
+                            s.hist_hi = (uint32_t)(h >> 24);
+                        } else {
+                            s.hist_bits = ((s.hist_bits << 1) | bit) & 0xFFFFFFu;
+                        }
+                        s.hist_count = s.hist_count < Cfg::hcap ? s.hist_count + 1 : Cfg::hcap;
                         bool accepted = false;
                         if (s.hist_count >= 8) {
                             s.maxref = s.max;
@@ -1445,7 +1513,12 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
                             int hit = -1;
                             if (s.hist_count >= cfg.win_len && !(cfg.dbg & 8)) {
                                 const uint32_t w = s.hist_bits & wmask;
-                                if (Cfg::m17) {
+                                if constexpr (Cfg::wide) {
+                                    const unsigned long long ww = ((unsigned long long)s.hist_hi << 24) | s.hist_bits;
+                                    for (int k = Cfg::n_pat - 1; k >= 0; k--) {
+                                        hit = (ww == wpat[k]) ? k : hit;
+                                    }
+                                } else if (Cfg::m17) {
                                     int pa;
                                     hit = m17_hit(w, s.lastsync, s.hlich, L.pat_meta, pa);
                                     s.hlich = pa;
@@ -1944,7 +2017,8 @@ launch(const float* raw, const float* filt, const float* prev_tail, float* fstal
        size_t max_sym, const int32_t* lock4, int32_t* sync_pos, uint8_t* sync_pat, uint8_t* pre, uint8_t* pre_rel,
        int32_t* n_sync, int max_sync, int32_t* hwords, uint8_t* hpay, const DdnFec3Tables* htab, int32_t* events,
        int32_t* n_events, hipStream_t st) {
-    const size_t shmem = HM ? (((sizeof(Lds4<CPW>) + 15) & ~(size_t)15) + sizeof(Lds4H<CPW>)) : sizeof(Lds4<CPW>);
+    using LdsT = Lds4<CPW, Fsk4Cfg<PROTO>::short_sym>;
+    const size_t shmem = HM ? (((sizeof(LdsT) + 15) & ~(size_t)15) + sizeof(Lds4H<CPW>)) : sizeof(LdsT);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fsk4_rx<CPW, MAXW, PROTO, HM>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     if (e != hipSuccess) {
@@ -1976,11 +2050,11 @@ ddn_dev_fsk4_rx(const float* raw, const float* filt, const float* prev_tail, flo
     if (n_channels <= 0 || n <= 0) {
         return hipSuccess;
     }
-    if (protocol < 1 || protocol > 7) {
+    if (protocol < 1 || protocol > 8) {
         return hipErrorInvalidValue;
     }
-    if ((protocol == 4 || protocol == 5 || protocol == 6 || protocol == 7) && handlers) {
-        return hipErrorInvalidValue; // M17 / YSF / dPMR / D-STAR frames are fixed counts: no handler family
+    if ((protocol == 4 || protocol == 5 || protocol == 6 || protocol == 7 || protocol == 8) && handlers) {
+        return hipErrorInvalidValue; // M17 / YSF / dPMR / D-STAR / EDACS frames are fixed counts: no handler family
     }
     const DdnFec3Tables* htab = nullptr;
     if (handlers) {
@@ -2018,6 +2092,9 @@ ddn_dev_fsk4_rx(const float* raw, const float* filt, const float* prev_tail, flo
         }                                                                                                                  \
         if (protocol == 7) { /* D-STAR: 4800 symbols/s, fixed counts */                                                    \
             return launch<CPW_, 12, 7, false>(DDN_RX4_ARGS);                                                                \
+        }                                                                                                                  \
+        if (protocol == 8) { /* EDACS: 9600 symbols/s, 48-symbol words, a fixed count */                                   \
+            return launch<CPW_, 12, 8, false>(DDN_RX4_ARGS);                                                                \
         }                                                                                                                  \
         return handlers ? launch<CPW_, MAXW_, 2, true>(DDN_RX4_ARGS) : launch<CPW_, MAXW_, 2, false>(DDN_RX4_ARGS);         \
     } while (0)

@@ -287,7 +287,7 @@ typedef struct ddn_fsk4_chain_config {
     int samples_per_call;
     int block_len;
     int input_format; /* DDN_IN_CU8 / DDN_IN_CF32 */
-    int protocol;     /* DDN_FSK4_DMR / DDN_FSK4_NXDN48 / _NXDN96 / _M17 / _YSF / _DPMR / _DSTAR (include/ddn_fsk4.h) */
+    int protocol;     /* DDN_FSK4_DMR / DDN_FSK4_NXDN48 / _NXDN96 / _M17 / _YSF / _DPMR / _DSTAR / _EDACS (include/ddn_fsk4.h) */
     int rf_mod;       /* 0 = C4FM rules, 2 = GFSK rules (what dsd-neo runs DMR with) */
     int inverted;     /* DMR: opts->inverted_dmr (handlers need 0); dPMR: opts->inverted_dpmr (-xd) */
     int handlers;     /* 1 = the reference's handlers decide the in-frame lengths (ddn_fsk4_rx_set_handlers) */
@@ -494,6 +494,34 @@ typedef struct ddn_dstar_chain_results { /* device pointers valid until the next
     const uint8_t* d_valid;       /* [S] 1 = the 1992 voice symbols were inside the records (always, except at flush past the end) */
 } ddn_dstar_chain_results;
 int ddn_fsk4_chain_get_dstar_results(ddn_fsk4_chain* c, ddn_dstar_chain_results* out);
+
+/* ---- EDACS control channel (protocol DDN_FSK4_EDACS): the fsk4 chain at 9600 symbols/s, two levels, behind the ProVoice channel profile
+ * (DDN_LPF_PROVOICE, what dsd_rtl_channel_profile_for(9600, 2, ..) picks - src/runtime/decode_mode.c:83-99), handlers = 0, inverted = 0
+ * (both polarities are hunted), rf_mod 0 / 2, vocoder = 0, and a 320-symbol carry: a frame ends 240 symbols behind its 48-symbol sync.
+ * Every frame is decoded once, whole, in the first call whose records hold its last symbol (flush decodes the tail), by
+ * ddn_edacs_frame_decode_batch (include/ddn_fsk4.h) against the thresholds its sync left.  The mode is -fh (ea_mode 0, esk_mask 0) until
+ * ddn_fsk4_chain_set_edacs_mode selects another: -fH (0, 0xA0), -fe (1, 0), -fE (1, 0xA0); any other value, or another protocol, is
+ * DDN_EINVAL, and the new mode applies from the next decode on.  ddn_fsk4_chain_get_edacs_results refuses any other protocol (DDN_EINVAL);
+ * ddn_fsk4_chain_config and ddn_fsk4_chain_results keep their sizes. */
+typedef struct ddn_edacs_chain_results { /* device pointers valid until the next run; S = n_channels * max_syncs sync slots */
+    size_t max_syncs;          /* sync slots per channel */
+    int ea_mode, esk_mask;     /* the mode the slots were decoded under */
+    const int32_t* d_n_sync;   /* [n_channels] frames (syncs) decoded in this call */
+    const int32_t* d_sync_pos; /* [S] record index of each sync's last symbol in this call's rows (ddn_fsk4_chain_results) */
+    const uint8_t* d_sync_pat; /* [S] 0 = EDACS_SYNC (-EDACS, negative), 1 = INV_EDACS_SYNC (+EDACS) */
+    const float* d_sync_thr5;  /* [S][5] {center, umid, lmid, max, min} the sync left */
+    const uint64_t* d_raw40;   /* [S][6] the six 40-bit words as received */
+    const uint64_t* d_vote40;  /* [S][2] the two voted codewords */
+    const uint8_t* d_bch_ok;   /* [S][2] voted codeword == the BCH(40,28) re-encoding of its message */
+    const uint8_t* d_frame_ok; /* [S] both (otherwise the reference prints "BCH FAIL") */
+    const uint32_t* d_msg28;   /* [S][2] the 28-bit messages after the ESK XOR */
+    const uint8_t* d_kind;     /* [S] 0 not a good frame, 1 standard, 2 EA, 3 standard site ID, 4 EA site ID */
+    const uint8_t* d_types;    /* [S][3] {MT-A, MT-B, MT-D} (standard) or {MT1, MT2, 0} (EA) of message 1 */
+    const int32_t* d_site6;    /* [S][6] standard: {site_id, priority, cc_lcn, scat, failsoft, auxiliary}; EA: {site_id, area, 0..} */
+    const uint8_t* d_valid;    /* [S] 1 = the 240 symbols were inside the records */
+} ddn_edacs_chain_results;
+int ddn_fsk4_chain_set_edacs_mode(ddn_fsk4_chain* c, int ea_mode, int esk_mask);
+int ddn_fsk4_chain_get_edacs_results(ddn_fsk4_chain* c, ddn_edacs_chain_results* out);
 
 /* ---- a mixed batch (BASELINE configs[3]): P25 Phase 1 + DMR + NXDN48 channel groups of one GPU, every receive loop with the
  * reference's handlers inside it; one stream per group inside the object, the groups' stages lined up (the three front ends, then the

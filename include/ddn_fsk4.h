@@ -18,7 +18,24 @@
 extern "C" {
 #endif
 
-enum { DDN_FSK4_DMR = 1, DDN_FSK4_NXDN48 = 2, DDN_FSK4_NXDN96 = 3, DDN_FSK4_M17 = 4, DDN_FSK4_YSF = 5, DDN_FSK4_DPMR = 6, DDN_FSK4_DSTAR = 7 };
+enum { DDN_FSK4_DMR = 1, DDN_FSK4_NXDN48 = 2, DDN_FSK4_NXDN96 = 3, DDN_FSK4_M17 = 4, DDN_FSK4_YSF = 5, DDN_FSK4_DPMR = 6, DDN_FSK4_DSTAR = 7,
+       DDN_FSK4_EDACS = 8 };
+/* EDACS control channel (-fh, -fH, -fe, -fE; decode_mode_apply_edacs_pv(), src/runtime/decode_mode.c:431-456): two levels at 9600
+ * symbols/s on the 9600_2 hunt profile - 5 samples per symbol at 48 ksps (out_rate_hz must be 9600 x 5..10), level ring 24 - with no
+ * matched filter (use_matched_filter is ignored), rf_mod 2 (what -fh sets) or 0, inverted refused (both polarities are hunted).
+ * The two 48-symbol words are compared exactly (frame_sync_try_provoice(), src/dsp/dsd_frame_sync.c:1421-1450;
+ * include/dsd-neo/core/sync_patterns.h:107-108) and accepted with the basic lock and a 48-symbol outer-only warm start
+ * (frame_sync_accept_edacs(), :1399-1409).  Sync pattern index: 0 = EDACS_SYNC, accepted as DSD_SYNC_EDACS_NEG (negative polarity,
+ * flags bit 4), 1 = INV_EDACS_SYNC, accepted as DSD_SYNC_EDACS_POS - the reference's own mapping.  lock_symbols[0] = 240 = the bits
+ * edacs() reads behind a sync (edacs_collect_bits(), src/protocol/edacs/edacs-fme.c:1966-1970); no handler family.  Thresholds stay
+ * static inside the frame (use_symbol(), dsd_dibit.c:261-275): the bit of a symbol is (symbol > center ? 0 : 1) after pattern 1 (POS)
+ * and (symbol > center ? 1 : 0) after pattern 0 (NEG) (store_two_level_dibit(), dsd_dibit.c:938-948,1024-1029).
+ * Deviations: the ProVoice words the same hunt compares (32 symbols, and the conventional short words) are not hunted - ProVoice voice
+ * is IMBE 7100x4400, which include/ddn_mbe.h refuses; a ProVoice word is a 2^-32 event per position on a control channel.  The dotting
+ * sequences do nothing here (frame_sync_handle_edacs_dotting() acts only while a trunk tune is active, :1411-1419). */
+#define DDN_EDACS_FRAME_SYMBOLS 240
+#define DDN_EDACS_TYPE_POS 38 /* DSD_SYNC_EDACS_POS + 1 (this project's type ids) */
+#define DDN_EDACS_TYPE_NEG 39
 /* D-STAR (-fd): the first two-level protocol.  4800 symbols/s on the 4800_2 hunt profile (level ring 24), no matched filter
  * (use_matched_filter is ignored, as for M17), rf_mod 2 (decode_mode_apply_dstar()) or 0, inverted refused.  The four 24-symbol words
  * are compared exactly (frame_sync_try_dstar(), src/dsp/dsd_frame_sync.c:1452-1503) with a 24-symbol outer-only warm start.
@@ -291,6 +308,30 @@ int ddn_dstar_voice_decode_batch(const uint8_t* d_records10, size_t stride_symbo
                                  const uint8_t* d_sync_pat, const int32_t* d_n_sync, const float* d_sync_thr5, int n_channels,
                                  size_t max_syncs, uint8_t* d_ambe_fr, uint8_t* d_sd_bytes, uint8_t* d_sd_kind, uint8_t* d_sd_hdr41,
                                  uint8_t* d_sd_crc_ok, uint8_t* d_sd_text, uint8_t* d_valid, void* hip_stream);
+
+/* ---- EDACS control-channel frames behind the loop's syncs (DDN_FSK4_EDACS; ddn_edacs.hip) ------------------------------------------
+ * Inputs are the loop's outputs: d_records10 [B][stride_symbols][10], d_counts, d_sync_pos / d_sync_pat [B][max_syncs], d_n_sync and the
+ * thresholds each sync left (d_sync_thr5, ddn_fsk4_rx_set_sync_thresholds).  One lane per slot s = c * max_syncs + k.  == edacs()
+ * (src/protocol/edacs/edacs-fme.c:2012-2066) for every sync whose 240 symbols lie inside the records:
+ *   the two-level bit of each symbol against the sync's center (pattern 1 = POS: symbol > center -> 0; pattern 0 = NEG: -> 1), six 40-bit
+ *   words MSB first (edacs_build_raw_frames(), :1973-1990) -> d_raw40 [S][6]; the bitwise majority of words 0, ~1, 2 and of 3, ~4, 5
+ *   (edacs_vote_frames(), :157-175) -> d_vote40 [S][2]; each voted word's 28-bit message (bits 39..12) re-encoded with the BCH(40,28)
+ *   code, generator x^12 + x^10 + x^8 + x^5 + x^4 + x^3 + 1 (0x1539: edacs_bch(), edacs-bch3.c), compared with the voted word ->
+ *   d_bch_ok [S][2], d_frame_ok [S] (both equal; otherwise the reference prints "BCH FAIL"); the two messages with esk_mask << 20 XORed
+ *   in (edacs_process_valid_frame(), :1993-2010) -> d_msg28 [S][2] (also on a failed frame, where the reference stops before the XOR);
+ *   d_kind [S]: 0 none (frame not good), 1 a standard-mode message (ea_mode 0), 2 an EA message (ea_mode 1), + 2 when it is a site ID:
+ *   d_types [S][3] = {MT-A msg_1[27:25], MT-B [24:22], MT-D [21:17]} (:1915-1940) or {MT1 [27:23], MT2 [22:19], 0} (:1265-1284);
+ *   the standard site ID (MT-A = 7, MT-B = 7, MT-D 0x08..0x0B): d_site6 [S][6] = {site_id msg_1 & 0x1F, priority (>> 9) & 7, cc_lcn
+ *   (>> 12) & 0x1F, SCAT bit 7, failsoft bit 6, auxiliary bit 5} (:1748-1781) - the reference prints "Site ID [%02X][%03d]" of site_id;
+ *   the EA site ID (MT1 = 0x1F, MT2 = 0xA): d_site6 = {((msg_1 & 0x7000) >> 7) | (msg_1 & 0x1F), area (msg_1 & 0xFE0) >> 5, 0, 0, 0, 0}
+ *   (:944-955).  d_valid [S] = 1 when the 240 symbols were inside the records; a slot that is not valid is written as zeros.
+ * ea_mode 0 / 1, esk_mask 0 or 0xA0: -fh = (0, 0), -fH = (0, 0xA0), -fe = (1, 0), -fE = (1, 0xA0).  Everything else edacs() does - the
+ * trunking layer (grants, LCN frequencies, tuning, AFS labels), analog voice and ProVoice - stays out. */
+int ddn_edacs_frame_decode_batch(const uint8_t* d_records10, size_t stride_symbols, const int32_t* d_counts, const int32_t* d_sync_pos,
+                                 const uint8_t* d_sync_pat, const int32_t* d_n_sync, const float* d_sync_thr5, int n_channels,
+                                 size_t max_syncs, int ea_mode, int esk_mask, uint64_t* d_raw40, uint64_t* d_vote40, uint8_t* d_bch_ok,
+                                 uint8_t* d_frame_ok, uint32_t* d_msg28, uint8_t* d_kind, uint8_t* d_types, int32_t* d_site6,
+                                 uint8_t* d_valid, void* hip_stream);
 
 /* CRC of decoded NXDN fields, rows = ddn_fec_nxdn_conv_batch output: kind 0 = SACCH (26 bits + CRC6, nxdn_deperm.c:1246-1261),
  * kind 1 = FACCH1 (80 bits + CRC12, nxdn_dcr_utils.c:21-42); kind + 2 = the same on rows of one bit per byte (what
