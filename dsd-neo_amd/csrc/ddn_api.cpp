@@ -45,7 +45,8 @@ taps_have_zero(const float* taps, int n) {
     return 0;
 }
 
-#define HIP_TRY(expr)                                                                                                  \
+// HIP_TRY for the front end, whose create is the first call to touch the runtime: an insufficient driver is DDN_ENODEV as well
+#define HIP_DRV_TRY(expr)                                                                                              \
     do {                                                                                                               \
         hipError_t e_ = (expr);                                                                                        \
         if (e_ != hipSuccess) {                                                                                        \
@@ -230,16 +231,16 @@ ddn_batch_reset(ddn_batch* b, void* hip_stream) {
         return DDN_EINVAL;
     }
     for (int i = 0; i < b->passes; i++) {
-        HIP_TRY(hipMemsetAsync(b->d_hbhist[i], 0, sizeof(ddn_f2) * (size_t)b->cfg.n_channels * 30,
-                               (hipStream_t)hip_stream));
+        HIP_DRV_TRY(hipMemsetAsync(b->d_hbhist[i], 0, sizeof(ddn_f2) * (size_t)b->cfg.n_channels * 30,
+                                   (hipStream_t)hip_stream));
     }
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t B = (size_t)b->cfg.n_channels;
-    HIP_TRY(ddn_dev_zero(b->d_carry, sizeof(ddn_f2) * B * DDN_CARRY_LEN, st));
-    HIP_TRY(ddn_dev_zero(b->d_state, sizeof(DdnFskState) * B, st));
+    HIP_DRV_TRY(ddn_dev_zero(b->d_carry, sizeof(ddn_f2) * B * DDN_CARRY_LEN, st));
+    HIP_DRV_TRY(ddn_dev_zero(b->d_state, sizeof(DdnFskState) * B, st));
     if (b->d_iqstate) {
-        HIP_TRY(hipMemsetAsync(b->d_iqstate, 0, sizeof(DdnIqCondState) * B, st));
-        HIP_TRY(hipMemsetAsync(b->d_lpf_hist, 0, sizeof(ddn_f2) * B * (size_t)(b->taps_len - 1), st));
+        HIP_DRV_TRY(hipMemsetAsync(b->d_iqstate, 0, sizeof(DdnIqCondState) * B, st));
+        HIP_DRV_TRY(hipMemsetAsync(b->d_lpf_hist, 0, sizeof(ddn_f2) * B * (size_t)(b->taps_len - 1), st));
     }
     return DDN_OK;
 }
@@ -332,9 +333,9 @@ ddn_batch_set_segments(ddn_batch* b, int n_seg, const int32_t* seg_channels, con
             return DDN_ERANGE;
         }
         if (!b->d_taps_s[k - 1]) {
-            HIP_TRY(hipMalloc(&b->d_taps_s[k - 1], sizeof(float) * (DDN_MAX_TAPS + 1)));
+            HIP_DRV_TRY(hipMalloc(&b->d_taps_s[k - 1], sizeof(float) * (DDN_MAX_TAPS + 1)));
         }
-        HIP_TRY(hipMemcpy(b->d_taps_s[k - 1], b->taps_s[k - 1], sizeof(float) * (size_t)len, hipMemcpyHostToDevice));
+        HIP_DRV_TRY(hipMemcpy(b->d_taps_s[k - 1], b->taps_s[k - 1], sizeof(float) * (size_t)len, hipMemcpyHostToDevice));
     }
     b->n_seg = n_seg;
     b->seg_first[0] = 0;
@@ -400,12 +401,12 @@ ddn_front_end_run_segments(ddn_batch* b, const void* const* d_iq, size_t n, floa
         has_zero = has_zero || taps_have_zero(b->taps_s[k - 1], b->taps_len);
     }
     if (b->timing) {
-        HIP_TRY(hipEventRecord(b->ev[0], st));
+        HIP_DRV_TRY(hipEventRecord(b->ev[0], st));
     }
-    HIP_TRY(ddn_dev_launch_fused_ex(&fa, has_zero, b->group ? b->group : 16, st));
+    HIP_DRV_TRY(ddn_dev_launch_fused_ex(&fa, has_zero, b->group ? b->group : 16, st));
     if (b->timing) {
-        HIP_TRY(hipEventRecord(b->ev[1], st));
-        HIP_TRY(hipEventRecord(b->ev[2], st));
+        HIP_DRV_TRY(hipEventRecord(b->ev[1], st));
+        HIP_DRV_TRY(hipEventRecord(b->ev[2], st));
         b->ev_valid = 1;
     }
     return DDN_OK;
@@ -436,15 +437,15 @@ ddn_front_end_run(ddn_batch* b, const void* d_iq, size_t n, float* d_disc, void*
             const int w = i & 1;
             const size_t need = sizeof(ddn_f2) * (size_t)B * n_o;
             if (b->dec_cap[w] < need) {
-                HIP_TRY(hipStreamSynchronize(st));
+                HIP_DRV_TRY(hipStreamSynchronize(st));
                 (void)hipFree(b->d_dec[w]);
                 b->d_dec[w] = nullptr;
                 b->dec_cap[w] = 0;
-                HIP_TRY(hipMalloc(&b->d_dec[w], need));
+                HIP_DRV_TRY(hipMalloc(&b->d_dec[w], need));
                 b->dec_cap[w] = need;
             }
-            HIP_TRY(ddn_dev_hb_decim2(d_iq, in_fmt, (long)n_in, n_in, block_len, B, i == 0 ? 31 : 15, b->d_hbhist[i],
-                                      b->d_dec[w], n_o, st));
+            HIP_DRV_TRY(ddn_dev_hb_decim2(d_iq, in_fmt, (long)n_in, n_in, block_len, B, i == 0 ? 31 : 15, b->d_hbhist[i],
+                                          b->d_dec[w], n_o, st));
             d_iq = b->d_dec[w];
             in_fmt = DDN_IN_CF32;
             block_len >>= 1;
@@ -456,27 +457,27 @@ ddn_front_end_run(ddn_batch* b, const void* d_iq, size_t n, float* d_disc, void*
         // through HBM once (8 B/sample each way) and the recurrences run one lane per channel (ddn_iqcond.hip)
         const size_t need = sizeof(ddn_f2) * (size_t)B * n;
         if (b->lpf_cap < need) {
-            HIP_TRY(hipStreamSynchronize(st));
+            HIP_DRV_TRY(hipStreamSynchronize(st));
             (void)hipFree(b->d_lpf);
             b->d_lpf = nullptr;
             b->lpf_cap = 0;
-            HIP_TRY(hipMalloc(&b->d_lpf, need));
+            HIP_DRV_TRY(hipMalloc(&b->d_lpf, need));
             b->lpf_cap = need;
         }
         DdnIqCondConfig c = b->iqc;
         c.squelch_on = b->cfg.squelch_level > 0.0f ? 1 : 0;
         c.squelch_level = b->cfg.squelch_level;
         if (b->timing) {
-            HIP_TRY(hipEventRecord(b->ev[0], st));
+            HIP_DRV_TRY(hipEventRecord(b->ev[0], st));
         }
-        HIP_TRY(ddn_dev_channel_lpf_c2c(d_iq, in_fmt, (long)n, n, block_len, B, b->d_taps, b->taps_len, taps_have_zero(b->taps, b->taps_len), b->d_lpf_hist,
-                                        b->d_lpf, n, st));
+        HIP_DRV_TRY(ddn_dev_channel_lpf_c2c(d_iq, in_fmt, (long)n, n, block_len, B, b->d_taps, b->taps_len, taps_have_zero(b->taps, b->taps_len), b->d_lpf_hist,
+                                            b->d_lpf, n, st));
         if (b->timing) {
-            HIP_TRY(hipEventRecord(b->ev[1], st));
+            HIP_DRV_TRY(hipEventRecord(b->ev[1], st));
         }
-        HIP_TRY(ddn_dev_iq_cond_disc(b->d_lpf, (long)n, n, block_len, B, &c, b->d_state, b->d_iqstate, d_disc, n, st));
+        HIP_DRV_TRY(ddn_dev_iq_cond_disc(b->d_lpf, (long)n, n, block_len, B, &c, b->d_state, b->d_iqstate, d_disc, n, st));
         if (b->timing) {
-            HIP_TRY(hipEventRecord(b->ev[2], st));
+            HIP_DRV_TRY(hipEventRecord(b->ev[2], st));
             b->ev_valid = 1;
         }
         return DDN_OK;
@@ -522,17 +523,17 @@ ddn_front_end_run(ddn_batch* b, const void* d_iq, size_t n, float* d_disc, void*
     }
 
     if (b->timing) {
-        HIP_TRY(hipEventRecord(b->ev[0], st));
+        HIP_DRV_TRY(hipEventRecord(b->ev[0], st));
     }
-    HIP_TRY(ddn_dev_launch_fused(&fa, b->taps, b->group, st));
+    HIP_DRV_TRY(ddn_dev_launch_fused(&fa, b->taps, b->group, st));
     if (b->timing) {
-        HIP_TRY(hipEventRecord(b->ev[1], st));
+        HIP_DRV_TRY(hipEventRecord(b->ev[1], st));
     }
     if (!fa.carry_out) {
-        HIP_TRY(ddn_dev_launch_carry(d_iq, in_fmt, n, (long)n, b->d_carry, B, st));
+        HIP_DRV_TRY(ddn_dev_launch_carry(d_iq, in_fmt, n, (long)n, b->d_carry, B, st));
     }
     if (b->timing) {
-        HIP_TRY(hipEventRecord(b->ev[2], st));
+        HIP_DRV_TRY(hipEventRecord(b->ev[2], st));
         b->ev_valid = 1;
     }
     if (fa.dbg_out && DDN_EXP_ENV("DDN_DBG_PRINT")) {
@@ -567,12 +568,12 @@ ddn_front_end_run_host(ddn_batch* b, const void* h_iq, size_t n, float* h_disc) 
     if (rc != DDN_OK) {
         return rc;
     }
-    HIP_TRY(hipMemcpy(b->d_in, h_iq, in_bytes, hipMemcpyHostToDevice));
+    HIP_DRV_TRY(hipMemcpy(b->d_in, h_iq, in_bytes, hipMemcpyHostToDevice));
     rc = ddn_front_end_run(b, b->d_in, n, b->d_out, nullptr);
     if (rc != DDN_OK) {
         return rc;
     }
-    HIP_TRY(hipMemcpy(h_disc, b->d_out, out_bytes, hipMemcpyDeviceToHost));
+    HIP_DRV_TRY(hipMemcpy(h_disc, b->d_out, out_bytes, hipMemcpyDeviceToHost));
     return DDN_OK;
 }
 
@@ -582,8 +583,8 @@ ddn_batch_get_fsk_state(ddn_batch* b, int channel, float out5[5]) {
         return DDN_EINVAL;
     }
     DdnFskState s;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(&s, b->d_state + channel, sizeof(s), hipMemcpyDeviceToHost));
+    HIP_DRV_TRY(hipDeviceSynchronize());
+    HIP_DRV_TRY(hipMemcpy(&s, b->d_state + channel, sizeof(s), hipMemcpyDeviceToHost));
     out5[0] = s.prev_i;
     out5[1] = s.prev_q;
     out5[2] = (float)s.have_prev;
@@ -607,9 +608,9 @@ ddn_batch_get_timing(ddn_batch* b, float out3[3]) {
     if (!b || !out3 || !b->ev_valid) {
         return DDN_EINVAL;
     }
-    HIP_TRY(hipEventSynchronize(b->ev[2]));
-    HIP_TRY(hipEventElapsedTime(&out3[0], b->ev[0], b->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&out3[1], b->ev[1], b->ev[2]));
-    HIP_TRY(hipEventElapsedTime(&out3[2], b->ev[0], b->ev[2]));
+    HIP_DRV_TRY(hipEventSynchronize(b->ev[2]));
+    HIP_DRV_TRY(hipEventElapsedTime(&out3[0], b->ev[0], b->ev[1]));
+    HIP_DRV_TRY(hipEventElapsedTime(&out3[1], b->ev[1], b->ev[2]));
+    HIP_DRV_TRY(hipEventElapsedTime(&out3[2], b->ev[0], b->ev[2]));
     return DDN_OK;
 }

@@ -1,18 +1,8 @@
 // ddn_api_audio.cpp - C-ABI of the voice-frame auto gain (include/ddn_hip.h, kernel ddn_audio.hip)
 #include <hip/hip_runtime.h>
 
+#include "ddn_api_util.h"
 #include "ddn_device.h"
-
-#define HIP_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) {                                                                                        \
-            ddn_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);                  \
-            return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice || e_ == hipErrorNoBinaryForGpu)             \
-                       ? DDN_ENODEV                                                                                    \
-                       : (e_ == hipErrorOutOfMemory ? DDN_ENOMEM : DDN_EHIP);                                          \
-        }                                                                                                              \
-    } while (0)
 
 static float
 effective_gain(float audio_gain, int algid_0x21) { // agf_effective_gain(), src/core/audio/gain.c:47-58

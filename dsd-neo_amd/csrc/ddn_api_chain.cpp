@@ -16,29 +16,12 @@
 #include <new>
 #include <thread>
 
+#include "ddn_api_util.h"
 #include "ddn_chain.h"
 #include "ddn_device.h"
 #include "ddn_hip.h"
 #include "ddn_internal.h"
 #include "ddn_mbe.h"
-
-#define HIP_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) {                                                                                        \
-            ddn_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);                  \
-            return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice || e_ == hipErrorNoBinaryForGpu)             \
-                       ? DDN_ENODEV                                                                                    \
-                       : (e_ == hipErrorOutOfMemory ? DDN_ENOMEM : DDN_EHIP);                                          \
-        }                                                                                                              \
-    } while (0)
-#define DDN_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        const int rc_ = (expr);                                                                                        \
-        if (rc_ != DDN_OK) {                                                                                           \
-            return rc_;                                                                                                \
-        }                                                                                                              \
-    } while (0)
 
 // Buffer sets: the receive loop of call k + 1 writes one set while call k is decoded out of another, and - _run_host - the results
 // of call k - 1 may still be leaving a third (the engine copies complete by HSA signal, which a HIP stream cannot wait for: with
@@ -62,6 +45,7 @@ struct ddn_p25_chain {
     int32_t* d_sym_cnt = nullptr;
     ddn_p25p1_framer* fr;
     ddn_mbe_batch* mbe;
+    DdnPool pool; // owns every device buffer of the chain but the long data units' (lp_pool), those made on first use included
     float* d_disc;
     float* d_disc2; // mixed chain only (ddn_p25_chain_double_disc): odd steps' discriminator output, so that the front end of call
                     // k + 1 (issued through _stage on a stream of its own) may run beside the loop of call k
@@ -155,27 +139,14 @@ struct ddn_p25_chain {
     hipEvent_t ev_t[6];
     // long data units (ddn_p25_chain_set_long_data_units; lp.MB == 0: off, nothing is issued for them)
     DdnLongPdu lp;
+    DdnPool lp_pool; // its buffers: released when the switch is cleared, filled again when it is set
     int after_flush; // the last call was ddn_p25_chain_flush (the switch may be set)
 };
-
-template <typename T>
-static bool
-dalloc(T** p, size_t count) {
-    if (hipMalloc((void**)p, count * sizeof(T) + 16) != hipSuccess) {
-        return false;
-    }
-    return hipMemset(*p, 0, count * sizeof(T)) == hipSuccess;
-}
 
 static void
 lpdu_free(ddn_p25_chain* c) {
     DdnLongPdu& l = c->lp;
-    void* all[] = {l.open, l.open_buf, l.sync, l.next, l.end, l.base, l.open_rec, l.open_hdr, l.blocks, l.valid, l.blocks18, l.crc9,
-                   l.n, l.out_rec, l.out_hdr, l.out_info, l.fin, l.nw, l.wk_row, l.wk_dst, l.wk_want, l.wk_want34, l.wk_llr, l.wk_cand,
-                   l.wk_cnt, l.wk_metric, l.wk_b12, l.wk_b18, l.wk_c9};
-    for (void* p : all) {
-        (void)hipFree(p);
-    }
+    c->lp_pool.release();
     memset(&l, 0, sizeof(l));
 }
 
@@ -216,29 +187,9 @@ ddn_p25_chain_destroy(ddn_p25_chain* c) {
     ddn_p25_rx_destroy(c->rx);
     ddn_cqpsk_batch_destroy(c->cq_fe);
     ddn_cq_rx_destroy(c->cq);
-    (void)hipFree(c->d_sym_cnt);
     ddn_p25p1_framer_destroy(c->fr);
     ddn_mbe_batch_destroy(c->mbe);
-    void* all[] = {c->d_disc, c->d_disc2, c->d_pcm_bcnt,
-                   c->d_pcm_boff, c->d_cnt_scan, c->d_cls, c->d_lists, c->d_list_n, c->d_tsbk_crc, c->d_words[0],
-                   c->d_words[1], c->d_wrel, c->d_werrs, c->d_vldu, c->d_rs_d[0], c->d_rs_d[1], c->d_rs_p[0], c->d_rs_p[1],
-                   c->d_rs_st[0], c->d_rs_st[1], c->d_lsd, c->d_lsd_ok, c->d_lsd_llr, c->d_hdu_hex, c->d_hdu_par, c->d_hdu_st,
-                   c->d_hdu_d, c->d_hdu_p, c->d_hdu_rs, c->d_td_d, c->d_td_p, c->d_td_st, c->d_td_rd, c->d_td_rp, c->d_td_rs,
-                   c->d_first, c->d_sc, c->d_nldu, c->d_sc_out, c->d_imbe_res, c->d_res_out, c->d_imbe_fr, c->d_imbe_soft,
-                   c->d_imbe_fl, c->d_imbe_d, c->d_iq[0], c->d_iq[1], c->d_pdu_slot, c->d_pdu_info, c->d_n_pdu,
-                   c->d_pdu_metric, c->d_pdu_hdr, c->d_pdu_valid, c->d_pdu_blocks, c->d_pdu_llr, c->d_pdu_wanted, c->d_pdu_cand,
-                   c->d_pdu_blocks18, c->d_pdu_crc9, c->d_pdu_cnt, c->d_pdu_hllr};
-    for (void* p : all) {
-        (void)hipFree(p);
-    }
-    for (int k = 0; k < NSET; k++) {
-        void* per_set[] = {c->d_rec[k], c->d_rec2[k], c->d_pcm_dense[k], c->d_pcm_slot[k], c->d_pcm_total[k], c->d_fl[k], c->d_new[k], c->d_ev[k],
-                           c->d_nev[k], c->d_evd[k], c->d_evl[k], c->d_evdl[k], c->d_nevl[k], c->d_cnt_full[k], c->d_nid[k], c->d_tsbk[k],
-                           c->d_pcm[k]};
-        for (void* p : per_set) {
-            (void)hipFree(p);
-        }
-    }
+    c->pool.release();
     if (c->s_main) {
         (void)hipStreamDestroy(c->s_main);
     }
@@ -272,8 +223,8 @@ ddn_p25_chain_destroy(ddn_p25_chain* c) {
     hipEvent_t evs[] = {c->ev_in[0], c->ev_in[1], c->ev_in_free[0], c->ev_in_free[1], c->ev_join_a, c->ev_t[0], c->ev_t[1], c->ev_t[2],
                         c->ev_t[3], c->ev_t[4], c->ev_t[5]};
     for (int k = 0; k < NSET; k++) {
-        hipEvent_t per_set[] = {c->ev_produced[k], c->ev_consumed[k], c->ev_out[k], c->ev_loop[k], c->ev_pre[k], c->ev_aux_done[k]};
-        for (hipEvent_t e : per_set) {
+        hipEvent_t set_evs[] = {c->ev_produced[k], c->ev_consumed[k], c->ev_out[k], c->ev_loop[k], c->ev_pre[k], c->ev_aux_done[k]};
+        for (hipEvent_t e : set_evs) {
             if (e) {
                 (void)hipEventDestroy(e);
             }
@@ -358,32 +309,33 @@ ddn_p25_chain_create(const ddn_p25_chain_config* cfg, ddn_p25_chain** out) {
         c->S = (size_t)c->B * (size_t)c->F;
         c->V = (size_t)c->B * (size_t)c->Fv * 9;
         const size_t B = (size_t)c->B, S = c->S, V = c->V;
-        bool ok = dalloc(&c->d_disc, B * (size_t)c->n) && dalloc(&c->d_sym_cnt, B);
+        DdnPool& m = c->pool;
+        bool ok = m.alloc(&c->d_disc, B * (size_t)c->n) && m.alloc(&c->d_sym_cnt, B);
         for (int k = 0; k < NSET && ok; k++) {
-            ok = dalloc(&c->d_rec[k], B * c->stride * 10) && dalloc(&c->d_fl[k], B * c->stride) && dalloc(&c->d_new[k], B)
-                 && dalloc(&c->d_ev[k], B * (size_t)c->E * 4) && dalloc(&c->d_nev[k], B) && dalloc(&c->d_evd[k], B * (size_t)c->E * 4)
-                 && dalloc(&c->d_evl[k], B * (size_t)c->EL * 4) && dalloc(&c->d_evdl[k], B * (size_t)c->EL * 4) && dalloc(&c->d_nevl[k], B)
-                 && dalloc(&c->d_cnt_full[k], B) && dalloc(&c->d_nid[k], S * 4) && dalloc(&c->d_tsbk[k], 3 * S * 12) && dalloc(&c->d_pcm[k], V * 160);
+            ok = m.alloc(&c->d_rec[k], B * c->stride * 10) && m.alloc(&c->d_fl[k], B * c->stride) && m.alloc(&c->d_new[k], B)
+                 && m.alloc(&c->d_ev[k], B * (size_t)c->E * 4) && m.alloc(&c->d_nev[k], B) && m.alloc(&c->d_evd[k], B * (size_t)c->E * 4)
+                 && m.alloc(&c->d_evl[k], B * (size_t)c->EL * 4) && m.alloc(&c->d_evdl[k], B * (size_t)c->EL * 4) && m.alloc(&c->d_nevl[k], B)
+                 && m.alloc(&c->d_cnt_full[k], B) && m.alloc(&c->d_nid[k], S * 4) && m.alloc(&c->d_tsbk[k], 3 * S * 12) && m.alloc(&c->d_pcm[k], V * 160);
         }
-        ok = ok && dalloc(&c->d_cnt_scan, B) && dalloc(&c->d_cls, S) && dalloc(&c->d_lists, S * DDN_LIST_COUNT) && dalloc(&c->d_list_n, 8)
-             && dalloc(&c->d_tsbk_crc, 3 * S) && dalloc(&c->d_words[0], S * 240)
-             && dalloc(&c->d_words[1], S * 240) && dalloc(&c->d_wrel, S * 240) && dalloc(&c->d_werrs, S * 24) && dalloc(&c->d_vldu, S)
-             && dalloc(&c->d_rs_d[0], S * 72) && dalloc(&c->d_rs_d[1], S * 96) && dalloc(&c->d_rs_p[0], S * 72)
-             && dalloc(&c->d_rs_p[1], S * 48) && dalloc(&c->d_rs_st[0], S) && dalloc(&c->d_rs_st[1], S) && dalloc(&c->d_lsd, S * 32)
-             && dalloc(&c->d_lsd_ok, S * 2) && dalloc(&c->d_lsd_llr, S * 32) && dalloc(&c->d_hdu_hex, S * 216)
-             && dalloc(&c->d_hdu_par, S * 432) && dalloc(&c->d_hdu_st, S * 36) && dalloc(&c->d_hdu_d, S * 120)
-             && dalloc(&c->d_hdu_p, S * 96) && dalloc(&c->d_hdu_rs, S) && dalloc(&c->d_td_d, S * 144) && dalloc(&c->d_td_p, S * 144)
-             && dalloc(&c->d_td_st, S * 12) && dalloc(&c->d_td_rd, S * 72) && dalloc(&c->d_td_rp, S * 72) && dalloc(&c->d_td_rs, S)
-             && dalloc(&c->d_first, V) && dalloc(&c->d_sc, V) && dalloc(&c->d_nldu, B) && dalloc(&c->d_sc_out, V)
-             && dalloc(&c->d_imbe_res, V * 5) && dalloc(&c->d_res_out, V * 5) && dalloc(&c->d_imbe_fr, V * 184)
-             && dalloc(&c->d_imbe_soft, V * 368) && dalloc(&c->d_imbe_fl, V) && dalloc(&c->d_imbe_d, V * 88)
-             && dalloc(&c->d_pdu_slot, B * (size_t)c->PF) && dalloc(&c->d_pdu_info, B * (size_t)c->PF * 4)
-             && dalloc(&c->d_n_pdu, B) && dalloc(&c->d_pdu_hdr, B * (size_t)c->PF * 12)
-             && dalloc(&c->d_pdu_valid, B * (size_t)c->PF * (size_t)c->PB) && dalloc(&c->d_pdu_blocks, B * (size_t)c->PF * (size_t)c->PB * 12)
-             && dalloc(&c->d_pdu_metric, B * (size_t)c->PF * (size_t)c->PB) && dalloc(&c->d_pdu_llr, B * (size_t)c->PF * (size_t)c->PB * 196)
-             && dalloc(&c->d_pdu_wanted, B * (size_t)c->PF * (size_t)c->PB) && dalloc(&c->d_pdu_cand, B * (size_t)c->PF * (size_t)c->PB * 8 * 24)
-             && dalloc(&c->d_pdu_blocks18, B * (size_t)c->PF * (size_t)c->PB * 18) && dalloc(&c->d_pdu_crc9, B * (size_t)c->PF * (size_t)c->PB)
-             && dalloc(&c->d_pdu_cnt, B * (size_t)c->PF * (size_t)c->PB) && dalloc(&c->d_pdu_hllr, B * (size_t)c->PF * 196);
+        ok = ok && m.alloc(&c->d_cnt_scan, B) && m.alloc(&c->d_cls, S) && m.alloc(&c->d_lists, S * DDN_LIST_COUNT) && m.alloc(&c->d_list_n, 8)
+             && m.alloc(&c->d_tsbk_crc, 3 * S) && m.alloc(&c->d_words[0], S * 240)
+             && m.alloc(&c->d_words[1], S * 240) && m.alloc(&c->d_wrel, S * 240) && m.alloc(&c->d_werrs, S * 24) && m.alloc(&c->d_vldu, S)
+             && m.alloc(&c->d_rs_d[0], S * 72) && m.alloc(&c->d_rs_d[1], S * 96) && m.alloc(&c->d_rs_p[0], S * 72)
+             && m.alloc(&c->d_rs_p[1], S * 48) && m.alloc(&c->d_rs_st[0], S) && m.alloc(&c->d_rs_st[1], S) && m.alloc(&c->d_lsd, S * 32)
+             && m.alloc(&c->d_lsd_ok, S * 2) && m.alloc(&c->d_lsd_llr, S * 32) && m.alloc(&c->d_hdu_hex, S * 216)
+             && m.alloc(&c->d_hdu_par, S * 432) && m.alloc(&c->d_hdu_st, S * 36) && m.alloc(&c->d_hdu_d, S * 120)
+             && m.alloc(&c->d_hdu_p, S * 96) && m.alloc(&c->d_hdu_rs, S) && m.alloc(&c->d_td_d, S * 144) && m.alloc(&c->d_td_p, S * 144)
+             && m.alloc(&c->d_td_st, S * 12) && m.alloc(&c->d_td_rd, S * 72) && m.alloc(&c->d_td_rp, S * 72) && m.alloc(&c->d_td_rs, S)
+             && m.alloc(&c->d_first, V) && m.alloc(&c->d_sc, V) && m.alloc(&c->d_nldu, B) && m.alloc(&c->d_sc_out, V)
+             && m.alloc(&c->d_imbe_res, V * 5) && m.alloc(&c->d_res_out, V * 5) && m.alloc(&c->d_imbe_fr, V * 184)
+             && m.alloc(&c->d_imbe_soft, V * 368) && m.alloc(&c->d_imbe_fl, V) && m.alloc(&c->d_imbe_d, V * 88)
+             && m.alloc(&c->d_pdu_slot, B * (size_t)c->PF) && m.alloc(&c->d_pdu_info, B * (size_t)c->PF * 4)
+             && m.alloc(&c->d_n_pdu, B) && m.alloc(&c->d_pdu_hdr, B * (size_t)c->PF * 12)
+             && m.alloc(&c->d_pdu_valid, B * (size_t)c->PF * (size_t)c->PB) && m.alloc(&c->d_pdu_blocks, B * (size_t)c->PF * (size_t)c->PB * 12)
+             && m.alloc(&c->d_pdu_metric, B * (size_t)c->PF * (size_t)c->PB) && m.alloc(&c->d_pdu_llr, B * (size_t)c->PF * (size_t)c->PB * 196)
+             && m.alloc(&c->d_pdu_wanted, B * (size_t)c->PF * (size_t)c->PB) && m.alloc(&c->d_pdu_cand, B * (size_t)c->PF * (size_t)c->PB * 8 * 24)
+             && m.alloc(&c->d_pdu_blocks18, B * (size_t)c->PF * (size_t)c->PB * 18) && m.alloc(&c->d_pdu_crc9, B * (size_t)c->PF * (size_t)c->PB)
+             && m.alloc(&c->d_pdu_cnt, B * (size_t)c->PF * (size_t)c->PB) && m.alloc(&c->d_pdu_hllr, B * (size_t)c->PF * 196);
         if (!ok) {
             ddn_set_error("ddn_p25_chain_create: device allocation failed");
             rc = DDN_ENOMEM;
@@ -1145,7 +1097,7 @@ ddn_p25_chain_double_disc(ddn_p25_chain* c) {
         return DDN_EINVAL;
     }
     if (!c->d_disc2) {
-        HIP_TRY(hipMalloc((void**)&c->d_disc2, sizeof(float) * (size_t)c->B * (size_t)c->n));
+        HIP_TRY(c->pool.alloc_bytes(&c->d_disc2, sizeof(float) * (size_t)c->B * (size_t)c->n));
     }
     return DDN_OK;
 }
@@ -1188,8 +1140,8 @@ ddn_p25_chain_run_host(ddn_p25_chain* c, const void* h_iq, const ddn_p25_chain_h
     c->after_flush = 0;
     const int cur = (int)(c->step % NSET);
     if (!c->d_iq[0]) {
-        HIP_TRY(hipMalloc(&c->d_iq[0], c->iq_bytes + 16));
-        HIP_TRY(hipMalloc(&c->d_iq[1], c->iq_bytes + 16));
+        HIP_TRY(c->pool.alloc_bytes(&c->d_iq[0], c->iq_bytes + 16));
+        HIP_TRY(c->pool.alloc_bytes(&c->d_iq[1], c->iq_bytes + 16));
     }
     if (out && c->sdma == 0) { // the first call that names result buffers decides the copy route
         const void* any = out->records10 ? (const void*)out->records10
@@ -1241,7 +1193,7 @@ ddn_p25_chain_run_host(ddn_p25_chain* c, const void* h_iq, const ddn_p25_chain_h
     HIP_TRY(hipStreamWaitEvent(c->s_aux, c->ev_produced[cur], 0));
     if (out && out->records2) { // the records' host form (packed inside chain_decode)
         if (!c->d_rec2[cur]) {
-            HIP_TRY(hipMalloc(&c->d_rec2[cur], (size_t)c->B * c->stride * 2));
+            HIP_TRY(c->pool.alloc_bytes(&c->d_rec2[cur], (size_t)c->B * c->stride * 2));
         }
         c->want_rec2 = 1;
     }
@@ -1250,13 +1202,13 @@ ddn_p25_chain_run_host(ddn_p25_chain* c, const void* h_iq, const ddn_p25_chain_h
     if (dense_pcm) { // the synthesized frames only, compacted beside the decode stage
         const size_t V = c->V;
         if (!c->d_pcm_bcnt) {
-            HIP_TRY(hipMalloc(&c->d_pcm_bcnt, ((V + 1023) / 1024) * sizeof(int32_t)));
-            HIP_TRY(hipMalloc(&c->d_pcm_boff, ((V + 1023) / 1024) * sizeof(int32_t)));
+            HIP_TRY(c->pool.alloc_bytes(&c->d_pcm_bcnt, ((V + 1023) / 1024) * sizeof(int32_t)));
+            HIP_TRY(c->pool.alloc_bytes(&c->d_pcm_boff, ((V + 1023) / 1024) * sizeof(int32_t)));
         }
         if (!c->d_pcm_dense[cur]) {
-            HIP_TRY(hipMalloc(&c->d_pcm_dense[cur], V * 160 * sizeof(float)));
-            HIP_TRY(hipMalloc(&c->d_pcm_slot[cur], V * sizeof(int32_t)));
-            HIP_TRY(hipMalloc(&c->d_pcm_total[cur], sizeof(int32_t)));
+            HIP_TRY(c->pool.alloc_bytes(&c->d_pcm_dense[cur], V * 160 * sizeof(float)));
+            HIP_TRY(c->pool.alloc_bytes(&c->d_pcm_slot[cur], V * sizeof(int32_t)));
+            HIP_TRY(c->pool.alloc_bytes(&c->d_pcm_total[cur], sizeof(int32_t)));
         }
         if (c->have_deferred) { // (behind the deferred synthesis, on its stream)
             c->deferred_dense = 1;
@@ -1412,13 +1364,14 @@ ddn_p25_chain_set_long_data_units(ddn_p25_chain* c, int max_blocks, int per_chan
     // the blocks one row can complete (their records are disjoint: 98 payload dibits each)
     const int W = (int)(c->stride / 98) + 2;
     const size_t U = 2 * B + B * (size_t)P, NW = B * (size_t)W;
-    bool ok = dalloc(&l.open, B) && dalloc(&l.open_buf, B) && dalloc(&l.sync, B) && dalloc(&l.next, B) && dalloc(&l.end, B)
-              && dalloc(&l.base, B) && dalloc(&l.open_rec, B) && dalloc(&l.open_hdr, B * 12) && dalloc(&l.blocks, U * MB * 12)
-              && dalloc(&l.valid, U * MB) && dalloc(&l.blocks18, U * MB * 18) && dalloc(&l.crc9, U * MB) && dalloc(&l.n, B)
-              && dalloc(&l.out_rec, B * P) && dalloc(&l.out_hdr, B * P * 12) && dalloc(&l.out_info, B * P * 4) && dalloc(&l.fin, B * P)
-              && dalloc(&l.nw, B) && dalloc(&l.wk_row, NW) && dalloc(&l.wk_dst, NW) && dalloc(&l.wk_want, NW) && dalloc(&l.wk_want34, NW)
-              && dalloc(&l.wk_llr, NW * 196) && dalloc(&l.wk_cand, NW * 8 * 24) && dalloc(&l.wk_cnt, NW) && dalloc(&l.wk_metric, NW)
-              && dalloc(&l.wk_b12, NW * 12) && dalloc(&l.wk_b18, NW * 18) && dalloc(&l.wk_c9, NW);
+    DdnPool& m = c->lp_pool;
+    bool ok = m.alloc(&l.open, B) && m.alloc(&l.open_buf, B) && m.alloc(&l.sync, B) && m.alloc(&l.next, B) && m.alloc(&l.end, B)
+              && m.alloc(&l.base, B) && m.alloc(&l.open_rec, B) && m.alloc(&l.open_hdr, B * 12) && m.alloc(&l.blocks, U * MB * 12)
+              && m.alloc(&l.valid, U * MB) && m.alloc(&l.blocks18, U * MB * 18) && m.alloc(&l.crc9, U * MB) && m.alloc(&l.n, B)
+              && m.alloc(&l.out_rec, B * P) && m.alloc(&l.out_hdr, B * P * 12) && m.alloc(&l.out_info, B * P * 4) && m.alloc(&l.fin, B * P)
+              && m.alloc(&l.nw, B) && m.alloc(&l.wk_row, NW) && m.alloc(&l.wk_dst, NW) && m.alloc(&l.wk_want, NW) && m.alloc(&l.wk_want34, NW)
+              && m.alloc(&l.wk_llr, NW * 196) && m.alloc(&l.wk_cand, NW * 8 * 24) && m.alloc(&l.wk_cnt, NW) && m.alloc(&l.wk_metric, NW)
+              && m.alloc(&l.wk_b12, NW * 12) && m.alloc(&l.wk_b18, NW * 18) && m.alloc(&l.wk_c9, NW);
     if (!ok) {
         lpdu_free(c);
         ddn_set_error("ddn_p25_chain_set_long_data_units: device allocation failed");

@@ -8,6 +8,7 @@
 #include <new>
 #include <vector>
 
+#include "ddn_api_util.h"
 #include "ddn_device.h"
 
 static int
@@ -19,17 +20,6 @@ taps_have_zero(const float* taps, int n) {
     }
     return 0;
 }
-
-#define HIP_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) {                                                                                        \
-            ddn_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);                  \
-            return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice || e_ == hipErrorNoBinaryForGpu)             \
-                       ? DDN_ENODEV                                                                                    \
-                       : (e_ == hipErrorOutOfMemory ? DDN_ENOMEM : DDN_EHIP);                                          \
-        }                                                                                                              \
-    } while (0)
 
 struct ddn_cqpsk_batch {
     ddn_cqpsk_config cfg;

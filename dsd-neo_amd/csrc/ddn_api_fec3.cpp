@@ -7,19 +7,9 @@
 #include <cstring>
 #include <vector>
 
+#include "ddn_api_util.h"
 #include "ddn_device.h"
 #include "ddn_fec3.h"
-
-#define HIP_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) {                                                                                        \
-            ddn_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);                  \
-            return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice || e_ == hipErrorNoBinaryForGpu)             \
-                       ? DDN_ENODEV                                                                                    \
-                       : (e_ == hipErrorOutOfMemory ? DDN_ENOMEM : DDN_EHIP);                                          \
-        }                                                                                                              \
-    } while (0)
 
 static int
 code_shape(int code, int* n, int* k) {

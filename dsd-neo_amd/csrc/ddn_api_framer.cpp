@@ -6,19 +6,9 @@
 #include <cstring>
 #include <new>
 
+#include "ddn_api_util.h"
 #include "ddn_device.h"
 #include "ddn_internal.h"
-
-#define HIP_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) {                                                                                        \
-            ddn_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);                  \
-            return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice || e_ == hipErrorNoBinaryForGpu)             \
-                       ? DDN_ENODEV                                                                                    \
-                       : (e_ == hipErrorOutOfMemory ? DDN_ENOMEM : DDN_EHIP);                                          \
-        }                                                                                                              \
-    } while (0)
 
 enum { T_NID = 0, T_BLK0, T_BLK1, T_BLK2, T_LDU1, T_LDU2, T_HDU_HEX, T_HDU_PAR, T_TDULC_DATA, T_TDULC_PAR, T_LSD, T_COUNT };
 

@@ -6,27 +6,9 @@
 #include <cstdint>
 #include <cstring>
 
+#include "ddn_api_util.h"
 #include "ddn_device.h"
-
-#define HIP_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) {                                                                                        \
-            ddn_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);                  \
-            return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice || e_ == hipErrorNoBinaryForGpu)             \
-                       ? DDN_ENODEV                                                                                    \
-                       : (e_ == hipErrorOutOfMemory ? DDN_ENOMEM : DDN_EHIP);                                          \
-        }                                                                                                              \
-    } while (0)
-
-extern "C" hipError_t ddn_dev_m17_lsf_cost(const uint8_t* rec, size_t stride, const int32_t* counts, const int32_t* sync_pos,
-                                           const uint8_t* sync_pat, const int32_t* n_sync, const float* sync_thr, int n_channels,
-                                           int max_syncs, int lmax, uint16_t* cost488, int32_t* slot_sync, hipStream_t st);
-extern "C" hipError_t ddn_dev_m17_lsf_finish(const uint8_t* dec, int dec_stride, const uint32_t* cost, const int32_t* slot_sync,
-                                             int n_channels, int lmax, int max_syncs, uint8_t* lsf30, uint8_t* status,
-                                             uint32_t* path_cost, hipStream_t st);
-extern "C" int ddn_fec_viterbi_k5_batch(const uint16_t* d_soft, size_t n, int in_len, const uint8_t* punct, int p_len, uint8_t* d_out,
-                                        int out_stride, uint32_t* d_cost, void* hip_stream);
+#include "ddn_fsk4.h"
 
 extern "C" int
 ddn_m17_lsf_decode_batch(const uint8_t* d_records10, size_t stride_symbols, const int32_t* d_counts, const int32_t* d_sync_pos,
@@ -69,17 +51,6 @@ ddn_m17_lsf_decode_batch(const uint8_t* d_records10, size_t stride_symbols, cons
     HIP_TRY(ef);
     return DDN_OK;
 }
-
-extern "C" hipError_t ddn_dev_m17_str_bits(const uint8_t* rec, size_t stride, const int32_t* counts, const int32_t* sync_pos,
-                                           const uint8_t* sync_pat, const int32_t* n_sync, int n_channels, int max_syncs, int lmax,
-                                           uint8_t* sym296, int32_t* slot_sync, uint8_t* slot_lich6, uint8_t* slot_cnt, uint8_t* slot_ok,
-                                           hipStream_t st);
-extern "C" hipError_t ddn_dev_m17_str_finish(const uint8_t* dec, int dec_stride, const int32_t* slot_sync, const uint8_t* slot_lich6,
-                                             const uint8_t* slot_cnt, const uint8_t* slot_ok, int n_channels, int lmax, int max_syncs,
-                                             uint8_t* lich6, uint8_t* lich_cnt, uint8_t* fn_payload18, uint8_t* status, hipStream_t st);
-extern "C" hipError_t ddn_dev_m17_lich(const uint8_t* sync_pat, const int32_t* n_sync, int n_channels, int max_syncs, const uint8_t* lsf30,
-                                       const uint8_t* lsf_status, const uint8_t* lich6, const uint8_t* lich_cnt, const uint8_t* str_status,
-                                       uint8_t* asm30, uint8_t* lich_lsf30, uint8_t* lich_status, hipStream_t st);
 
 extern "C" int
 ddn_m17_str_decode_batch(const uint8_t* d_records10, size_t stride_symbols, const int32_t* d_counts, const int32_t* d_sync_pos,
@@ -134,13 +105,6 @@ ddn_m17_lich_assemble_batch(const uint8_t* d_sync_pat, const int32_t* d_n_sync, 
     return DDN_OK;
 }
 
-extern "C" hipError_t ddn_dev_ysf_fich_cost(const uint8_t* rec, size_t stride, const int32_t* counts, const int32_t* sync_pos,
-                                            const int32_t* n_sync, int n_channels, int max_syncs, int lmax, uint16_t* cost200,
-                                            int32_t* slot_sync, hipStream_t st);
-extern "C" hipError_t ddn_dev_ysf_fich_finish(const uint8_t* dec, int dec_stride, const uint32_t* cost, const int32_t* slot_sync,
-                                              int n_channels, int lmax, int max_syncs, uint8_t* fich4, uint8_t* status, uint32_t* v_error,
-                                              hipStream_t st);
-
 extern "C" int
 ddn_ysf_fich_decode_batch(const uint8_t* d_records10, size_t stride_symbols, const int32_t* d_counts, const int32_t* d_sync_pos,
                           const int32_t* d_n_sync, int n_channels, size_t max_syncs, uint8_t* d_fich4, uint8_t* d_status, uint32_t* d_v_error,
@@ -182,19 +146,6 @@ ddn_ysf_fich_decode_batch(const uint8_t* d_records10, size_t stride_symbols, con
     HIP_TRY(ef);
     return DDN_OK;
 }
-
-extern "C" hipError_t ddn_dev_ysf_plan(const int32_t* sync_pos, const int32_t* n_sync, const int32_t* counts, int n_channels, int max_syncs,
-                                       int lmax, const uint8_t* fich4, const uint8_t* fich_status, uint8_t* last2, uint8_t* info,
-                                       int32_t* slot_sync, hipStream_t st);
-extern "C" hipError_t ddn_dev_ysf_payload_costs(const uint8_t* rec, size_t stride, const int32_t* sync_pos, int n_channels, int max_syncs,
-                                                int lmax, const uint8_t* info, const int32_t* slot_sync, uint16_t* cost200,
-                                                uint16_t* cost360, uint8_t* ambe49, uint8_t* errs2, uint8_t* want200, uint8_t* want360,
-                                                uint8_t* frames, uint8_t* n_frames, hipStream_t st);
-extern "C" int ddn_fec_viterbi_k5_batch_wanted(const uint16_t* d_soft, size_t n, int in_len, const uint8_t* punct, int p_len, uint8_t* d_out,
-                                               int out_stride, uint32_t* d_cost, const uint8_t* d_wanted, void* hip_stream);
-extern "C" hipError_t ddn_dev_ysf_dch_finish(const uint8_t* decA, const uint32_t* pcA, const uint8_t* decB, const uint32_t* pcB,
-                                             const int32_t* slot_sync, const uint8_t* info, int n_channels, int lmax, int max_syncs,
-                                             uint8_t* dch40, uint8_t* dch_status, uint32_t* dch_cost, hipStream_t st);
 
 // include/ddn_fsk4.h
 extern "C" int

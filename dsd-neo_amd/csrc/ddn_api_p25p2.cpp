@@ -7,26 +7,9 @@
 
 #include <cstdint>
 
+#include "ddn_api_util.h"
 #include "ddn_device.h"
 #include "ddn_p25p2_seq.h"
-
-#define HIP_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) {                                                                                        \
-            ddn_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);                  \
-            return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice || e_ == hipErrorNoBinaryForGpu)             \
-                       ? DDN_ENODEV                                                                                    \
-                       : (e_ == hipErrorOutOfMemory ? DDN_ENOMEM : DDN_EHIP);                                          \
-        }                                                                                                              \
-    } while (0)
-#define DDN_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        const int r_ = (expr);                                                                                         \
-        if (r_ != DDN_OK) {                                                                                            \
-            return r_;                                                                                                 \
-        }                                                                                                              \
-    } while (0)
 
 namespace {
 // stream-ordered scratch: arenas (one hipMallocAsync each, carved by get()), released when the call leaves (also on its error paths)

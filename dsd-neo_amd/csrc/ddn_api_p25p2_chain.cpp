@@ -13,30 +13,13 @@
 #include <cstring>
 #include <new>
 
+#include "ddn_api_util.h"
 #include "ddn_chain.h"
 #include "ddn_device.h"
 #include "ddn_hip.h"
 #include "ddn_internal.h"
 #include "ddn_mbe.h"
 #include "ddn_p25p2_seq.h"
-
-#define HIP_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) {                                                                                        \
-            ddn_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);                  \
-            return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice || e_ == hipErrorNoBinaryForGpu)             \
-                       ? DDN_ENODEV                                                                                    \
-                       : (e_ == hipErrorOutOfMemory ? DDN_ENOMEM : DDN_EHIP);                                          \
-        }                                                                                                              \
-    } while (0)
-#define DDN_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        const int rc_ = (expr);                                                                                        \
-        if (rc_ != DDN_OK) {                                                                                           \
-            return rc_;                                                                                                \
-        }                                                                                                              \
-    } while (0)
 
 struct ddn_p25p2_chain {
     ddn_p25p2_chain_config cfg;
@@ -45,6 +28,7 @@ struct ddn_p25p2_chain {
     ddn_cqpsk_batch* fe;
     ddn_cq_rx* rx;
     ddn_mbe_batch* mbe;
+    DdnPool pool; // owns every device buffer below
     float* d_sym;
     int32_t* d_sym_cnt;
     uint8_t *d_rec[2], *d_fl[2];
@@ -63,15 +47,6 @@ struct ddn_p25p2_chain {
     long step;
 };
 
-template <typename T>
-static bool
-dalloc(T** p, size_t count) {
-    if (hipMalloc((void**)p, count * sizeof(T) + 16) != hipSuccess) {
-        return false;
-    }
-    return hipMemset(*p, 0, count * sizeof(T)) == hipSuccess;
-}
-
 extern "C" void
 ddn_p25p2_chain_destroy(ddn_p25p2_chain* c) {
     if (!c) {
@@ -81,12 +56,7 @@ ddn_p25p2_chain_destroy(ddn_p25p2_chain* c) {
     ddn_cqpsk_batch_destroy(c->fe);
     ddn_cq_rx_destroy(c->rx);
     ddn_mbe_batch_destroy(c->mbe);
-    void* all[] = {c->d_sym, c->d_sym_cnt, c->d_rec[0], c->d_rec[1], c->d_fl[0], c->d_fl[1], c->d_new[0], c->d_new[1], c->d_cnt_scan, c->d_cnt_full,
-                   c->d_sync_pos, c->d_n_sync, c->d_dropped, c->d_bits, c->d_llr, c->d_seed, c->d_state, c->d_info, c->d_payload, c->d_ambe_fr,
-                   c->d_ambe_rel, c->d_ess, c->d_vsrc, c->d_vcount, c->d_vres, c->d_vres_out, c->d_vfr, c->d_vrel, c->d_vskip, c->d_vbits, c->d_pcm};
-    for (void* p : all) {
-        (void)hipFree(p);
-    }
+    c->pool.release();
     delete c;
 }
 
@@ -125,15 +95,16 @@ ddn_p25p2_chain_create(const ddn_p25p2_chain_config* cfg, const uint64_t* seed44
         c->ms = ddn_cqpsk_max_symbols(c->fe, (size_t)c->n);
         c->stride = (size_t)c->T + c->ms;
         const size_t B = (size_t)c->B, R = B * (size_t)c->G * 4, V = 2 * B * (size_t)c->cap;
-        bool ok = dalloc(&c->d_sym, B * c->ms) && dalloc(&c->d_sym_cnt, B) && dalloc(&c->d_cnt_scan, B) && dalloc(&c->d_cnt_full, B)
-                  && dalloc(&c->d_sync_pos, B * (size_t)c->G) && dalloc(&c->d_n_sync, B) && dalloc(&c->d_dropped, B)
-                  && dalloc(&c->d_bits, B * (size_t)c->G * 1400) && dalloc(&c->d_llr, B * (size_t)c->G * 1400) && dalloc(&c->d_seed, B)
-                  && dalloc(&c->d_state, B) && dalloc(&c->d_info, R * 8) && dalloc(&c->d_payload, R * 180) && dalloc(&c->d_ambe_fr, R * 384)
-                  && dalloc(&c->d_ambe_rel, R * 384) && dalloc(&c->d_ess, R * 96) && dalloc(&c->d_vsrc, V) && dalloc(&c->d_vcount, 2 * B)
-                  && dalloc(&c->d_vres, V * 5) && dalloc(&c->d_vres_out, V * 5) && dalloc(&c->d_vfr, V * 96) && dalloc(&c->d_vrel, V * 96)
-                  && dalloc(&c->d_vskip, V) && dalloc(&c->d_vbits, V * 49) && dalloc(&c->d_pcm, V * 160);
+        DdnPool& m = c->pool;
+        bool ok = m.alloc(&c->d_sym, B * c->ms) && m.alloc(&c->d_sym_cnt, B) && m.alloc(&c->d_cnt_scan, B) && m.alloc(&c->d_cnt_full, B)
+                  && m.alloc(&c->d_sync_pos, B * (size_t)c->G) && m.alloc(&c->d_n_sync, B) && m.alloc(&c->d_dropped, B)
+                  && m.alloc(&c->d_bits, B * (size_t)c->G * 1400) && m.alloc(&c->d_llr, B * (size_t)c->G * 1400) && m.alloc(&c->d_seed, B)
+                  && m.alloc(&c->d_state, B) && m.alloc(&c->d_info, R * 8) && m.alloc(&c->d_payload, R * 180) && m.alloc(&c->d_ambe_fr, R * 384)
+                  && m.alloc(&c->d_ambe_rel, R * 384) && m.alloc(&c->d_ess, R * 96) && m.alloc(&c->d_vsrc, V) && m.alloc(&c->d_vcount, 2 * B)
+                  && m.alloc(&c->d_vres, V * 5) && m.alloc(&c->d_vres_out, V * 5) && m.alloc(&c->d_vfr, V * 96) && m.alloc(&c->d_vrel, V * 96)
+                  && m.alloc(&c->d_vskip, V) && m.alloc(&c->d_vbits, V * 49) && m.alloc(&c->d_pcm, V * 160);
         for (int k = 0; k < 2 && ok; k++) {
-            ok = dalloc(&c->d_rec[k], B * c->stride * 10) && dalloc(&c->d_fl[k], B * c->stride) && dalloc(&c->d_new[k], B);
+            ok = m.alloc(&c->d_rec[k], B * c->stride * 10) && m.alloc(&c->d_fl[k], B * c->stride) && m.alloc(&c->d_new[k], B);
         }
         if (!ok) {
             ddn_set_error("ddn_p25p2_chain_create: device allocation failed");

@@ -8,21 +8,11 @@
 #include <new>
 #include <vector>
 
+#include "ddn_api_util.h"
 #include "ddn_device.h"
 #include "ddn_fsk4.h"
 #include "ddn_tables_fsk4.h"
 #include "ddn_tables_dpmr.h"
-
-#define HIP_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) {                                                                                        \
-            ddn_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);                  \
-            return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice || e_ == hipErrorNoBinaryForGpu)             \
-                       ? DDN_ENODEV                                                                                    \
-                       : (e_ == hipErrorOutOfMemory ? DDN_ENOMEM : DDN_EHIP);                                          \
-        }                                                                                                              \
-    } while (0)
 
 namespace {
 // sync words as sign strings ('1' = +3, '3' = -3): ETSI TS 102 361-1 table 9.2 (BS / MS / direct-mode sourced data and voice)

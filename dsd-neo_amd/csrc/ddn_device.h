@@ -478,6 +478,47 @@ hipError_t ddn_dev_fsk4_chain_syncs_thr(const int32_t* c_pos, const uint8_t* c_p
                                         int32_t* d_pos, uint8_t* d_pat, uint8_t* d_pre, uint8_t* d_prel, int32_t* d_n, int myd,
                                         int32_t* o_pos, uint8_t* o_pat, uint8_t* o_pre, uint8_t* o_prel, int32_t* o_n, int32_t* dropped,
                                         int n_channels, const float* c_thr, const float* s_thr, float* d_thr, float* o_thr, hipStream_t st);
+/* ---- ddn_m17.hip / ddn_dpmr.hip: the launchers behind the M17, YSF and dPMR frame decoders (ddn_api_m17.cpp, the fsk4 chain) ---- */
+hipError_t ddn_dev_m17_lsf_cost(const uint8_t* rec, size_t stride, const int32_t* counts, const int32_t* sync_pos,
+                                const uint8_t* sync_pat, const int32_t* n_sync, const float* sync_thr, int n_channels,
+                                int max_syncs, int lmax, uint16_t* cost488, int32_t* slot_sync, hipStream_t st);
+hipError_t ddn_dev_m17_lsf_finish(const uint8_t* dec, int dec_stride, const uint32_t* cost, const int32_t* slot_sync,
+                                  int n_channels, int lmax, int max_syncs, uint8_t* lsf30, uint8_t* status,
+                                  uint32_t* path_cost, hipStream_t st);
+hipError_t ddn_dev_m17_str_bits(const uint8_t* rec, size_t stride, const int32_t* counts, const int32_t* sync_pos,
+                                const uint8_t* sync_pat, const int32_t* n_sync, int n_channels, int max_syncs, int lmax,
+                                uint8_t* sym296, int32_t* slot_sync, uint8_t* slot_lich6, uint8_t* slot_cnt, uint8_t* slot_ok,
+                                hipStream_t st);
+hipError_t ddn_dev_m17_str_finish(const uint8_t* dec, int dec_stride, const int32_t* slot_sync, const uint8_t* slot_lich6,
+                                  const uint8_t* slot_cnt, const uint8_t* slot_ok, int n_channels, int lmax, int max_syncs,
+                                  uint8_t* lich6, uint8_t* lich_cnt, uint8_t* fn_payload18, uint8_t* status, hipStream_t st);
+hipError_t ddn_dev_m17_lich(const uint8_t* sync_pat, const int32_t* n_sync, int n_channels, int max_syncs, const uint8_t* lsf30,
+                            const uint8_t* lsf_status, const uint8_t* lich6, const uint8_t* lich_cnt, const uint8_t* str_status,
+                            uint8_t* asm30, uint8_t* lich_lsf30, uint8_t* lich_status, hipStream_t st);
+hipError_t ddn_dev_ysf_fich_cost(const uint8_t* rec, size_t stride, const int32_t* counts, const int32_t* sync_pos,
+                                 const int32_t* n_sync, int n_channels, int max_syncs, int lmax, uint16_t* cost200,
+                                 int32_t* slot_sync, hipStream_t st);
+hipError_t ddn_dev_ysf_fich_finish(const uint8_t* dec, int dec_stride, const uint32_t* cost, const int32_t* slot_sync,
+                                   int n_channels, int lmax, int max_syncs, uint8_t* fich4, uint8_t* status, uint32_t* v_error,
+                                   hipStream_t st);
+hipError_t ddn_dev_ysf_plan(const int32_t* sync_pos, const int32_t* n_sync, const int32_t* counts, int n_channels, int max_syncs,
+                            int lmax, const uint8_t* fich4, const uint8_t* fich_status, uint8_t* last2, uint8_t* info,
+                            int32_t* slot_sync, hipStream_t st);
+hipError_t ddn_dev_ysf_payload_costs(const uint8_t* rec, size_t stride, const int32_t* sync_pos, int n_channels, int max_syncs,
+                                     int lmax, const uint8_t* info, const int32_t* slot_sync, uint16_t* cost200,
+                                     uint16_t* cost360, uint8_t* ambe49, uint8_t* errs2, uint8_t* want200, uint8_t* want360,
+                                     uint8_t* frames, uint8_t* n_frames, hipStream_t st);
+hipError_t ddn_dev_ysf_dch_finish(const uint8_t* decA, const uint32_t* pcA, const uint8_t* decB, const uint32_t* pcB,
+                                  const int32_t* slot_sync, const uint8_t* info, int n_channels, int lmax, int max_syncs,
+                                  uint8_t* dch40, uint8_t* dch_status, uint32_t* dch_cost, hipStream_t st);
+hipError_t ddn_dev_ysf_voice_file(const int32_t* n_sync, int n_channels, int max_syncs, const uint8_t* info, const uint8_t* ambe49,
+                                  const uint8_t* errs2, const uint8_t* bits_fd, const int32_t* res_fd, const uint8_t* n_frames,
+                                  int mode, int vf, uint8_t* bits, int32_t* res, uint8_t* skip, int32_t* v_n, int32_t* v_slot,
+                                  hipStream_t st);
+hipError_t ddn_dev_dpmr_voice_file(const int32_t* n_sync, int n_channels, int max_syncs, const uint8_t* fr_slot,
+                                   const uint8_t* voiced2, const uint8_t* muted2, int vf, uint8_t* fr, int32_t* v_n, int32_t* v_slot,
+                                   uint8_t* v_half, uint8_t* v_muted, uint8_t* v_skip, hipStream_t st);
+hipError_t ddn_dev_ysf_pack96(const uint8_t* frames184, size_t n, uint8_t* frames96, hipStream_t st);
 hipError_t ddn_dev_u8_shr1(const uint8_t* in, size_t n, uint8_t* out, hipStream_t st);
 hipError_t ddn_dev_tsbk_select(const uint8_t* cand, const int32_t* counts, size_t n, uint8_t* out12, uint8_t* crc_ok, uint8_t* sel,
                                hipStream_t st);

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ddn_api_util.h"
 #include "ddn_device.h"
 #include "ddn_fec3.h"
 #include "ddn_fsk4.h"
@@ -275,15 +276,6 @@ ddn_dev_dpmr_voice_file(const int32_t* n_sync, int n_channels, int max_syncs, co
     return hipGetLastError();
 }
 
-#define DDN_TRY_HIP(expr)                                                                                                              \
-    do {                                                                                                                               \
-        const hipError_t e_ = (expr);                                                                                                  \
-        if (e_ != hipSuccess) {                                                                                                        \
-            ddn_set_error("%s failed: %s", #expr, hipGetErrorString(e_));                                                              \
-            return e_ == hipErrorOutOfMemory ? DDN_ENOMEM : DDN_EHIP;                                                                  \
-        }                                                                                                                              \
-    } while (0)
-
 extern "C" int
 ddn_dpmr_superframe_decode_batch(const uint8_t* d_records10, size_t stride_symbols, const int32_t* d_counts, const int32_t* d_sync_pos,
                                  const int32_t* d_n_sync, int n_channels, size_t max_syncs, int inverted, uint8_t* d_cch_bits2x48,
@@ -303,11 +295,11 @@ ddn_dpmr_superframe_decode_batch(const uint8_t* d_records10, size_t stride_symbo
     }
     hipStream_t st = (hipStream_t)hip_stream;
     const DdnFec3Tables* T = nullptr;
-    DDN_TRY_HIP(ddn_dev_fec3_tables(&T, st));
+    DDN_LAUNCH_TRY(ddn_dev_fec3_tables(&T, st));
     hipLaunchKernelGGL(k_dpmr_superframe, dim3((unsigned)max_syncs, (unsigned)n_channels), dim3(64), 0, st, d_records10, stride_symbols,
                        d_counts, d_sync_pos, d_n_sync, (int)max_syncs, inverted, T, d_cch_bits2x48, d_ham_ok2x6, d_crc_ok2, d_fields2x8, d_id,
                        d_color, d_valid);
-    DDN_TRY_HIP(hipGetLastError());
+    DDN_LAUNCH_TRY(hipGetLastError());
     return DDN_OK;
 }
 
@@ -328,7 +320,7 @@ ddn_dpmr_identity_batch(const int32_t* d_n_sync, int n_channels, size_t max_sync
     }
     hipLaunchKernelGGL(k_dpmr_identity, dim3((unsigned)((n_channels + 63) / 64)), dim3(64), 0, (hipStream_t)hip_stream, d_n_sync, n_channels,
                        (int)max_syncs, d_valid, d_fields2x8, d_ham_ok2x6, d_crc_ok2, d_id, d_state3, d_kind, d_strong, d_tg, d_src);
-    DDN_TRY_HIP(hipGetLastError());
+    DDN_LAUNCH_TRY(hipGetLastError());
     return DDN_OK;
 }
 
@@ -349,7 +341,7 @@ ddn_dpmr_voice_gather(const uint8_t* d_records10, size_t stride_symbols, const i
     }
     hipLaunchKernelGGL(k_dpmr_voice_gather, dim3((unsigned)max_syncs, (unsigned)n_channels), dim3(64), 0, (hipStream_t)hip_stream, d_records10,
                        stride_symbols, d_sync_pos, d_n_sync, (int)max_syncs, inverted, d_fields2x8, d_valid, d_ambe_fr, d_voiced2, d_muted2);
-    DDN_TRY_HIP(hipGetLastError());
+    DDN_LAUNCH_TRY(hipGetLastError());
     return DDN_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ddn_api_util.h"
 #include "ddn_expf.h"
 #include "ddn_fsk4.h"
 #include "ddn_internal.h"
@@ -320,15 +321,6 @@ k_dstar_voice(const uint8_t* __restrict__ rec, size_t stride, const int32_t* __r
 
 } // namespace
 
-#define DDN_TRY_HIP(expr)                                                                                                              \
-    do {                                                                                                                               \
-        const hipError_t e_ = (expr);                                                                                                  \
-        if (e_ != hipSuccess) {                                                                                                        \
-            ddn_set_error("%s failed: %s", #expr, hipGetErrorString(e_));                                                              \
-            return e_ == hipErrorOutOfMemory ? DDN_ENOMEM : DDN_EHIP;                                                                  \
-        }                                                                                                                              \
-    } while (0)
-
 extern "C" int
 ddn_dstar_header_decode_batch(const uint8_t* d_records10, size_t stride_symbols, const int32_t* d_counts, const int32_t* d_sync_pos,
                               const uint8_t* d_sync_pat, const int32_t* d_n_sync, const float* d_sync_thr5, int n_channels, size_t max_syncs,
@@ -346,7 +338,7 @@ ddn_dstar_header_decode_batch(const uint8_t* d_records10, size_t stride_symbols,
     }
     hipLaunchKernelGGL(k_dstar_header, dim3((unsigned)max_syncs, (unsigned)n_channels), dim3(64), 0, (hipStream_t)hip_stream, d_records10,
                        stride_symbols, d_counts, d_sync_pos, d_sync_pat, d_n_sync, d_sync_thr5, (int)max_syncs, d_hdr41, d_hdr_crc_ok, d_valid);
-    DDN_TRY_HIP(hipGetLastError());
+    DDN_LAUNCH_TRY(hipGetLastError());
     return DDN_OK;
 }
 
@@ -370,6 +362,6 @@ ddn_dstar_voice_decode_batch(const uint8_t* d_records10, size_t stride_symbols, 
     hipLaunchKernelGGL(k_dstar_voice, dim3((unsigned)max_syncs, (unsigned)n_channels), dim3(64), 0, (hipStream_t)hip_stream, d_records10,
                        stride_symbols, d_counts, d_sync_pos, d_sync_pat, d_n_sync, d_sync_thr5, (int)max_syncs, d_ambe_fr, d_sd_bytes,
                        d_sd_kind, d_sd_hdr41, d_sd_crc_ok, d_sd_text, d_valid);
-    DDN_TRY_HIP(hipGetLastError());
+    DDN_LAUNCH_TRY(hipGetLastError());
     return DDN_OK;
 }

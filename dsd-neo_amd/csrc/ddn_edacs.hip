@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ddn_api_util.h"
 #include "ddn_fsk4.h"
 #include "ddn_internal.h"
 
@@ -153,15 +154,6 @@ k_edacs_frame(const uint8_t* __restrict__ rec, size_t stride, const int32_t* __r
 
 } // namespace
 
-#define DDN_TRY_HIP(expr)                                                                                                              \
-    do {                                                                                                                               \
-        const hipError_t e_ = (expr);                                                                                                  \
-        if (e_ != hipSuccess) {                                                                                                        \
-            ddn_set_error("%s failed: %s", #expr, hipGetErrorString(e_));                                                              \
-            return e_ == hipErrorOutOfMemory ? DDN_ENOMEM : DDN_EHIP;                                                                  \
-        }                                                                                                                              \
-    } while (0)
-
 extern "C" int
 ddn_edacs_frame_decode_batch(const uint8_t* d_records10, size_t stride_symbols, const int32_t* d_counts, const int32_t* d_sync_pos,
                              const uint8_t* d_sync_pat, const int32_t* d_n_sync, const float* d_sync_thr5, int n_channels, size_t max_syncs,
@@ -183,6 +175,6 @@ ddn_edacs_frame_decode_batch(const uint8_t* d_records10, size_t stride_symbols, 
                        stride_symbols, d_counts, d_sync_pos, d_sync_pat, d_n_sync, d_sync_thr5, (int)max_syncs, ea_mode, esk_mask,
                        (unsigned long long*)d_raw40, (unsigned long long*)d_vote40, d_bch_ok, d_frame_ok, d_msg28, d_kind, d_types, d_site6,
                        d_valid);
-    DDN_TRY_HIP(hipGetLastError());
+    DDN_LAUNCH_TRY(hipGetLastError());
     return DDN_OK;
 }

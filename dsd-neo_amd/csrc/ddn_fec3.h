@@ -1,10 +1,7 @@
 // ddn_fec3.h - internal launch prototypes of ddn_fec3.hip (the C-ABI is in include/ddn_hip.h)
 #ifndef DDN_FEC3_H
 #define DDN_FEC3_H
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "ddn_internal.h"
+#include "ddn_device.h" /* (ddn_m17.hip, which defines launchers declared there, has it from here) */
 
 /* syndrome -> positions-to-flip tables of the DMR / NXDN block codes, one copy per device, built in the reference's init-loop
  * order (ddn_fec3.hip) */

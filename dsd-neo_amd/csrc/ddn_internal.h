@@ -33,6 +33,11 @@ struct ddn_fsk4_chain;
 int ddn_p25_chain_stage0_prepare(struct ddn_p25_chain* c, void* hip_stream, float** disc_out);
 float* ddn_fsk4_chain_disc_buffer(struct ddn_fsk4_chain* c);
 void* ddn_fsk4_chain_reads_done_event(struct ddn_fsk4_chain* c);
+/* the mixed chain's overlapped schedule: a second discriminator buffer for the odd steps (ddn_api_chain.cpp) */
+int ddn_p25_chain_double_disc(struct ddn_p25_chain* c);
+/* ddn_fec_viterbi_k5_batch over the code words d_wanted [n] marks, 0 = leave undecoded (ddn_api_fec.cpp) */
+int ddn_fec_viterbi_k5_batch_wanted(const uint16_t* d_soft, size_t n, int in_len, const uint8_t* punct, int p_len, uint8_t* d_out,
+                                    int out_stride, uint32_t* d_cost, const uint8_t* d_wanted, void* hip_stream);
 /* the two kernels of ddn_mbe_synth_batch as separate calls (ddn_api_mbe.cpp) */
 struct ddn_mbe_batch;
 int ddn_mbe_params_only(struct ddn_mbe_batch* b, const uint8_t* d_bits, const int32_t* d_result_in, size_t n_frames, int32_t* d_result_out,
