@@ -9,6 +9,8 @@ import pytest
 import ddn
 import orc
 import rx4
+from chain_fsk4_stream import dmr_data_stream as _dmr_data_stream
+from chain_fsk4_stream import dmr_voice_stream as _dmr_voice_stream
 from conftest import golden
 
 pytestmark = pytest.mark.gpu
@@ -308,55 +310,6 @@ def test_dmr_chain_voice_bursts_to_pcm(built):
                 assert np.array_equal(g[4], ro[0]), (tp, pos)
                 total += 1
     assert total >= 18, total
-
-
-def _dmr_data_stream(rng):
-    """a BS stream of data bursts (both time slots alternating): CSBKs until the colour-code gate locks, then every data type the
-    handler treats differently -> (dibits, [(type, kwargs, what was sent)])"""
-    import dmrgen
-    plan = [(3, {})] * 8 + [(6, {}), (8, {}), (8, {}), (8, dict(confirmed=True, dbsn=0)), (8, dict(confirmed=True, dbsn=1)),
-                            (8, dict(confirmed=True, dbsn=2, good_crc=False)), (7, {}), (7, dict(confirmed=True, dbsn=3)),
-                            (10, dict(confirmed=True)), (1, {}), (2, {}), (1, dict(hurt=True)), (3, dict(good_crc=False)), (0, {}), (11, {}),
-                            (4, {}), (5, {}), (9, {}), (6, dict(good_crc=False)), (3, {})]
-    plan = plan + plan[8:]
-    out, sent = [], []
-    for k, (ty, kw) in enumerate(plan):
-        kw = dict(kw)
-        hurt = kw.pop("hurt", False)
-        if ty == 8:
-            s = dmrgen.r34_bytes(rng, **kw)
-            info = dmrgen.r34_info(s)
-        elif ty == 10:
-            info = rng.integers(0, 2, 196).astype(np.uint8)
-            info[96:100] = 0
-            c = dmrgen.crc9_confirmed_rate1(info)
-            info[7:16] = [(c >> (8 - i)) & 1 for i in range(9)]
-            s = info.copy()
-        else:
-            s = dmrgen.payload_bits(ty, rng, **kw)
-            t = s.copy()
-            if hurt:
-                t[16:24] ^= np.unpackbits(np.array([0xA5], np.uint8))          # one wrong byte: RS(12,9) repairs it
-            info = dmrgen.bptc_196x96(t)
-        out.append(dmrgen.burst(k & 1, 7, ty, info))
-        sent.append((ty, kw, hurt, s))
-    return np.concatenate(out), sent
-
-
-def _dmr_voice_stream(rng, n_superframes=4):
-    """CSBKs on both slots until the colour-code gate locks, then voice superframes on slot 1 (link control embedded in bursts B..E,
-    the third one with a wrong checksum) beside idle data bursts on slot 2 -> (dibits, the link controls sent)"""
-    import dmrgen
-    out = [dmrgen.burst(k & 1, 7, 3, dmrgen.bptc_196x96(dmrgen.payload_bits(3, rng))) for k in range(8)]
-    lcs = []
-    for q in range(n_superframes):
-        lc = rng.integers(0, 2, 72).astype(np.uint8)
-        good = q != 2
-        crc5 = None if good else (int(np.packbits(lc).astype(np.int64).sum()) % 31) ^ 0x0A
-        lcs.append((lc, good))
-        for b in dmrgen.voice_superframe(0, 7, lc, rng, crc5):
-            out += [b, dmrgen.burst(1, 7, 9, dmrgen.bptc_196x96(rng.integers(0, 2, 96)))]
-    return np.concatenate(out), lcs
 
 
 def test_dmr_chain_data_bursts_link_control_rate34_and_embedded_lc(built):

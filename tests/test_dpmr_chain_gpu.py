@@ -11,8 +11,20 @@ import ddn
 import dpmr
 import dpmrgen
 import mbe
-import orc
 import rx4
+
+# the per-slot checks, the chain's collector, its whole-stream reference and its checks live in tests/chain_fsk4_stream.py (the
+# short-call tests share them)
+from chain_fsk4_stream import DPMR_VOICE_PLAN as VOICE_PLAN
+from chain_fsk4_stream import dpmr_aiid as aiid
+from chain_fsk4_stream import dpmr_check_chain_channel as check_chain_channel
+from chain_fsk4_stream import dpmr_check_chain_voice as check_chain_voice
+from chain_fsk4_stream import dpmr_check_identity as check_identity
+from chain_fsk4_stream import dpmr_check_superframe as check_superframe
+from chain_fsk4_stream import dpmr_check_voice_slot as check_voice_slot
+from chain_fsk4_stream import dpmr_oracle_stream as oracle_stream
+from chain_fsk4_stream import dpmr_run_chain as run_chain
+from chain_fsk4_stream import dpmr_voice_transmission as _voice_transmission
 
 pytestmark = pytest.mark.gpu
 
@@ -55,38 +67,6 @@ def device_decode(streams, syncs, inverted, state=None):
     out = {k: v.cpu().numpy() for k, v in o.items()}
     out["state"] = st.cpu().numpy()
     return out
-
-
-KIND = {None: 0, "called": 1, "calling": 2}
-
-
-def aiid(v):
-    return None if int(v) < 0 else dpmr.air_interface_id(int(v))
-
-
-def check_superframe(got, c, k, sf):
-    """slot (c, k) of the device outputs == the restatement's superframe dict"""
-    for h in range(2):
-        w = sf["cch"][h]
-        assert np.array_equal(got["bits"][c, k, h], np.asarray(w["bits48"], np.uint8)), (c, k, h)
-        assert got["ham"][c, k, h].tolist() == w["ham"], (c, k, h)
-        assert bool(got["crc"][c, k, h]) == bool(w["crc_ok"]), (c, k, h)
-        want = [w["fn"], dpmr.value(w["bits48"][2:14]), w["mode"], w["version"], w["format"], w["emergency"], w["reserved"], w["slow"]]
-        assert got["fields"][c, k, h].tolist() == want, (c, k, h)
-    assert int(got["id"][c, k]) == sf["id"] and int(got["color"][c, k]) == sf["color"], (c, k)
-
-
-def check_identity(got, c, k, sf):
-    assert int(got["kind"][c, k]) == KIND[sf["kind"]] and bool(got["strong"][c, k]) == sf["strong"], (c, k)
-    assert aiid(got["tg"][c, k]) == sf["tg"] and aiid(got["src"][c, k]) == sf["src"], (c, k)
-
-
-def check_voice_slot(got, c, k, sf):
-    halves = dpmr.voice_halves(sf)
-    for f in range(8):
-        assert np.array_equal(got["fr"][c, k, f], rx4.ambe2450_deinterleave(sf["voice"][f])[0]), (c, k, f)
-    for h in range(2):
-        assert bool(got["voiced"][c, k, h]) == halves[h] and bool(got["muted"][c, k, h]) == (sf["cch"][h]["version"] == 3), (c, k, h)
 
 
 def test_superframe_kernels_on_the_capture_records_under_both_words(built):
@@ -162,114 +142,6 @@ def _upload(l, part):
     return p
 
 
-def run_chain(x, n, inverted=0, vocoder=1, rf_mod=2):
-    """x: cu8 [B][samples][2] in calls of n samples + flush -> per channel the decoded superframes
-    [(absolute sync position, slot outputs)] and the synthesised frames [(absolute sync position, half, muted, pcm, result)]"""
-    l = ddn.lib()
-    B = x.shape[0]
-    calls = x.shape[1] // n
-    ch = ddn.Fsk4ChainC(B, n, ddn.FSK4_DPMR, rf_mod=rf_mod, inverted=inverted, handlers=0, vocoder=vocoder)
-    sfs, voice = [[] for _ in range(B)], [[] for _ in range(B)]
-    base = np.zeros(B, np.int64)
-    seams = [0]
-
-    def take():
-        r, rd = ch.results(), ch.dpmr_results()
-        S, T, F = rd.max_syncs, r.carry_symbols, rd.voice_frames
-        f = ch.fetch
-        pos, new, ns = f(rd.d_sync_pos, np.int32, (B, S)), f(r.d_new, np.int32, (B,)), f(rd.d_n_sync, np.int32, (B,))
-        got = dict(bits=f(rd.d_cch_bits2x48, np.uint8, (B, S, 2, 48)), ham=f(rd.d_ham_ok2x6, np.uint8, (B, S, 2, 6)),
-                   crc=f(rd.d_crc_ok2, np.uint8, (B, S, 2)), fields=f(rd.d_fields2x8, np.int32, (B, S, 2, 8)), id=f(rd.d_id, np.int32, (B, S)),
-                   color=f(rd.d_color, np.int32, (B, S)), valid=f(rd.d_valid, np.uint8, (B, S)), kind=f(rd.d_kind, np.uint8, (B, S)),
-                   strong=f(rd.d_strong, np.uint8, (B, S)), tg=f(rd.d_tg, np.int32, (B, S)), src=f(rd.d_src, np.int32, (B, S)))
-        if vocoder:
-            assert F >= 8
-            got.update(fr=f(rd.d_ambe_fr, np.uint8, (B, S, 8, 4, 24)), voiced=f(rd.d_voiced2, np.uint8, (B, S, 2)),
-                       muted=f(rd.d_muted2, np.uint8, (B, S, 2)))
-            nv, slot = f(rd.d_n_voice, np.int32, (B,)), f(rd.d_voice_slot, np.int32, (B, F))
-            half, mut, skip = f(rd.d_voice_half, np.uint8, (B, F)), f(rd.d_voice_muted, np.uint8, (B, F)), f(rd.d_voice_skip, np.uint8, (B, F))
-            res, pcm = f(rd.d_voice_result, np.int32, (B, F, 5)), f(rd.d_pcm, np.float32, (B, F, 160))
-        else:
-            assert F == 0 and rd.d_pcm is None
-        for c in range(B):
-            for k in range(int(ns[c])):
-                one = {key: v[c, k] for key, v in got.items()}
-                if pos[c, k] < T:
-                    seams[0] += 1                  # a superframe whose sync came in the previous call
-                sfs[c].append((int(base[c]) + int(pos[c, k]) - int(T), one))
-            if vocoder:
-                assert not pcm[c, nv[c]:].any() and skip[c, nv[c]:].all() and not skip[c, :nv[c]].any() and nv[c] % 4 == 0
-                for j in range(int(nv[c])):
-                    voice[c].append((int(base[c]) + int(pos[c, slot[c, j]]) - int(T), int(half[c, j]), int(mut[c, j]), pcm[c, j].copy(),
-                                     res[c, j].copy()))
-            base[c] += int(new[c])
-
-    for k in range(calls):
-        p = _upload(l, np.ascontiguousarray(x[:, k * n:(k + 1) * n]))
-        ch.run(p)
-        take()
-        l.ddn_device_free(p)
-    ch.flush()
-    take()
-    ch.close()
-    return sfs, voice, seams[0]
-
-
-def oracle_stream(xc, n, inverted=0, rf_mod=2):
-    """one channel through the pinned front end (call by call, as the chain) and the oracle loop -> (dibits, syncs, decode_stream)"""
-    fe = orc.OracleFrontEnd(profile=1)
-    calls = len(xc) // n
-    disc = np.concatenate([fe.run_cu8(np.ascontiguousarray(xc[k * n:(k + 1) * n]), 8192) for k in range(calls)])
-    o = rx4.OracleFsk4Rx(dpmr.profile(inverted, rf_mod=rf_mod)).run(disc, max_sync=4096)
-    dib, sp = o["rec4"][:, 0].astype(np.uint8), np.asarray(o["sync_pos"])
-    return dib, sp, dpmr.decode_stream(dib, sp, inverted)
-
-
-def check_chain_channel(sfs_c, want):
-    """every whole superframe of the oracle's stream, once, in order, equal field for field (slots the chain saw past the stream's end
-    at flush are the restatement's skipped ones: valid = 0)"""
-    got = [(p, g) for p, g in sfs_c if g["valid"]]
-    assert len({p for p, _ in sfs_c}) == len(sfs_c), "a superframe decoded twice"
-    assert [p for p, _ in got] == [int(s) for s in want[1][[k for k, _ in want[2]]]], (len(got), len(want[2]))
-    for (p, g), (k, sf) in zip(got, want[2]):
-        g1 = {key: v[None, None] for key, v in g.items()}
-        check_superframe(g1, 0, 0, sf)
-        check_identity(g1, 0, 0, sf)
-        if "fr" in g:
-            check_voice_slot(g1, 0, 0, sf)
-    return got
-
-
-def check_chain_voice(voice_c, want, talk_path):
-    """the synthesised frames == the voiced halves voice_plan selects, in air order; PCM and result rows == the CPU vocoder fed with
-    the restated frames through the oracle frame FEC, history carried across the calls"""
-    plan = []
-    for k, sf in want[2]:
-        halves = dpmr.voice_halves(sf)
-        frames, muted = dpmr.voice_plan([c["mode"] for c in sf["cch"]], [c["version"] for c in sf["cch"]])
-        voiced = [h for h in range(2) if halves[h]]
-        if voiced:
-            assert muted == int(sf["cch"][voiced[-1]]["version"] == 3)
-        for h in voiced:
-            for i in range(4):
-                plan.append((int(want[1][k]), h, int(sf["cch"][h]["version"] == 3), sf["voice"][4 * h + i]))
-    assert [(v[0], v[1], v[2]) for v in voice_c] == [(p[0], p[1], p[2]) for p in plan], (len(voice_c), len(plan))
-    if not plan:
-        return 0
-    frames = np.stack([rx4.ambe2450_deinterleave(p[3])[0] for p in plan])
-    bits, res, _ = mbe.oracle_frame_decode(ddn.MBE_AMBE, frames)
-    voc = mbe.OracleVocoder(ddn.MBE_AMBE, 1)
-    F = len(plan)
-    pcm, ro = np.zeros((1, F, 160), np.float32), np.zeros((1, F, 5), np.int32)
-    bits, res = np.ascontiguousarray(bits[None]), np.ascontiguousarray(res[None])
-    assert mbe._o().om_process_batch(ddn.MBE_AMBE, C.addressof(voc.tab), bits.ctypes.data, res.ctypes.data, 0, talk_path, 1, F, pcm.ctypes.data,
-                                     ro.ctypes.data, C.addressof(voc.cur), C.addressof(voc.prev), C.addressof(voc.enh)) == 0
-    for j, g in enumerate(voice_c):
-        assert np.array_equal(g[3].view(np.uint32), pcm[0, j].view(np.uint32)), (talk_path, j, float(np.abs(g[3] - pcm[0, j]).max()))
-        assert np.array_equal(g[4], ro[0, j]), (talk_path, j)
-    return F
-
-
 def _capture_iq():
     from conftest import golden
     return np.ascontiguousarray(golden("iq_dpmr.npz")["iq"], np.uint8)
@@ -339,21 +211,6 @@ def test_chain_xd(built):
     assert {(int(g["fields"][0, 0]), int(g["fields"][1, 0])) for g in good} == {(0, 1), (2, 3)}
     assert {int(g["color"]) for g in good} == {2}
     assert aiid(got[-1][1]["tg"]) == "3939*5*" and aiid(got[-1][1]["src"]) == "3939*5*"
-
-
-def _voice_transmission(rng, plan):
-    """generated superframes: (mode0, mode1, version0, version1) per superframe; AMBE frames from mbe.ambe_encode"""
-    sfs = []
-    for i, (m0, m1, v0, v1) in enumerate(plan):
-        fn = (0, 1) if i % 2 == 0 else (2, 3)
-        cch = [dpmrgen.cch_dibits(dpmrgen.cch_bits(fn=fn[h], half=(0x5A5, 0x3C3)[h] + i % 2, mode=(m0, m1)[h], version=(v0, v1)[h]))
-               for h in range(2)]
-        tch = [dpmrgen.ambe_dibits(mbe.ambe_encode(b)) for b in mbe.random_ambe_bits(rng, (8,))]
-        sfs.append(dpmrgen.superframe(cch[0], cch[1], dpmrgen.color_pattern(i % 64), tch))
-    return sfs
-
-
-VOICE_PLAN = [(0, 0, 0, 0), (1, 1, 0, 0), (5, 5, 0, 3), (2, 2, 0, 0), (0, 7, 3, 0), (4, 1, 0, 3), (5, 0, 3, 3), (0, 0, 0, 0)] * 3
 
 
 def test_generated_voice_through_the_batch_entries(built):

@@ -9,7 +9,6 @@ import pytest
 
 import ddn
 import dstar
-import orc
 import rx4
 
 pytestmark = pytest.mark.gpu
@@ -17,74 +16,10 @@ pytestmark = pytest.mark.gpu
 N_CALL = 48000
 
 
-def _upload(l, part):
-    p = C.c_void_p()
-    assert l.ddn_device_alloc(part.nbytes, C.byref(p)) == 0 and l.ddn_device_upload(p, part.ctypes.data, part.nbytes) == 0
-    return p
-
-
-def run_chain(x, n, rf_mod=2):
-    """x: cu8 [B][samples][2] in calls of n samples + flush -> per channel [(absolute sync position, pattern, slot outputs)]"""
-    l = ddn.lib()
-    B = x.shape[0]
-    ch = ddn.Fsk4ChainC(B, n, ddn.FSK4_DSTAR, rf_mod=rf_mod, handlers=0, vocoder=0)
-    units = [[] for _ in range(B)]
-    base = np.zeros(B, np.int64)
-
-    def take():
-        r, rd = ch.results(), ch.dstar_results()
-        S, T = rd.max_syncs, r.carry_symbols
-        f = ch.fetch
-        pos, new, ns = f(rd.d_sync_pos, np.int32, (B, S)), f(r.d_new, np.int32, (B,)), f(rd.d_n_sync, np.int32, (B,))
-        got = dict(pat=f(rd.d_sync_pat, np.uint8, (B, S)), thr=f(rd.d_sync_thr5, np.float32, (B, S, 5)), h41=f(rd.d_hdr41, np.uint8, (B, S, 41)),
-                   hok=f(rd.d_hdr_crc_ok, np.uint8, (B, S)), hv=f(rd.d_hdr_valid, np.uint8, (B, S)),
-                   ambe=f(rd.d_ambe_fr, np.uint8, (B, S, 21, 4, 24)), sdb=f(rd.d_sd_bytes, np.uint8, (B, S, 60)),
-                   kind=f(rd.d_sd_kind, np.uint8, (B, S)), sh41=f(rd.d_sd_hdr41, np.uint8, (B, S, 41)), sok=f(rd.d_sd_crc_ok, np.uint8, (B, S)),
-                   text=f(rd.d_sd_text, np.uint8, (B, S, 60)), valid=f(rd.d_valid, np.uint8, (B, S)))
-        for c in range(B):
-            for k in range(int(ns[c])):
-                units[c].append((int(base[c]) + int(pos[c, k]) - int(T), {key: v[c, k] for key, v in got.items()}))
-            base[c] += int(new[c])
-
-    for k in range(x.shape[1] // n):
-        p = _upload(l, np.ascontiguousarray(x[:, k * n:(k + 1) * n]))
-        ch.run(p)
-        take()
-        l.ddn_device_free(p)
-    ch.flush()
-    take()
-    ch.close()
-    return units
-
-
-def oracle_stream(xc, n, rf_mod=2):
-    """one channel through the pinned front end (6.25 kHz filter, call by call as the chain) and the oracle loop -> (syncs, patterns,
-    decode_stream)"""
-    fe = orc.OracleFrontEnd(profile=1)
-    calls = len(xc) // n
-    disc = np.concatenate([fe.run_cu8(np.ascontiguousarray(xc[k * n:(k + 1) * n]), 8192) for k in range(calls)])
-    o = rx4.OracleFsk4Rx(dstar.profile(rf_mod)).run(disc, max_sync=4096)
-    return o, dstar.decode_stream(o["sym"], o["sync_pos"], o["sync_pat"], o["sync_thr"])
-
-
-def check_chain_channel(units_c, want):
-    """every unit of the oracle's stream, once, in order, equal field for field"""
-    o, dec = want
-    assert len({p for p, _ in units_c}) == len(units_c), "a unit decoded twice"
-    got = [(p, g) for p, g in units_c if g["valid"]]
-    assert [p for p, _ in got] == [int(o["sync_pos"][k]) for k, _ in dec], (len(got), len(dec))
-    for (p, g), (k, u) in zip(got, dec):
-        assert int(g["pat"]) == u["pat"] and np.array_equal(g["thr"].view(np.uint32), o["sync_thr"][k].view(np.uint32)), k
-        if u["pat"] >= 2:
-            assert g["hv"] and bytes(g["h41"]) == bytes(u["header41"]) and bool(g["hok"]) == bool(u["header_crc_ok"]), k
-        else:
-            assert not g["hv"] and not g["h41"].any()
-        sd = u["sd"]
-        assert np.array_equal(g["ambe"], u["ambe"]), k
-        assert bytes(g["sdb"]) == sd["bytes"] and int(g["kind"]) == sd["kind"], k
-        assert bytes(g["sh41"]) == sd["hdr41"] and bool(g["sok"]) == sd["crc_ok"], k
-        assert bytes(g["text"]) == (sd["text"] or bytes(60)), k
-    return got
+# the collector, the whole-stream reference and the check live in tests/chain_fsk4_stream.py (the short-call tests share them)
+from chain_fsk4_stream import dstar_check_chain_channel as check_chain_channel
+from chain_fsk4_stream import dstar_oracle_stream as oracle_stream
+from chain_fsk4_stream import dstar_run_chain as run_chain
 
 
 def src_of(got):

@@ -10,75 +10,16 @@ import pytest
 import ddn
 import edacs
 import edacsgen
-import orc
 
 pytestmark = pytest.mark.gpu
 
 N_CALL = 48000
 
 
-def _upload(l, part):
-    p = C.c_void_p()
-    assert l.ddn_device_alloc(part.nbytes, C.byref(p)) == 0 and l.ddn_device_upload(p, part.ctypes.data, part.nbytes) == 0
-    return p
-
-
-def run_chain(x, n, rf_mod=2, mode="-fh"):
-    """x: cu8 [B][samples][2] in calls of n samples + flush -> per channel [(absolute sync position, slot outputs)]"""
-    l = ddn.lib()
-    B = x.shape[0]
-    ch = ddn.Fsk4ChainC(B, n, ddn.FSK4_EDACS, rf_mod=rf_mod, handlers=0, vocoder=0)
-    ch.set_edacs_mode(*edacs.MODES[mode])
-    units = [[] for _ in range(B)]
-    base = np.zeros(B, np.int64)
-
-    def take():
-        r, rd = ch.results(), ch.edacs_results()
-        assert (rd.ea_mode, rd.esk_mask) == edacs.MODES[mode]
-        S, T = rd.max_syncs, r.carry_symbols
-        f = ch.fetch
-        pos, new, ns = f(rd.d_sync_pos, np.int32, (B, S)), f(r.d_new, np.int32, (B,)), f(rd.d_n_sync, np.int32, (B,))
-        got = dict(pat=f(rd.d_sync_pat, np.uint8, (B, S)), thr=f(rd.d_sync_thr5, np.float32, (B, S, 5)), raw40=f(rd.d_raw40, np.uint64, (B, S, 6)),
-                   vote40=f(rd.d_vote40, np.uint64, (B, S, 2)), bch_ok=f(rd.d_bch_ok, np.uint8, (B, S, 2)),
-                   frame_ok=f(rd.d_frame_ok, np.uint8, (B, S)), msg28=f(rd.d_msg28, np.uint32, (B, S, 2)), kind=f(rd.d_kind, np.uint8, (B, S)),
-                   types=f(rd.d_types, np.uint8, (B, S, 3)), site6=f(rd.d_site6, np.int32, (B, S, 6)), valid=f(rd.d_valid, np.uint8, (B, S)))
-        for c in range(B):
-            for k in range(int(ns[c])):
-                units[c].append((int(base[c]) + int(pos[c, k]) - int(T), {key: v[c, k] for key, v in got.items()}))
-            base[c] += int(new[c])
-
-    for k in range(x.shape[1] // n):
-        p = _upload(l, np.ascontiguousarray(x[:, k * n:(k + 1) * n]))
-        ch.run(p)
-        take()
-        l.ddn_device_free(p)
-    ch.flush()
-    take()
-    ch.close()
-    return units
-
-
-def loop_stream(xc, n, rf_mod=2):
-    """one channel through the pinned front end (ProVoice profile, call by call as the chain) and the restated loop"""
-    fe = orc.OracleFrontEnd(profile=3)
-    calls = len(xc) // n
-    disc = np.concatenate([fe.run_cu8(np.ascontiguousarray(xc[k * n:(k + 1) * n]), 8192) for k in range(calls)])
-    return edacs.LoopRx(rf_mod).run(disc, max_sync=4096)
-
-
-def check_chain_channel(units_c, o, mode="-fh"):
-    """every frame of the restated stream, once, in order, equal field for field"""
-    ea, esk = edacs.MODES[mode]
-    assert len({p for p, _ in units_c}) == len(units_c), "a frame decoded twice"
-    got = [(p, g) for p, g in units_c if g["valid"]]
-    want = [(int(p), int(pat), t) for p, pat, t in zip(o["sync_pos"], o["sync_pat"], o["sync_thr"]) if int(p) + 1 + edacs.FRAME <= len(o["sym"])]
-    assert [p for p, _ in got] == [p for p, _, _ in want], (len(got), len(want))
-    for (p, g), (_, pat, t) in zip(got, want):
-        assert int(g["pat"]) == pat and np.array_equal(g["thr"].view(np.uint32), t.view(np.uint32)), p
-        u = edacs.decode_slot(o["sym"], p, pat, t, ea, esk)
-        for key in ("raw40", "vote40", "bch_ok", "frame_ok", "msg28", "kind", "types", "site6"):
-            assert np.array_equal(np.asarray(g[key]).astype(np.int64).reshape(-1), np.asarray(u[key], np.uint64).astype(np.int64).reshape(-1)), (p, key)
-    return [g for _, g in got]
+# the collector, the whole-stream reference and the check live in tests/chain_fsk4_stream.py (the short-call tests share them)
+from chain_fsk4_stream import edacs_check_chain_channel as check_chain_channel
+from chain_fsk4_stream import edacs_loop_stream as loop_stream
+from chain_fsk4_stream import edacs_run_chain as run_chain
 
 
 def _capture_iq():
