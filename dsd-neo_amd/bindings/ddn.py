@@ -1209,12 +1209,17 @@ class P25P2ChainResults(C.Structure):  # == ddn_p25p2_chain_results
 
 
 class P25P2ChainC:
-    """ddn_p25p2_chain: I/Q of B Phase 2 channels -> MAC PDUs + PCM of both logical channels, one C call per batch of samples"""
+    """ddn_p25p2_chain: I/Q of B Phase 2 channels -> MAC PDUs + PCM of both logical channels, one C call per batch of samples.
+    `handle`: a non-owning view of a chain object that exists already (a node part's), as Fsk4ChainC has it"""
 
-    def __init__(self, seeds44, samples_per_call, block_len=8192, input_format=0, vocoder=1, max_groups=0):
+    def __init__(self, seeds44, samples_per_call, block_len=8192, input_format=0, vocoder=1, max_groups=0, handle=None):
         import numpy as np
         self.np = np
+        self.own = handle is None
         self.B, self.n = len(seeds44), samples_per_call
+        if handle is not None:
+            self.h = C.c_void_p(handle)
+            return
         cfg = P25P2ChainConfig(self.B, samples_per_call, block_len, input_format, 0, vocoder, max_groups, 0.0)
         seeds = np.ascontiguousarray(seeds44, np.uint64)
         self.h = C.c_void_p()
@@ -1238,9 +1243,9 @@ class P25P2ChainC:
         return a
 
     def close(self):
-        if self.h:
+        if self.h and self.own:
             lib().ddn_p25p2_chain_destroy(self.h)
-            self.h = C.c_void_p()
+        self.h = C.c_void_p()
 
     def __del__(self):
         try:

@@ -66,6 +66,8 @@ struct Part {
     int in_turn = 0;
     int in_flight = 0; // mixed, host input: calls queued since the last wait (a buffer set is reused every second call)
     hipStream_t st = nullptr;
+    hipEvent_t ev_in[2] = {nullptr, nullptr}; // FSK4 / P25P2, host input: the copies into input set k have left the caller's memory
+    bool ev_in_set[2] = {false, false};       // (recorded at least once)
     size_t sample_bytes = 2;
     int samples = 0;
     char err[256] = {0};
@@ -81,7 +83,9 @@ hip_rc(hipError_t e, const char* what) {
 }
 
 // host blocks -> this part's device input buffers (two sets, used in turn: the previous call's kernels may still read the other set),
-// on the part's stream ahead of the run call
+// on the part's stream ahead of the run call.  The copies are only queued here; ddn_node_run_host's promise - the previous call's
+// h_iq may be refilled once this call has returned - is kept by the caller on the host side (staged_run below, or the mixed kind's
+// stream wait), which also bounds what a host that never calls ddn_node_wait can have queued to two calls.
 int
 stage_inputs(Part* p, int n_groups, const void* d_out[3]) {
     for (int g = 0; g < n_groups; g++) {
@@ -112,7 +116,41 @@ stage_inputs(Part* p, int n_groups, const void* d_out[3]) {
 
 int
 make_stream(Part* p) {
-    return p->st ? DDN_OK : hip_rc(hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking), "hipStreamCreate");
+    if (p->st) {
+        return DDN_OK;
+    }
+    int rc = hip_rc(hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking), "hipStreamCreate");
+    for (hipEvent_t& e : p->ev_in) {
+        if (rc == DDN_OK) {
+            rc = hip_rc(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
+        }
+    }
+    return rc;
+}
+
+// The FSK4 and P25P2 kinds' host-input call: this call's copies, an event behind them, the chain's kernels - all on the part's stream -
+// and then, as ddn_p25_chain_run_host does, a host-side wait for the PREVIOUS call's copies: its h_iq has left the host before this
+// call returns.  That copy sits behind the kernels of the call before it, so at most two calls are ever queued, and the device
+// still has this call's copy and kernels to run while the host refills (a wait for the whole stream would leave it idle).
+// (ddn_p25p2_chain_run happens to wait for its stream itself - its decoder lists' lengths come back to the host - and
+// ddn_fsk4_chain_run does not: the promise is kept here, whatever the chain object does.)
+int
+staged_run(Part* p, int (*run)(Part*, const void*)) {
+    const int set = p->in_turn; // (stage_inputs moves in_turn on)
+    const void* d[3];
+    int rc = stage_inputs(p, 1, d);
+    if (rc == DDN_OK) {
+        rc = hip_rc(hipEventRecord(p->ev_in[set], p->st), "hipEventRecord");
+        p->ev_in_set[set] = rc == DDN_OK;
+    }
+    if (rc == DDN_OK) {
+        rc = run(p, d[0]);
+    }
+    if (p->ev_in_set[set ^ 1]) { // (whatever became of this call: the caller is about to refill the previous call's buffer)
+        const int rc2 = hip_rc(hipEventSynchronize(p->ev_in[set ^ 1]), "hipEventSynchronize");
+        rc = rc != DDN_OK ? rc : rc2;
+    }
+    return rc;
 }
 
 void
@@ -121,6 +159,12 @@ free_inputs(Part* p) {
         for (void*& d : g) {
             (void)hipFree(d);
             d = nullptr;
+        }
+    }
+    for (hipEvent_t& e : p->ev_in) {
+        if (e) {
+            (void)hipEventDestroy(e);
+            e = nullptr;
         }
     }
     if (p->st) {
@@ -211,11 +255,7 @@ const Ops kFsk4 = {
         p->chain = c;
         return rc == DDN_OK ? make_stream(p) : rc;
     },
-    [](Part* p) {
-        const void* d[3];
-        const int rc = stage_inputs(p, 1, d);
-        return rc == DDN_OK ? ddn_fsk4_chain_run((ddn_fsk4_chain*)p->chain, d[0], p->st) : rc;
-    },
+    [](Part* p) { return staged_run(p, [](Part* q, const void* d) { return ddn_fsk4_chain_run((ddn_fsk4_chain*)q->chain, d, q->st); }); },
     [](Part* p) { return ddn_fsk4_chain_run((ddn_fsk4_chain*)p->chain, p->a_iq3[0], p->st); },
     [](Part* p) { return hip_rc(hipStreamSynchronize(p->st), "hipStreamSynchronize"); },
     [](Part* p) {
@@ -233,11 +273,7 @@ const Ops kP25p2 = {
         p->chain = c;
         return rc == DDN_OK ? make_stream(p) : rc;
     },
-    [](Part* p) {
-        const void* d[3];
-        const int rc = stage_inputs(p, 1, d);
-        return rc == DDN_OK ? ddn_p25p2_chain_run((ddn_p25p2_chain*)p->chain, d[0], p->st) : rc;
-    },
+    [](Part* p) { return staged_run(p, [](Part* q, const void* d) { return ddn_p25p2_chain_run((ddn_p25p2_chain*)q->chain, d, q->st); }); },
     [](Part* p) { return ddn_p25p2_chain_run((ddn_p25p2_chain*)p->chain, p->a_iq3[0], p->st); },
     [](Part* p) { return hip_rc(hipStreamSynchronize(p->st), "hipStreamSynchronize"); },
     [](Part* p) {

@@ -68,7 +68,11 @@ int ddn_node_on_part(ddn_node* n, int part, int (*fn)(void* chain_object, void* 
  * Kinds other than P25: h_iq holds every channel's row in the order of the global channel index (MIXED: the P25 group's rows, then the
  * DMR group's, then the NXDN48 group's); a part copies its blocks into device buffers of its own (two sets, used in turn) and runs its
  * chain object on them; outs is ignored - the results stay on the device (ddn_node_chain_object + the kind's _get_results, through
- * ddn_node_on_part where the caller's thread has another device current). */
+ * ddn_node_on_part where the caller's thread has another device current).
+ * The same promise holds for every kind: when the call returns, the previous call's h_iq has left the host and may be refilled (this
+ * call's may not, until the next call or ddn_node_wait has returned).  A host that never calls ddn_node_wait therefore has at most
+ * two calls queued per part: P25 by ddn_p25_chain_run_host's own host-side waits, FSK4 and P25P2 by a host-side wait for the event
+ * behind the previous call's input copies, MIXED by waiting for its own copies in every call and for the chain object every second. */
 int ddn_node_run_host(ddn_node* n, const void* h_iq, const ddn_p25_chain_host_out* outs);
 /* the same with device-resident input: d_iq[p] = that part's I/Q on its device (ddn_p25_chain_run_pipelined; MIXED: d_iq[3 p + g] =
  * part p's group g, NULL where the part has no channel of the group - ddn_mixed_chain_run) */
