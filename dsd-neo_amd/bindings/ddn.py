@@ -414,6 +414,10 @@ PROTOTYPES.update({
     "ddn_m17_lsf_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5 + [C.c_int, C.c_size_t] + [C.c_void_p] * 4),
     "ddn_m17_str_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 4 + [C.c_int, C.c_size_t] + [C.c_void_p] * 5),
     "ddn_m17_lich_assemble_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 9),
+    "ddn_m17_pkt_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5 + [C.c_int, C.c_size_t] + [C.c_void_p] * 4),
+    "ddn_m17_brt_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 4 + [C.c_int, C.c_size_t] + [C.c_void_p] * 3),
+    "ddn_m17_data_state_bytes": (C.c_size_t, []),
+    "ddn_m17_data_assemble_batch": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_size_t] + [C.c_void_p] * 13 + [C.c_int, C.c_void_p]),
     "ddn_ysf_fich_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3 + [C.c_int, C.c_size_t] + [C.c_void_p] * 4),
     "ddn_dpmr_superframe_decode_batch": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3 + [C.c_int, C.c_size_t, C.c_int]
                                          + [C.c_void_p] * 8),
@@ -566,6 +570,13 @@ class EdacsChainResults(C.Structure):  # == ddn_edacs_chain_results
                                   "d_msg28", "d_kind", "d_types", "d_site6", "d_valid")]
 
 
+class M17DataChainResults(C.Structure):  # == ddn_m17_data_chain_results
+    _fields_ = [("max_syncs", C.c_size_t), ("max_packets", C.c_int)] + [
+        (k, C.c_void_p) for k in ("d_n_sync", "d_sync_pos", "d_sync_pat", "d_pkt26", "d_pkt_frame_status", "d_pkt_cost", "d_bits25",
+                                  "d_brt_frame_status", "d_pkt_status", "d_pkt_count", "d_brt_state", "d_n_packets", "d_packet",
+                                  "d_packet_app_len", "d_packet_crc_ok", "d_packet_slot")]
+
+
 def dpmr_air_interface_id(v):
     """ddn_dpmr_air_interface_id: the seven characters the reference prints for a raw 24-bit dPMR ID"""
     out = C.create_string_buffer(8)
@@ -617,6 +628,8 @@ PROTOTYPES.update({
     "ddn_fsk4_chain_get_dstar_results": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_fsk4_chain_get_edacs_results": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_fsk4_chain_set_edacs_mode": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "ddn_fsk4_chain_set_m17_packet_slots": (C.c_int, [C.c_void_p, C.c_int]),
+    "ddn_fsk4_chain_get_m17_data_results": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_fsk4_chain_flush": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ddn_fsk4_chain_front_end": (C.c_void_p, [C.c_void_p]),
     "ddn_fsk4_chain_rx": (C.c_void_p, [C.c_void_p]),
@@ -694,6 +707,16 @@ class Fsk4ChainC:
     def set_edacs_mode(self, ea_mode, esk_mask):
         """ddn_fsk4_chain_set_edacs_mode: -fh (0, 0), -fH (0, 0xA0), -fe (1, 0), -fE (1, 0xA0)"""
         _check(lib().ddn_fsk4_chain_set_edacs_mode(self.h, ea_mode, esk_mask), "ddn_fsk4_chain_set_edacs_mode")
+
+    def m17_data_results(self):
+        """ddn_fsk4_chain_get_m17_data_results (DDN_FSK4_M17 chains only): packet and BERT frames of the last call"""
+        r = M17DataChainResults()
+        _check(lib().ddn_fsk4_chain_get_m17_data_results(self.h, C.byref(r)), "ddn_fsk4_chain_get_m17_data_results")
+        return r
+
+    def set_m17_packet_slots(self, max_packets):
+        """ddn_fsk4_chain_set_m17_packet_slots: completed packets stored per channel and call (1 .. 33, default 4), before the first run"""
+        _check(lib().ddn_fsk4_chain_set_m17_packet_slots(self.h, max_packets), "ddn_fsk4_chain_set_m17_packet_slots")
 
     @property
     def rx(self):

@@ -190,7 +190,11 @@ static int
 m17_alloc(ddn_fsk4_chain* c) {
     const size_t S = c->S;
     return alloc_rc(BUF(m17.lsf, S * 30) && BUF(m17.lsf_st, S) && BUF(m17.l6, S * 6) && BUF(m17.cnt, S) && BUF(m17.fp, S * 18) && BUF(m17.st, S)
-                      && BUF(m17.assembly, (size_t)c->B * 32) && BUF(m17.ll, S * 30) && BUF(m17.ll_st, S) && BUF(m17.cost, S));
+                      && BUF(m17.assembly, (size_t)c->B * 32) && BUF(m17.ll, S * 30) && BUF(m17.ll_st, S) && BUF(m17.cost, S)
+                      // packet and BERT frames; the carried state starts all zeros (= a stream's start)
+                      && BUF(m17.p26, S * 26) && BUF(m17.pf_st, S) && BUF(m17.p_cost, S) && BUF(m17.b25, S * 25) && BUF(m17.bf_st, S)
+                      && BUF(m17.data_state, (size_t)c->B * ddn_m17_data_state_bytes()) && BUF(m17.p_st, S) && BUF(m17.p_cnt, S)
+                      && BUF(m17.b_state, S * 8) && BUF(m17.n_packets, (size_t)c->B));
 }
 
 static int
@@ -204,7 +208,21 @@ m17_decode(ddn_fsk4_chain* c, int cur, int, hipStream_t st) {
                                      c->m17.fp, c->m17.st, st));
     DDN_TRY(ddn_m17_lich_assemble_batch(c->d_spat, c->d_ns, c->B, (size_t)c->myd, c->m17.lsf, c->m17.lsf_st, c->m17.l6, c->m17.cnt, c->m17.st,
                                         c->m17.assembly, c->m17.ll, c->m17.ll_st, st));
-    HIP_TRY(hipEventRecord(c->ev_reads, st));
+    // packet and BERT frames, then the walk that carries a packet and the BERT receiver across calls (this call's new records are
+    // what the next call's rows begin behind)
+    if (!c->m17.packet) { // (the packet slots: ddn_fsk4_chain_set_m17_packet_slots may change their number until the first run)
+        const size_t BP = (size_t)c->B * (size_t)c->m17.P;
+        DDN_TRY(alloc_rc(BUF(m17.packet, BP * 832) && BUF(m17.packet_len, BP) && BUF(m17.packet_ok, BP) && BUF(m17.packet_slot, BP)));
+    }
+    DDN_TRY(ddn_m17_pkt_decode_batch(rec, c->stride, c->d_cnt_full, c->d_spos, c->d_spat, c->d_ns, c->d_thr, c->B, (size_t)c->myd, c->m17.p26,
+                                     c->m17.pf_st, c->m17.p_cost, st));
+    DDN_TRY(ddn_m17_brt_decode_batch(rec, c->stride, c->d_cnt_full, c->d_spos, c->d_spat, c->d_ns, c->B, (size_t)c->myd, c->m17.b25,
+                                     c->m17.bf_st, st));
+    HIP_TRY(hipEventRecord(c->ev_reads, st)); // (the walk reads the sync lists too, but they are the decode stage's own copies)
+    DDN_TRY(ddn_m17_data_assemble_batch(c->d_spat, c->d_spos, c->d_ns, c->d_new[cur], c->B, (size_t)c->myd, c->m17.p26, c->m17.pf_st,
+                                        c->m17.b25, c->m17.bf_st, c->m17.data_state, c->m17.p_st, c->m17.p_cnt, c->m17.b_state,
+                                        c->m17.packet, c->m17.packet_len, c->m17.packet_ok, c->m17.packet_slot, c->m17.n_packets, c->m17.P,
+                                        st));
     return DDN_OK;
 }
 
@@ -474,6 +492,7 @@ ddn_fsk4_chain_create(const ddn_fsk4_chain_config* cfg, ddn_fsk4_chain** out) {
     c->n = cfg->samples_per_call;
     c->T = tr->T;
     c->myc = 16;
+    c->m17.P = 4;
     const int rc = fsk4_setup(c);
     if (rc != DDN_OK) {
         ddn_fsk4_chain_destroy(c);
@@ -741,6 +760,44 @@ ddn_fsk4_chain_get_dstar_results(ddn_fsk4_chain* c, ddn_dstar_chain_results* r) 
     r->d_sd_crc_ok = c->dstar.sok;
     r->d_sd_text = c->dstar.text;
     r->d_valid = c->dstar.vv;
+    return DDN_OK;
+}
+
+extern "C" int
+ddn_fsk4_chain_set_m17_packet_slots(ddn_fsk4_chain* c, int max_packets) {
+    if (!c || c->cfg.protocol != DDN_FSK4_M17 || c->step != 0 || max_packets < 1 || max_packets > 33) {
+        ddn_set_error("ddn_fsk4_chain_set_m17_packet_slots: an M17 chain before its first run, 1 .. 33 packet slots");
+        return DDN_EINVAL;
+    }
+    c->m17.P = max_packets;
+    return DDN_OK;
+}
+
+extern "C" int
+ddn_fsk4_chain_get_m17_data_results(ddn_fsk4_chain* c, ddn_m17_data_chain_results* r) {
+    if (!c || !r || c->cfg.protocol != DDN_FSK4_M17) {
+        ddn_set_error("ddn_fsk4_chain_get_m17_data_results: not an M17 chain");
+        return DDN_EINVAL;
+    }
+    memset(r, 0, sizeof(*r));
+    r->max_syncs = (size_t)c->myd;
+    r->max_packets = c->m17.P;
+    r->d_n_sync = c->d_ns;
+    r->d_sync_pos = c->d_spos;
+    r->d_sync_pat = c->d_spat;
+    r->d_pkt26 = c->m17.p26;
+    r->d_pkt_frame_status = c->m17.pf_st;
+    r->d_pkt_cost = c->m17.p_cost;
+    r->d_bits25 = c->m17.b25;
+    r->d_brt_frame_status = c->m17.bf_st;
+    r->d_pkt_status = c->m17.p_st;
+    r->d_pkt_count = c->m17.p_cnt;
+    r->d_brt_state = c->m17.b_state;
+    r->d_n_packets = c->m17.n_packets;
+    r->d_packet = c->m17.packet;
+    r->d_packet_app_len = c->m17.packet_len;
+    r->d_packet_crc_ok = c->m17.packet_ok;
+    r->d_packet_slot = c->m17.packet_slot;
     return DDN_OK;
 }
 

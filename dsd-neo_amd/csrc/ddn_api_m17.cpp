@@ -223,3 +223,110 @@ ddn_ysf_payload_decode_batch(const uint8_t* d_records10, size_t stride_symbols, 
     HIP_TRY(ef);
     return DDN_OK;
 }
+
+// ---- M17 packet and BERT frames (include/ddn_fsk4.h) --------------------------------------------------------------------------------------
+extern "C" int
+ddn_m17_pkt_decode_batch(const uint8_t* d_records10, size_t stride_symbols, const int32_t* d_counts, const int32_t* d_sync_pos,
+                         const uint8_t* d_sync_pat, const int32_t* d_n_sync, const float* d_sync_thr5, int n_channels, size_t max_syncs,
+                         uint8_t* d_pkt26, uint8_t* d_status, uint32_t* d_path_cost, void* hip_stream) {
+    if (!d_records10 || !d_counts || !d_sync_pos || !d_sync_pat || !d_n_sync || !d_sync_thr5 || !d_pkt26 || !d_status || n_channels <= 0
+        || max_syncs == 0 || max_syncs > (1u << 24) || stride_symbols == 0) {
+        ddn_set_error("ddn_m17_pkt_decode_batch: bad argument");
+        return DDN_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int lmax = (int)(stride_symbols / 192 + 1); // a packet frame takes 192 symbols
+    const size_t S = (size_t)n_channels * (size_t)lmax;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_cost = up(S * 420 * sizeof(uint16_t)), b_dec = up(S * 32), b_pc = up(S * sizeof(uint32_t)), b_slot = up(S * sizeof(int32_t)),
+                 b_want = up(S);
+    uint8_t* scratch = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&scratch, b_cost + b_dec + b_pc + b_slot + b_want, st));
+    uint16_t* cost = (uint16_t*)scratch;
+    uint8_t* dec = scratch + b_cost;
+    uint32_t* pc = (uint32_t*)(dec + b_dec);
+    int32_t* slot = (int32_t*)((uint8_t*)pc + b_pc);
+    uint8_t* want = (uint8_t*)slot + b_slot;
+    int rc = DDN_OK;
+    hipError_t e = hipMemsetAsync(d_status, 0, (size_t)n_channels * max_syncs, st);
+    if (e == hipSuccess) {
+        e = ddn_dev_m17_pkt_cost(d_records10, stride_symbols, d_counts, d_sync_pos, d_sync_pat, d_n_sync, d_sync_thr5, n_channels, (int)max_syncs,
+                                 lmax, cost, slot, want, st);
+    }
+    if (e == hipSuccess) { // (blocks of 16 slots none of which holds a packet frame are left alone)
+        rc = ddn_fec_viterbi_k5_batch_wanted(cost, S, 420, nullptr, 0, dec, 32, pc, want, st);
+    }
+    if (e == hipSuccess && rc == DDN_OK) {
+        e = ddn_dev_m17_pkt_finish(dec, 32, pc, slot, n_channels, lmax, (int)max_syncs, d_pkt26, d_status, d_path_cost, st);
+    }
+    const hipError_t ef = hipFreeAsync(scratch, st);
+    if (rc != DDN_OK) {
+        return rc;
+    }
+    HIP_TRY(e);
+    HIP_TRY(ef);
+    return DDN_OK;
+}
+
+extern "C" int
+ddn_m17_brt_decode_batch(const uint8_t* d_records10, size_t stride_symbols, const int32_t* d_counts, const int32_t* d_sync_pos,
+                         const uint8_t* d_sync_pat, const int32_t* d_n_sync, int n_channels, size_t max_syncs, uint8_t* d_bits25,
+                         uint8_t* d_status, void* hip_stream) {
+    if (!d_records10 || !d_counts || !d_sync_pos || !d_sync_pat || !d_n_sync || !d_bits25 || !d_status || n_channels <= 0 || max_syncs == 0
+        || max_syncs > (1u << 24) || stride_symbols == 0) {
+        ddn_set_error("ddn_m17_brt_decode_batch: bad argument");
+        return DDN_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int lmax = (int)(stride_symbols / 192 + 1); // a BERT frame takes 192 symbols
+    const size_t S = (size_t)n_channels * (size_t)lmax;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_sym = up(S * 402), b_dec = up(S * 25), b_slot = up(S * sizeof(int32_t)), b_want = up(S);
+    uint8_t* scratch = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&scratch, b_sym + b_dec + b_slot + b_want, st));
+    uint8_t* sym = scratch;
+    uint8_t* dec = sym + b_sym;
+    int32_t* slot = (int32_t*)(dec + b_dec);
+    uint8_t* want = (uint8_t*)slot + b_slot;
+    hipError_t e = hipMemsetAsync(d_status, 0, (size_t)n_channels * max_syncs, st);
+    if (e == hipSuccess) {
+        e = ddn_dev_m17_brt_bits(d_records10, stride_symbols, d_counts, d_sync_pos, d_sync_pat, d_n_sync, n_channels, (int)max_syncs, lmax, sym,
+                                 slot, want, st);
+    }
+    if (e == hipSuccess) { // 201 steps (197 bits + 4 flush), 197 bits chained back
+        e = ddn_dev_k5_nxdn_wanted(sym, nullptr, (int)S, 201, 197, nullptr, dec, 25, want, 1, st);
+    }
+    if (e == hipSuccess) {
+        e = ddn_dev_m17_brt_finish(dec, 25, slot, n_channels, lmax, (int)max_syncs, d_bits25, d_status, st);
+    }
+    const hipError_t ef = hipFreeAsync(scratch, st);
+    HIP_TRY(e);
+    HIP_TRY(ef);
+    return DDN_OK;
+}
+
+extern "C" size_t
+ddn_m17_data_state_bytes(void) {
+    return ddn_dev_m17_data_state_bytes();
+}
+
+extern "C" int
+ddn_m17_data_assemble_batch(const uint8_t* d_sync_pat, const int32_t* d_sync_pos, const int32_t* d_n_sync, const int32_t* d_advance,
+                            int n_channels, size_t max_syncs, const uint8_t* d_pkt26, const uint8_t* d_pkt_frame_status,
+                            const uint8_t* d_bits25, const uint8_t* d_brt_frame_status, void* d_state, uint8_t* d_pkt_status,
+                            uint8_t* d_pkt_count, int32_t* d_brt_state, uint8_t* d_packet, int32_t* d_packet_app_len,
+                            uint8_t* d_packet_crc_ok, int32_t* d_packet_slot, int32_t* d_n_packets, int max_packets, void* hip_stream) {
+    if (!d_sync_pat || !d_sync_pos || !d_n_sync || !d_pkt26 || !d_pkt_frame_status || !d_bits25 || !d_brt_frame_status || !d_state
+        || !d_pkt_status || !d_pkt_count || !d_brt_state || !d_packet || !d_packet_app_len || !d_packet_crc_ok || !d_packet_slot
+        || !d_n_packets || n_channels <= 0 || max_syncs == 0 || max_syncs > (1u << 24) || max_packets < 1 || max_packets > 33) {
+        ddn_set_error("ddn_m17_data_assemble_batch: bad argument");
+        return DDN_EINVAL;
+    }
+    // (the walk writes the slots of packet and BERT frames only)
+    HIP_TRY(hipMemsetAsync(d_pkt_status, 0, (size_t)n_channels * max_syncs, (hipStream_t)hip_stream));
+    HIP_TRY(hipMemsetAsync(d_pkt_count, 0, (size_t)n_channels * max_syncs, (hipStream_t)hip_stream));
+    HIP_TRY(ddn_dev_m17_data_walk(d_sync_pat, d_sync_pos, d_n_sync, d_advance, n_channels, (int)max_syncs, d_pkt26, d_pkt_frame_status,
+                                  d_bits25, d_brt_frame_status, d_state, d_pkt_status, d_pkt_count, d_brt_state, d_packet, d_packet_app_len,
+                                  d_packet_crc_ok, d_packet_slot, d_n_packets, max_packets, (hipStream_t)hip_stream));
+    return DDN_OK;
+}

@@ -73,6 +73,12 @@ struct ddn_fsk4_chain {
     struct { // M17: the frame decoders' slot arrays (ddn_m17_*_batch), the carried LICH assembly buffer
         uint8_t *lsf, *lsf_st, *l6, *cnt, *fp, *st, *assembly, *ll, *ll_st;
         uint32_t* cost;
+        // packet and BERT frames (ddn_m17_data.hip): the frame decoders' slot arrays, the state carried per channel, the walk's outputs
+        // per sync slot and - P slots per channel, made at the first run - per completed packet
+        int P;
+        uint8_t *p26, *pf_st, *b25, *bf_st, *data_state, *p_st, *p_cnt, *packet, *packet_ok;
+        uint32_t* p_cost;
+        int32_t *b_state, *n_packets, *packet_len, *packet_slot;
     } m17;
     struct { // YSF: the frame information channel of every decoded sync
         uint8_t *fich4, *st;

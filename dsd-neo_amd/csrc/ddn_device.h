@@ -495,6 +495,23 @@ hipError_t ddn_dev_m17_str_finish(const uint8_t* dec, int dec_stride, const int3
 hipError_t ddn_dev_m17_lich(const uint8_t* sync_pat, const int32_t* n_sync, int n_channels, int max_syncs, const uint8_t* lsf30,
                             const uint8_t* lsf_status, const uint8_t* lich6, const uint8_t* lich_cnt, const uint8_t* str_status,
                             uint8_t* asm30, uint8_t* lich_lsf30, uint8_t* lich_status, hipStream_t st);
+// M17 packet / BERT frames and the per-channel state behind them (ddn_m17_data.hip)
+size_t ddn_dev_m17_data_state_bytes(void);
+hipError_t ddn_dev_m17_pkt_cost(const uint8_t* rec, size_t stride, const int32_t* counts, const int32_t* sync_pos, const uint8_t* sync_pat,
+                                const int32_t* n_sync, const float* sync_thr, int n_channels, int max_syncs, int lmax, uint16_t* cost420,
+                                int32_t* slot_sync, uint8_t* slot_want, hipStream_t st);
+hipError_t ddn_dev_m17_pkt_finish(const uint8_t* dec, int dec_stride, const uint32_t* cost, const int32_t* slot_sync, int n_channels,
+                                  int lmax, int max_syncs, uint8_t* pkt26, uint8_t* status, uint32_t* path_cost, hipStream_t st);
+hipError_t ddn_dev_m17_brt_bits(const uint8_t* rec, size_t stride, const int32_t* counts, const int32_t* sync_pos, const uint8_t* sync_pat,
+                                const int32_t* n_sync, int n_channels, int max_syncs, int lmax, uint8_t* sym402, int32_t* slot_sync,
+                                uint8_t* slot_want, hipStream_t st);
+hipError_t ddn_dev_m17_brt_finish(const uint8_t* dec, int dec_stride, const int32_t* slot_sync, int n_channels, int lmax, int max_syncs,
+                                  uint8_t* bits25, uint8_t* status, hipStream_t st);
+hipError_t ddn_dev_m17_data_walk(const uint8_t* sync_pat, const int32_t* sync_pos, const int32_t* n_sync, const int32_t* advance,
+                                 int n_channels, int max_syncs, const uint8_t* pkt26, const uint8_t* pkt_frame_status,
+                                 const uint8_t* bits25, const uint8_t* brt_frame_status, void* state, uint8_t* pkt_status,
+                                 uint8_t* pkt_count, int32_t* brt_state, uint8_t* packet, int32_t* packet_app_len, uint8_t* packet_crc_ok,
+                                 int32_t* packet_slot, int32_t* n_packets, int max_packets, hipStream_t st);
 hipError_t ddn_dev_ysf_fich_cost(const uint8_t* rec, size_t stride, const int32_t* counts, const int32_t* sync_pos,
                                  const int32_t* n_sync, int n_channels, int max_syncs, int lmax, uint16_t* cost200,
                                  int32_t* slot_sync, hipStream_t st);

@@ -523,6 +523,38 @@ typedef struct ddn_edacs_chain_results { /* device pointers valid until the next
 int ddn_fsk4_chain_set_edacs_mode(ddn_fsk4_chain* c, int ea_mode, int esk_mask);
 int ddn_fsk4_chain_get_edacs_results(ddn_fsk4_chain* c, ddn_edacs_chain_results* out);
 
+/* ---- M17 packet mode and BERT (protocol DDN_FSK4_M17): behind the LSF, stream and LICH calls every M17 chain call also runs
+ * ddn_m17_pkt_decode_batch -> ddn_m17_brt_decode_batch -> ddn_m17_data_assemble_batch (include/ddn_fsk4.h); the packet buffer, the frame
+ * count, the BERT receiver and the end of the last lock are carried per channel across calls and through flush, so a packet of up to 33
+ * frames completes in the call that holds its last symbol.  A call stores max_packets completed packets per channel: 4, until
+ * ddn_fsk4_chain_set_m17_packet_slots asks for another number (1 .. 33) before the first run - any other value, a chain that has run,
+ * or another protocol is DDN_EINVAL.  ddn_fsk4_chain_get_m17_data_results refuses any other protocol (DDN_EINVAL);
+ * ddn_fsk4_chain_config and ddn_fsk4_chain_results keep their sizes. */
+typedef struct ddn_m17_data_chain_results { /* device pointers valid until the next run; S = n_channels * max_syncs sync slots */
+    size_t max_syncs;                  /* sync slots per channel */
+    int max_packets;                   /* packet slots per channel and call (P) */
+    const int32_t* d_n_sync;           /* [n_channels] syncs handed out in this call */
+    const int32_t* d_sync_pos;         /* [S] record index of each sync's last symbol in this call's rows (ddn_fsk4_chain_results) */
+    const uint8_t* d_sync_pat;         /* [S] 0 / 1 preamble, 2 / 3 EOT, 4 / 5 LSF, 6 / 7 BERT, 8 / 9 stream, 10 / 11 packet */
+    const uint8_t* d_pkt26;            /* [S][26] a packet frame's 25 chunk bytes + metadata byte */
+    const uint8_t* d_pkt_frame_status; /* [S] 1 = a packet frame decoded in this call */
+    const uint32_t* d_pkt_cost;        /* [S] its decoder's path cost */
+    const uint8_t* d_bits25;           /* [S][25] a BERT frame's 197 bits, most significant bit first */
+    const uint8_t* d_brt_frame_status; /* [S] 1 = a BERT frame decoded in this call */
+    const uint8_t* d_pkt_status;       /* [S] 0 none, 1 metadata invalid, 2 counter mismatch, 3 EOF byte count invalid, 4 chunk filed,
+                                          5 filed then frame count overflow, 6 final with a CRC mismatch, 7 final, CRC good */
+    const uint8_t* d_pkt_count;        /* [S] the frame count before a packet frame */
+    const int32_t* d_brt_state;        /* [S][8] {locked, lfsr, lock_count, window_bits, window_errors, total_bits, total_errors,
+                                          resyncs} after a BERT frame (other slots are not written) */
+    const int32_t* d_n_packets;        /* [n_channels] packets completed in this call (also those past max_packets) */
+    const uint8_t* d_packet;           /* [n_channels][P][832] the first P of them: total bytes (CRC included), zeros behind */
+    const int32_t* d_packet_app_len;   /* [n_channels][P] application bytes */
+    const uint8_t* d_packet_crc_ok;    /* [n_channels][P] */
+    const int32_t* d_packet_slot;      /* [n_channels][P] the sync slot of the frame that completed it */
+} ddn_m17_data_chain_results;
+int ddn_fsk4_chain_set_m17_packet_slots(ddn_fsk4_chain* c, int max_packets);
+int ddn_fsk4_chain_get_m17_data_results(ddn_fsk4_chain* c, ddn_m17_data_chain_results* out);
+
 /* ---- a mixed batch (BASELINE configs[3]): P25 Phase 1 + DMR + NXDN48 channel groups of one GPU, every receive loop with the
  * reference's handlers inside it; one stream per group inside the object, the groups' stages lined up (the three front ends, then the
  * three receive loops side by side), the frame FEC / voice stages on a fourth stream behind their loops so that the next call's

@@ -202,6 +202,50 @@ int ddn_ysf_payload_decode_batch(const uint8_t* d_records10, size_t stride_symbo
 int ddn_m17_lich_assemble_batch(const uint8_t* d_sync_pat, const int32_t* d_n_sync, int n_channels, size_t max_syncs, const uint8_t* d_lsf30,
                                 const uint8_t* d_lsf_status, const uint8_t* d_lich6, const uint8_t* d_lich_cnt, const uint8_t* d_str_status,
                                 uint8_t* d_assembly32, uint8_t* d_lich_lsf30, uint8_t* d_lich_status, void* hip_stream);
+/* ---- M17 packet and BERT frames behind the loop ------------------------------------------------------------------------------------------
+ * == processM17PKT() up to its checks (src/protocol/m17/m17.c:3076-3098) for every accepted packet sync (pattern 10 / 11) whose 184 payload
+ * symbols lie inside the call's records: soft symbols -> soft_symbol_to_viterbi_cost() against the thresholds the sync left (d_sync_thr5,
+ * as ddn_m17_lsf_decode_batch) -> de-randomise -> de-interleave -> de-puncture P3 to 420 costs, 0x7FFF where a bit was cut (:2991-3001) ->
+ * viterbi_decode -> its bytes 1 .. 26: d_pkt26 [B][max_syncs][26] = the 25 chunk bytes + the metadata byte.  d_status: 0 = not a packet
+ * sync, or the frame is not complete in this call; 1 = decoded.  d_path_cost (optional) = the decoder's path cost. */
+int ddn_m17_pkt_decode_batch(const uint8_t* d_records10, size_t stride_symbols, const int32_t* d_counts, const int32_t* d_sync_pos,
+                             const uint8_t* d_sync_pat, const int32_t* d_n_sync, const float* d_sync_thr5, int n_channels, size_t max_syncs,
+                             uint8_t* d_pkt26, uint8_t* d_status, uint32_t* d_path_cost, void* hip_stream);
+/* == processM17BRT() up to the receiver (:1325-1336; m17_decode_bert_payload_bits :1247-1276) for every accepted BERT sync (pattern 6 / 7)
+ * with a complete frame: hard dibits -> de-randomise -> de-interleave -> de-puncture P2 to 402 symbol values bit << 1, the cut bit reads 0
+ * (:1232-1245) -> CNXDNConvolution over 201 steps, 197 bits chained back: d_bits25 [B][max_syncs][25], most significant bit first, the last
+ * three bits zero.  d_status as above. */
+int ddn_m17_brt_decode_batch(const uint8_t* d_records10, size_t stride_symbols, const int32_t* d_counts, const int32_t* d_sync_pos,
+                             const uint8_t* d_sync_pat, const int32_t* d_n_sync, int n_channels, size_t max_syncs, uint8_t* d_bits25,
+                             uint8_t* d_status, void* hip_stream);
+/* What the reference does with those frames, in the order of the syncs of a call, on a state carried per channel from call to call
+ * (d_state: n_channels x ddn_m17_data_state_bytes() bytes of device memory, all zeros before a stream's first call):
+ *   a packet frame goes through processM17PKT()'s checks in their order (:3100-3150): the metadata byte (m17_packet_parse_metadata_byte,
+ *     m17_algorithms.c:367-386), the counter against the carried count, the EOF byte count (m17_packet_app_bytes_from_eof :336-353), the
+ *     25-byte copy at 25 x count, on EOF m17_pkt_finalize_eot (:3052-3074: CRC16 over the application bytes against the two behind them;
+ *     the packet is reported whatever the verdict, buffer and count cleared), else the overflow check and the increment; every rejection
+ *     clears buffer and count;
+ *   a BERT frame's 197 bits go through m17_prbs9_rx_push_bit (m17_algorithms.c:125-167; lock after 18 bits, 128-bit windows, resync above
+ *     18 errors in one);
+ *   an EOT marker (pattern 2 / 3) zeroes the count - not the buffer - and restarts the BERT receiver (dispatch_m17.c:39-50);
+ *   carrier loss (no_carrier_reset_m17_and_sample_buffers, src/engine/engine.c:2169-2184: buffer, count and BERT receiver) is applied at
+ *     the sync that follows it: the loop declares it at the 1800th hunted symbol without a sync, so at a sync whose position lies more
+ *     than 1800 symbols behind the last symbol of the previous lock (8 symbols behind a preamble sync, 184 behind any other).
+ * d_advance [n_channels] (NULL = zeros): by how many records the next call's rows begin behind this call's (a chain's new records of the
+ * call; single calls on fresh rows pass NULL) - it carries the end of the last lock into the next call's positions.
+ * d_pkt26 / d_pkt_frame_status, d_bits25 / d_brt_frame_status: the two calls above.  Out, per sync slot: d_pkt_status (0 none, 1 metadata
+ * invalid, 2 counter mismatch, 3 EOF byte count invalid, 4 chunk filed, 5 filed, then frame count overflow, 6 final, CRC mismatch, 7 final,
+ * CRC good), d_pkt_count = the count before a packet frame (0 elsewhere), d_brt_state [..][8] = {locked, lfsr, lock_count, window_bits,
+ * window_errors, total_bits, total_errors, resyncs} after a BERT frame (the slots of other syncs are not written).  Out, per channel and call: d_n_packets [B] = packets completed (every one, also
+ * those past max_packets, which are not stored - their slots still read 6 / 7), and for the first max_packets (1 .. 33) of them
+ * d_packet [B][max_packets][832] = bytes [0, end) of the reference's buffer at finalisation (end = 25 x count + the EOF value), zeros
+ * behind, d_packet_app_len, d_packet_crc_ok, d_packet_slot (the sync slot of the EOF frame). */
+size_t ddn_m17_data_state_bytes(void);
+int ddn_m17_data_assemble_batch(const uint8_t* d_sync_pat, const int32_t* d_sync_pos, const int32_t* d_n_sync, const int32_t* d_advance,
+                                int n_channels, size_t max_syncs, const uint8_t* d_pkt26, const uint8_t* d_pkt_frame_status,
+                                const uint8_t* d_bits25, const uint8_t* d_brt_frame_status, void* d_state, uint8_t* d_pkt_status,
+                                uint8_t* d_pkt_count, int32_t* d_brt_state, uint8_t* d_packet, int32_t* d_packet_app_len,
+                                uint8_t* d_packet_crc_ok, int32_t* d_packet_slot, int32_t* d_n_packets, int max_packets, void* hip_stream);
 int ddn_fsk4_rx_set_timing(ddn_fsk4_rx* b, int enable);
 int ddn_fsk4_rx_get_timing(ddn_fsk4_rx* b, float* ms2); /* {matched filter, receive loop} of the last run */
 

@@ -4,9 +4,11 @@ reference's --iq-replay log carries (NAC, DUID, TSBK opcodes with CRC status, LD
 voice-frame counts).  Everything between the capture file and the printed lines runs through the C-ABI: capture reader,
 front end, receive loop, framer gathers, BCH / trellis / CRC / Hamming / Reed-Solomon kernels.
 
-usage: python tools/decode_capture.py CAPTURE.iq[.json] [--lock SYMBOLS] [--max-frames N]
+usage: python tools/decode_capture.py CAPTURE.iq[.json] [--lock SYMBOLS] [--max-frames N] [--m17]
        --lock: in-frame symbols after a sync (default 840 = LDU-sized; 156 / 336 suit one- / three-block TSDU control
-               channels - dibits read outside the in-frame span carry no soft decisions)"""
+               channels - dibits read outside the in-frame span carry no soft decisions)
+       --m17:  read the capture as M17 (cu8 at 48 kHz) through the fsk4 chain object instead and print a line per completed packet:
+               application length, CRC verdict, protocol identifier and, for SMS (0x05), the text"""
 import argparse
 import ctypes as C
 import os
@@ -138,12 +140,99 @@ def decode(path, lock=840, max_frames=64, out=print):
     return lines
 
 
+M17_PROTOCOLS = {0x00: "RAW", 0x01: "AX.25", 0x02: "APRS", 0x03: "6LoWPAN", 0x04: "IPv4", 0x05: "SMS", 0x06: "Winlink", 0x07: "TLE"}  # M17 spec
+
+
+def m17_packet_protocol(app):
+    """the protocol identifier in front of a packet's application bytes (M17 specification, packet superframe: one byte below 0x80,
+    else a UTF-8 style sequence of two to four bytes, shortest form only, 21 bits at most) -> (identifier, its length), or None where it is malformed
+    (what m17_packet_protocol_decode() refuses, src/protocol/m17/m17_parse.c:580-632)"""
+    if len(app) == 0:
+        return None
+    b0 = int(app[0])
+    if b0 < 0x80:
+        return b0, 1
+    for mask, lead, need, low in ((0xE0, 0xC0, 2, 0x80), (0xF0, 0xE0, 3, 0x800), (0xF8, 0xF0, 4, 0x10000)):
+        if (b0 & mask) == lead:
+            if len(app) < need or any((int(b) & 0xC0) != 0x80 for b in app[1:need]):
+                return None
+            v = b0 & (~mask & 0xFF)
+            for b in app[1:need]:
+                v = (v << 6) | (int(b) & 0x3F)
+            return (v, need) if low <= v <= 0x1FFFFF else None
+    return None
+
+
+def m17_packet_line(app, crc_ok):
+    """one line per completed packet"""
+    text = "packet: %3d application bytes, CRC %s" % (len(app), "ok" if crc_ok else "ERR")
+    proto = m17_packet_protocol(app)
+    if proto is None:
+        return text + ", protocol: invalid"
+    ident, used = proto
+    text += ", protocol %s (0x%02X)" % (M17_PROTOCOLS.get(ident, "reserved / unknown"), ident)
+    if ident == 0x05:
+        text += ': "%s"' % bytes(bytearray(int(b) for b in app[used:])).split(b"\x00")[0].decode("utf-8", "replace")
+    return text
+
+
+def decode_m17(path, out=print):
+    """the capture through ddn_fsk4_chain (protocol M17) in calls of one second + the flush -> a line per completed packet"""
+    import numpy as np
+    import ddn
+    l = ddn.lib()
+    paths = (C.c_char_p * 1)(path.encode())
+    buf, n = C.c_void_p(), C.c_size_t()
+    info = (C.c_uint8 * 8192)()
+    rc = l.ddn_iq_load_batch(paths, 1, C.byref(buf), C.byref(n), info)
+    if rc != 0:
+        raise SystemExit("cannot open capture (%d): %s" % (rc, l.ddn_last_error().decode()))
+    fmt, rate, base_dec, _, demod_rate = np.frombuffer(bytes(info[:24]), np.uint32)[1:6]
+    if int(fmt) != 1 or int(demod_rate) != 48000 or int(base_dec) != 1:
+        raise SystemExit("--m17 takes cu8 captures at 48 kHz (format %d, %d Hz, base_decimation %d)" % (fmt, demod_rate, base_dec))
+    host = np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_uint8)), (n.value * 2,)).copy().reshape(1, -1, 2)
+    l.ddn_iq_free(buf)
+    per = 48000
+    calls = -(-host.shape[1] // per)
+    pad = np.full((1, calls * per, 2), 127, np.uint8)
+    pad[:, :host.shape[1]] = host
+    ch = ddn.Fsk4ChainC(1, per, ddn.FSK4_M17, rf_mod=0, handlers=0, vocoder=0)
+    ch.set_m17_packet_slots(33)
+    lines = []
+
+    def take():
+        d = ch.m17_data_results()
+        P = int(d.max_packets)
+        k = min(int(ch.fetch(d.d_n_packets, np.int32, (1,))[0]), P)
+        by, ln, ok = ch.fetch(d.d_packet, np.uint8, (1, P, 832)), ch.fetch(d.d_packet_app_len, np.int32, (1, P)), ch.fetch(d.d_packet_crc_ok, np.uint8, (1, P))
+        for j in range(k):
+            lines.append(m17_packet_line(by[0, j, :int(ln[0, j])], int(ok[0, j])))
+
+    for k in range(calls):
+        part = np.ascontiguousarray(pad[:, k * per:(k + 1) * per])
+        p = C.c_void_p()
+        assert l.ddn_device_alloc(part.nbytes, C.byref(p)) == 0 and l.ddn_device_upload(p, part.ctypes.data, part.nbytes) == 0
+        ch.run(p)
+        take()
+        l.ddn_device_free(p)
+    ch.flush()
+    take()
+    ch.close()
+    for t in lines:
+        out(t)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("capture")
     ap.add_argument("--lock", type=int, default=840)
     ap.add_argument("--max-frames", type=int, default=64)
+    ap.add_argument("--m17", action="store_true")
     a = ap.parse_args()
+    if a.m17:
+        decode_m17(a.capture)
+        return
     decode(a.capture, a.lock, a.max_frames)
 
 
