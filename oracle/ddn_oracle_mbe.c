@@ -671,13 +671,13 @@ om_process(int codec, const ddn_mbe_tables* T, const uint8_t* bits, const int32_
         enhance(cur);
         synthesize(pcm, cur, enh, seed, frame_no);
         *enh = *cur;
-        cur->un = prev->un = enh->un = un + 1;
+        cur->un = prev->un = enh->un = (int)((uint32_t)un + 1u); /* the counter wraps as the device's uint32 does */
     } else {
         const int un = cur->un;
         flags |= MBE_PROCESS_FLAG_MUTE;
         memset(pcm, 0, sizeof(float) * 160);
         om_init_parms(cur, prev, enh);
-        cur->un = prev->un = enh->un = un + 1;
+        cur->un = prev->un = enh->un = (int)((uint32_t)un + 1u); /* the counter wraps as the device's uint32 does */
     }
     if (res_out) {
         res_out[0] = (int32_t)flags;

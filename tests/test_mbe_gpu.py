@@ -164,6 +164,41 @@ def test_imbe_invalid_fundamental_repeats_three_times_then_mutes(built):
         assert mbe.parms_equal(c, o.cur[s]) and mbe.parms_equal(p, o.prev[s]) and mbe.parms_equal(e, o.enh[s]), s
 
 
+@pytest.mark.parametrize("codec", [ddn.MBE_IMBE, ddn.MBE_AMBE])
+def test_repeat_counter_of_a_set_state_follows_prev(built, codec):
+    """ddn_mbe_batch_set_state does not promise cur.repeat == prev.repeat (a migrated call): a repeated frame counts from the
+    copied previous frame's repeat, as mbe_useLastMbeParms + repeat++ does - with cur.repeat = 2 and prev.repeat = 0 set, four
+    repeat frames give repeat 1, 2, 3 (synthesized) and then the mute; flags, PCM and state equal the restatement bit for bit"""
+    rng = np.random.default_rng(91 + codec)
+    S = 3
+    gen = mbe.random_imbe_bits if codec == ddn.MBE_IMBE else mbe.random_ambe_bits
+    o = mbe.OracleVocoder(codec, S)
+    g = GpuVocoder(codec, S)
+    first = gen(rng, (S, 2))
+    want_pcm, _, rc = o.run(first)
+    got_pcm, _ = g.run(first)
+    assert rc == 0 and np.array_equal(got_pcm.view(np.uint32), want_pcm.view(np.uint32))
+    for s in range(S):
+        c, p, e = g.state(s)
+        c.repeat, p.repeat = 2, 0
+        assert ddn.lib().ddn_mbe_batch_set_state(g.h, s, C.byref(c), C.byref(p), C.byref(e)) == 0
+        o.cur[s].repeat, o.prev[s].repeat = 2, 0
+    bits = gen(rng, (S, 4))
+    res_in = np.zeros((S, 4, 5), np.int32)
+    res_in[..., 0] = 1
+    res_in[..., 3] = res_in[..., 4] = 6 if codec == ddn.MBE_IMBE else 4
+    want_pcm, want_res, rc = o.run(bits, res_in)
+    got_pcm, got_res = g.run(bits, res_in)
+    assert rc == 0 and np.array_equal(got_res, want_res)
+    assert np.array_equal(got_pcm.view(np.uint32), want_pcm.view(np.uint32))
+    REPEAT, MUTE = 0x8, 0x10
+    for s in range(S):
+        assert [int(f) & 0x18 for f in got_res[s, :, 0]] == [REPEAT, REPEAT, REPEAT, REPEAT | MUTE]
+        assert all(np.abs(got_pcm[s, k]).max() > 0 for k in range(3)) and np.all(got_pcm[s, 3] == 0)
+        c, p, e = g.state(s)
+        assert mbe.parms_equal(c, o.cur[s]) and mbe.parms_equal(p, o.prev[s]) and mbe.parms_equal(e, o.enh[s]), s
+
+
 def test_c5_shape_8192_frames_properties(built):
     """BASELINE configs[4] / SURVEY §8d C5: 8192 voice frames as 64 talk paths x 128 frames.  A sample of talk paths is
     compared with the restatement; the whole batch is checked through size-independent properties: a talk path's output
