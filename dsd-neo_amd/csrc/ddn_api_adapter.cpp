@@ -142,7 +142,10 @@ op25_gardner_cc(struct demod_state* s) {
         return;
     }
     const int sps = s->ted_sps > 0 ? s->ted_sps : 5;
-    const int sym_rate = s->symbol_rate_hz > 0 ? s->symbol_rate_hz : 4800;
+    // the gain rule goes by the rate the reference derives (cqpsk_symbol_rate_hz, src/dsp/costas.cpp:135-141): rate_out over the
+    // integer sps, rounded; a state without rate_out keeps the configured symbol rate
+    const int sym_rate = (s->rate_out > 0 && s->ted_sps > 0) ? (s->rate_out + sps / 2) / sps
+                                                             : (s->symbol_rate_hz > 0 ? s->symbol_rate_hz : 4800);
     const int key[2] = {sps, sym_rate};
     if (!a->ted || memcmp(key, a->ted_key, sizeof(key)) != 0 || a->ted_gain != s->ted_gain) {
         if (a->ted) {

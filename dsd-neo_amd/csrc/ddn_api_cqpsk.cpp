@@ -97,6 +97,10 @@ ddn_cqpsk_batch_create(const ddn_cqpsk_config* cfg, ddn_cqpsk_batch** out) {
         ddn_set_error("channel LPF design failed for rate %d profile %d", cfg->sample_rate_hz, cfg->lpf_profile);
         return DDN_ERANGE;
     }
+    // the Gardner stage picks its gain from the symbol rate the reference derives from the output rate and the integer
+    // sps, rounded to nearest (cqpsk_symbol_rate_hz, src/dsp/costas.cpp:135-141) - not from the configured one: 12000 /
+    // 4800 Hz is sps 2 and 6000 sym/s there, on the 0.018 side of the 5500 threshold
+    const int ted_rate_hz = (cfg->sample_rate_hz + b->sps / 2) / b->sps;
     b->fll_nt = ddn_design_fll_band_edge(b->sps, b->fll_taps, &b->fll_alpha, &b->fll_beta);
     const size_t B = (size_t)cfg->n_channels;
     if (hipMalloc(&b->d_taps, sizeof(float) * (DDN_MAX_TAPS + 1)) != hipSuccess
@@ -108,7 +112,7 @@ ddn_cqpsk_batch_create(const ddn_cqpsk_config* cfg, ddn_cqpsk_batch** out) {
         || hipMalloc(&b->d_cnt, sizeof(int) * B) != hipSuccess
         || (b->taps_len >= 3
             && hipMemcpy(b->d_taps, b->taps, sizeof(float) * (size_t)b->taps_len, hipMemcpyHostToDevice) != hipSuccess)
-        || ddn_ted_batch_create(cfg->n_channels, b->sps, cfg->symbol_rate_hz, cfg->ted_gain, &b->ted) != DDN_OK
+        || ddn_ted_batch_create(cfg->n_channels, b->sps, ted_rate_hz, cfg->ted_gain, &b->ted) != DDN_OK
         || ddn_ted_batch_set_block_len(b->ted, (size_t)cfg->block_len) != DDN_OK
         || cq_fill(b, nullptr) != DDN_OK || hipDeviceSynchronize() != hipSuccess) {
         ddn_set_error("ddn_cqpsk_batch_create: device allocation failed");

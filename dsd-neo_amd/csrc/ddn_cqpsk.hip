@@ -454,11 +454,11 @@ k_cqpsk_agc_fll(const f2* __restrict__ in, long n, size_t stride, int n_channels
     }
 }
 
-// Register-resident variant for the tap counts in use (2 sps + 1 = 9, 11, 21).  The per-sample feedback loop issues its
+// Register-resident variant for the tap counts in use (2 sps + 1 = 9, 11, 17, 21).  The per-sample feedback loop issues its
 // instructions in order, so what limits it is the LDS round trips inside the loop (delay-line write -> read, shuffles),
 // not the FLOPs: here the delay line is a circular buffer in REGISTERS - the sample loop is unrolled by NT so the write
 // slot and every tap's read slot are compile-time register names - the four accumulators are exchanged with DPP
-// quad-permutes (VALU, no LDS), and a tile holds a whole number of NT-sample chunks (TS = 3 NT or 2 NT) so the circular
+// quad-permutes (VALU, no LDS), and a tile holds a whole number of NT-sample chunks (TS = 3 NT) so the circular
 // alignment survives tile boundaries; only the last tile of a call can end mid-chunk, and the carried state stores the
 // delay line oldest-first so the next call starts aligned again.
 // (round 6) The loop wave is bound by its own instruction stream - one wavefront issues a vector instruction every ~4.7 cycles and

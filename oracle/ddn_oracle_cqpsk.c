@@ -394,7 +394,10 @@ void
 orc_cqpsk_fe_init(orc_cqpsk_fe* fe, int rate_hz, int symbol_rate_hz, int profile, int lpf_enable, float ted_gain) {
     memset(fe, 0, sizeof(*fe));
     fe->taps_len = lpf_enable ? orc_channel_lpf_design(rate_hz, profile, fe->taps, ORC_MAX_TAPS) : 0;
-    orc_cqpsk_init(&fe->chain, symbol_rate_hz > 0 ? rate_hz / symbol_rate_hz : 5, symbol_rate_hz, ted_gain);
+    /* the Gardner gain goes by the symbol rate the reference derives from the rate and the integer sps
+     * (cqpsk_symbol_rate_hz, src/dsp/costas.cpp:135-141), which is the configured one only where the two divide */
+    const int sps = symbol_rate_hz > 0 ? rate_hz / symbol_rate_hz : 5;
+    orc_cqpsk_init(&fe->chain, sps, sps > 0 ? (rate_hz + sps / 2) / sps : 4800, ted_gain);
 }
 
 /* scratch >= 4 * block_len floats; returns symbols written */

@@ -502,6 +502,7 @@ class OracleCqpskFe:
         o.orc_cqpsk_fe_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]
         o.orc_cqpsk_fe_run_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p]
         o.orc_cqpsk_fe_run_f32.restype = C.c_long
+        o.orc_cqpsk_fe_get_state.argtypes = [C.c_void_p, C.c_void_p]
         self.o = o
         self.st = C.create_string_buffer(o.orc_cqpsk_fe_sizeof())
         o.orc_cqpsk_fe_init(self.st, rate, sym_rate, profile, lpf_enable, ted_gain)
@@ -514,24 +515,60 @@ class OracleCqpskFe:
         k = self.o.orc_cqpsk_fe_run_f32(self.st, iq.ctypes.data, n, block_len, out.ctypes.data, scr.ctypes.data)
         return out[:k].copy()
 
+    def state(self):
+        """float32 [8] = agc_avg, fll.freq, fll.phase, costas.phase, costas.freq, costas.error_smooth, ted.mu, ted.omega"""
+        s = np.zeros(8, np.float32)
+        self.o.orc_cqpsk_fe_get_state(self.st, s.ctypes.data)
+        return s
+
+
+class RefCqpskFe:
+    """full_demod(cqpsk_enable) of the compiled reference, one demod_state kept across run() calls (each call = consecutive blocks of
+    block_len samples and a shorter last one, like OracleCqpskFe.run)"""
+
+    def __init__(self, rate=24000, sym_rate=4800, profile=5, lpf_enable=1):
+        r = ref()
+        r.refh_cqpsk_create.restype = C.c_void_p
+        r.refh_cqpsk_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        r.refh_cqpsk_run_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long]
+        r.refh_cqpsk_run_f32.restype = C.c_long
+        r.refh_cqpsk_get_state.argtypes = [C.c_void_p, C.c_void_p]
+        r.refh_fe_destroy.argtypes = [C.c_void_p]
+        self.r = r
+        self.h = r.refh_cqpsk_create(rate, sym_rate, profile, lpf_enable)
+        assert self.h
+
+    def run(self, iq, block_len):
+        iq = np.ascontiguousarray(iq, np.float32)
+        n = iq.shape[0]
+        out = np.zeros(n + 16, np.float32)
+        k = self.r.refh_cqpsk_run_f32(self.h, iq.ctypes.data, n, block_len, out.ctypes.data, len(out))
+        return out[:k].copy()
+
+    def state(self):
+        """the same eight words as OracleCqpskFe.state()"""
+        s = np.zeros(8, np.float32)
+        self.r.refh_cqpsk_get_state(self.h, s.ctypes.data)
+        return s
+
+    def close(self):
+        if self.h:
+            self.r.refh_fe_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 def ref_cqpsk_f32(iq, block_len, rate=24000, sym_rate=4800, profile=5, lpf=1):
-    r = ref()
-    r.refh_cqpsk_create.restype = C.c_void_p
-    r.refh_cqpsk_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-    r.refh_cqpsk_run_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long]
-    r.refh_cqpsk_run_f32.restype = C.c_long
-    r.refh_cqpsk_get_state.argtypes = [C.c_void_p, C.c_void_p]
-    r.refh_fe_destroy.argtypes = [C.c_void_p]
-    iq = np.ascontiguousarray(iq, np.float32)
-    n = iq.shape[0]
-    h = r.refh_cqpsk_create(rate, sym_rate, profile, lpf)
-    out = np.zeros(n + 16, np.float32)
-    k = r.refh_cqpsk_run_f32(h, iq.ctypes.data, n, block_len, out.ctypes.data, len(out))
-    st = np.zeros(8, np.float32)
-    r.refh_cqpsk_get_state(h, st.ctypes.data)
-    r.refh_fe_destroy(h)
-    return out[:k].copy(), st
+    fe = RefCqpskFe(rate, sym_rate, profile, lpf)
+    out = fe.run(iq, block_len)
+    st = fe.state()
+    fe.close()
+    return out, st
 
 
 # ---- IMBE de-interleave (oracle/ddn_oracle_block.c; reference harness refh_imbe_deinterleave) --------------------------

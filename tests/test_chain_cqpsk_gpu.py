@@ -11,6 +11,7 @@ import pytest
 import chain_stream
 import ddn
 import orc
+from chain_cqpsk_stream import CARRY, SHORT_CALLS, oracle_stream, symbols_per_call
 from conftest import golden
 
 pytestmark = pytest.mark.gpu
@@ -40,15 +41,6 @@ def run_chain(iq, n_call):
     col.take()
     ch.close()
     return col, n_total
-
-
-def oracle_stream(iq, n_total, n_call):
-    x = ((iq[:n_total].astype(np.float32) - 127.5) * np.float32(1.0 / 127.5)).astype(np.float32)
-    fe = orc.OracleCqpskFe(rate=48000)          # a call = consecutive full_demod() blocks of 8192 + a shorter last one, like the chain's
-    sym = np.concatenate([fe.run(x[k:k + n_call], 8192) for k in range(0, n_total, n_call)])
-    rx = orc.OracleCqRx(orc.CQ_P25P1)
-    rec, fl = rx.run(sym)
-    return sym, rec, fl, rx.events.rows(), rx.events.data()
 
 
 def check_stream(col, sym, rec, fl, rows, data):
@@ -89,6 +81,33 @@ def test_control_channel_capture_to_tsbk_payloads(built, n_call):
     assert len(net) >= 2       # "WACN: 92065; SYS: 0D5"
     for b in net:
         assert ((int(b[3]) << 12) | (int(b[4]) << 4) | (int(b[5]) >> 4), ((int(b[5]) & 0xF) << 8) | int(b[6])) == (0x92065, 0x0D5)
+
+
+@pytest.mark.parametrize("name,n_call", SHORT_CALLS)
+def test_short_calls_decode_every_frame_once(built, name, n_call):
+    """the carried records, the carried sync list and the decode stage at calls that bring a third of the carry, about 819 records, and
+    959 - 961 of them: every sync waits for records of later calls, and is still decoded exactly once, whole, equal to the whole-stream
+    oracle (check_stream)"""
+    iq = np.ascontiguousarray(golden(name)["iq"])
+    col, n_total = run_chain(iq, n_call)
+    assert col.ch.T == CARRY
+    check_stream(col, *oracle_stream(iq, n_total, n_call))
+    want_new = symbols_per_call(iq, n_total, n_call)
+    for c in range(3):
+        new = np.array([len(r) for r in col.rec[c][:-1]])               # (the last entry is the flush's)
+        assert np.array_equal(new, want_new), (c, new, want_new)
+        if n_call == 3201:
+            assert new.max() < CARRY                                    # no call brought as many records as the carry holds
+        if n_call == 9600:
+            assert len(set(new.tolist()) & {CARRY - 1, CARRY, CARRY + 1}) >= 2
+    good = [f for _, f in sorted(col.frames[0].items()) if f["nid"][0] > 0]
+    assert len(good) >= 6
+    if "_vc" in name:
+        ldus = [f for f in good if f["nid"][2] in (5, 10)]
+        assert len(ldus) >= 2 and all(int(f["nid"][1]) == 0x106 for f in ldus)
+        assert all(f["rs1s"] == 0 for f in ldus if f["nid"][2] == 5) and all(f["rs2s"] == 0 for f in ldus if f["nid"][2] == 10)
+        pcm = np.concatenate([v[4] for v in col.voice[0]])
+        assert len(col.voice[0]) >= 18 and float(np.abs(pcm).sum()) > 0
 
 
 def test_simulcast_capture_grant_update(built):

@@ -15,11 +15,7 @@ def _oracle(iq, rate, blk, lpf, splits):
     for c in range(iq.shape[0]):
         fe = orc.OracleCqpskFe(rate=rate, lpf_enable=lpf)
         parts = [fe.run(iq[c, a:b], blk) for a, b in zip(splits[:-1], splits[1:])]
-        s = np.zeros(8, np.float32)
-        import ctypes as C
-        fe.o.orc_cqpsk_fe_get_state.argtypes = [C.c_void_p, C.c_void_p]
-        fe.o.orc_cqpsk_fe_get_state(fe.st, s.ctypes.data)
-        out.append((parts, s))
+        out.append((parts, fe.state()))
     return out
 
 

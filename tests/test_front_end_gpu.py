@@ -359,6 +359,25 @@ def test_single_stream_adapter_full_demod_and_gardner(built):
             check(blk.reshape(-1)[:2 * len(want)], want.reshape(-1), exact=True)
         pos += ln
     l.ddn_demod_state_release(C.byref(s3))
+    # --- with rate_out set the gain rule goes by (rate_out + sps / 2) / sps, as the reference's: 12000 Hz at sps 2 is 6000 sym/s (the
+    # 0.018 gain once 240 symbols have locked), whatever symbol_rate_hz says
+    sig2 = orc.synth_dqpsk_f32(0, 1, 900, 2)[0]
+    ted6, ted48 = orc.OracleTed(2, 6000), orc.OracleTed(2, 4800)
+    s4 = ddn.DemodState(cqpsk_enable=1, ted_sps=2, symbol_rate_hz=4800, rate_out=12000)
+    pos, switched = 0, False
+    for ln in (600, 600, 560):
+        blk = np.ascontiguousarray(sig2[pos:pos + ln]).copy()
+        keep = blk.copy()
+        s4.lowpassed = blk.ctypes.data_as(C.POINTER(C.c_float))
+        s4.lp_len = 2 * ln
+        l.op25_gardner_cc(C.byref(s4))
+        want, other = ted6.block(keep), ted48.block(keep)
+        assert s4.lp_len == 2 * len(want)
+        check(blk.reshape(-1)[:2 * len(want)], want.reshape(-1), exact=True)
+        switched |= want.shape != other.shape or not np.array_equal(want.view(np.uint32), other.view(np.uint32))
+        pos += ln
+    assert switched
+    l.ddn_demod_state_release(C.byref(s4))
 
 
 @pytest.mark.parametrize("counts", [(21, 19, 10), (5, 30), (16, 16, 16), (1, 1, 45)])
