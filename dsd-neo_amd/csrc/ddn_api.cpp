@@ -13,6 +13,7 @@
 #include <cstring>
 #include <new>
 
+#include "ddn_api_util.h"
 #include "ddn_device.h"
 
 static thread_local char g_err[512] = "";
@@ -33,16 +34,6 @@ ddn_last_error(void) {
 extern "C" const char*
 ddn_version(void) {
     return "dsdneo-hip 0.1 (gfx950)";
-}
-
-static int
-taps_have_zero(const float* taps, int n) {
-    for (int i = 0; i < n; i++) {
-        if (taps[i] == 0.0f) {
-            return 1;
-        }
-    }
-    return 0;
 }
 
 // HIP_TRY for the front end, whose create is the first call to touch the runtime: an insufficient driver is DDN_ENODEV as well
@@ -92,17 +83,6 @@ struct ddn_batch {
     size_t lpf_cap;
 };
 
-static int
-ensure_device() {
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) {
-        ddn_set_error("no HIP device available (%s)", e == hipSuccess ? "count=0" : hipGetErrorString(e));
-        return DDN_ENODEV;
-    }
-    return DDN_OK;
-}
-
 extern "C" int
 ddn_batch_create(const ddn_front_end_config* cfg, ddn_batch** out) {
     if (!cfg || !out || cfg->n_channels <= 0 || cfg->sample_rate_hz <= 0) {
@@ -113,10 +93,8 @@ ddn_batch_create(const ddn_front_end_config* cfg, ddn_batch** out) {
         ddn_set_error("ddn_batch_create: unknown input_format %d", cfg->input_format);
         return DDN_EINVAL;
     }
-    int rc = ensure_device();
-    if (rc != DDN_OK) {
-        return rc;
-    }
+    DDN_TRY(ddn_have_device());
+    int rc;
     ddn_batch* b = new (std::nothrow) ddn_batch();
     if (!b) {
         return DDN_ENOMEM;
@@ -412,12 +390,14 @@ ddn_front_end_run_segments(ddn_batch* b, const void* const* d_iq, size_t n, floa
     return DDN_OK;
 }
 
+static int
+check_front_end_run(const char* who, const ddn_batch* b, const void* iq, const float* disc) {
+    return (b && iq && disc) ? DDN_OK : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_front_end_run(ddn_batch* b, const void* d_iq, size_t n, float* d_disc, void* hip_stream) {
-    if (!b || !d_iq || !d_disc) {
-        ddn_set_error("ddn_front_end_run: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_front_end_run(__func__, b, d_iq, d_disc));
     if (n == 0) {
         return DDN_OK;
     }
@@ -551,9 +531,7 @@ ddn_front_end_run(ddn_batch* b, const void* d_iq, size_t n, float* d_disc, void*
 
 extern "C" int
 ddn_front_end_run_host(ddn_batch* b, const void* h_iq, size_t n, float* h_disc) {
-    if (!b || !h_iq || !h_disc) {
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_front_end_run(__func__, b, h_iq, h_disc));
     if (n == 0) {
         return DDN_OK;
     }

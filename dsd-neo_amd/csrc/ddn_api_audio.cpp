@@ -16,38 +16,28 @@ effective_gain(float audio_gain, int algid_0x21) { // agf_effective_gain(), src/
     return gain;
 }
 
+static int
+check_agf(const char* who, const float* pcm, int n_streams, int n_frames, const float* aout_gain) {
+    return (pcm && aout_gain && n_streams > 0 && n_frames >= 0) ? DDN_OK : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_audio_agf_batch(float* d_pcm, int n_streams, int n_frames, float audio_gain, int algid_0x21, float* d_aout_gain,
                     void* hip_stream) {
-    if (!d_pcm || !d_aout_gain || n_streams <= 0 || n_frames < 0) {
-        ddn_set_error("ddn_audio_agf_batch: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_agf(__func__, d_pcm, n_streams, n_frames, d_aout_gain));
     HIP_TRY(ddn_dev_agf(d_pcm, n_streams, n_frames, effective_gain(audio_gain, algid_0x21), d_aout_gain, (hipStream_t)hip_stream));
     return DDN_OK;
 }
 
 extern "C" int
 ddn_audio_agf_host(float* pcm, int n_streams, int n_frames, float audio_gain, int algid_0x21, float* aout_gain) {
-    if (!pcm || !aout_gain || n_streams <= 0 || n_frames < 0) {
-        return DDN_EINVAL;
-    }
-    const size_t np = (size_t)n_streams * (size_t)n_frames * 160;
-    float *d_p = nullptr, *d_g = nullptr;
-    int rc = DDN_OK;
-    if (hipMalloc(&d_p, np * 4 + 4) != hipSuccess || hipMalloc(&d_g, (size_t)n_streams * 4) != hipSuccess) {
-        ddn_set_error("ddn_audio_agf_host: device allocation failed (no device?)");
-        rc = DDN_ENODEV;
-    } else if (hipMemcpy(d_p, pcm, np * 4, hipMemcpyHostToDevice) != hipSuccess
-               || hipMemcpy(d_g, aout_gain, (size_t)n_streams * 4, hipMemcpyHostToDevice) != hipSuccess
-               || ddn_dev_agf(d_p, n_streams, n_frames, effective_gain(audio_gain, algid_0x21), d_g, nullptr) != hipSuccess
-               || hipMemcpy(pcm, d_p, np * 4, hipMemcpyDeviceToHost) != hipSuccess
-               || hipMemcpy(aout_gain, d_g, (size_t)n_streams * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-        rc = DDN_EHIP;
-    }
-    (void)hipFree(d_p);
-    (void)hipFree(d_g);
-    return rc;
+    DDN_TRY(check_agf(__func__, pcm, n_streams, n_frames, aout_gain));
+    DdnStaged s;
+    float* p = s.inout(pcm, (size_t)n_streams * (size_t)n_frames * 160 * 4);
+    float* g = s.inout(aout_gain, (size_t)n_streams * 4);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_audio_agf_batch(p, n_streams, n_frames, audio_gain, algid_0x21, g, nullptr));
+    return s.finish();
 }
 
 // drop-in shape of agf() for one talk path: the caller's aout_gain travels as a plain float (the reference keeps it in dsd_state)
@@ -78,13 +68,16 @@ ddn_audio_s16_state_init(float* state32, int n_streams) {
     return DDN_OK;
 }
 
+static int
+check_s16(const char* who, const float* pcm, int n_streams, int n_frames, int use_agsm, const int16_t* out, const float* state32,
+          const float* gain_a) {
+    return (pcm && out && state32 && (!use_agsm || gain_a) && n_streams > 0 && n_frames >= 0) ? DDN_OK : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_audio_s16_batch(const float* d_pcm, int n_streams, int n_frames, float audio_gain, int use_hpf_d, int use_agsm,
                     int16_t* d_out, float* d_state32, float* d_gain_a, void* hip_stream) {
-    if (!d_pcm || !d_out || !d_state32 || (use_agsm && !d_gain_a) || n_streams <= 0 || n_frames < 0) {
-        ddn_set_error("ddn_audio_s16_batch: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_s16(__func__, d_pcm, n_streams, n_frames, use_agsm, d_out, d_state32, d_gain_a));
     HIP_TRY(ddn_dev_audio_s16(d_pcm, n_streams, n_frames, audio_gain, use_hpf_d, use_agsm, hpf_d_coef(), d_out, d_state32,
                               d_gain_a, (hipStream_t)hip_stream));
     return DDN_OK;
@@ -93,30 +86,14 @@ ddn_audio_s16_batch(const float* d_pcm, int n_streams, int n_frames, float audio
 extern "C" int
 ddn_audio_s16_host(const float* pcm, int n_streams, int n_frames, float audio_gain, int use_hpf_d, int use_agsm, int16_t* out,
                    float* state32, float* gain_a) {
-    if (!pcm || !out || !state32 || (use_agsm && !gain_a) || n_streams <= 0 || n_frames < 0) {
-        return DDN_EINVAL;
-    }
-    const size_t np = (size_t)n_streams * (size_t)n_frames * 160, ns = (size_t)n_streams * DDN_S16_STATE_FLOATS * 4;
-    float *d_p = nullptr, *d_s = nullptr, *d_g = nullptr;
-    int16_t* d_o = nullptr;
-    int rc = DDN_OK;
-    if (hipMalloc(&d_p, np * 4 + 4) != hipSuccess || hipMalloc(&d_o, np * 2 + 4) != hipSuccess
-        || hipMalloc(&d_s, ns) != hipSuccess || hipMalloc(&d_g, (size_t)n_streams * 4) != hipSuccess) {
-        ddn_set_error("ddn_audio_s16_host: device allocation failed (no device?)");
-        rc = DDN_ENODEV;
-    } else if (hipMemcpy(d_p, pcm, np * 4, hipMemcpyHostToDevice) != hipSuccess
-               || hipMemcpy(d_s, state32, ns, hipMemcpyHostToDevice) != hipSuccess
-               || (gain_a && hipMemcpy(d_g, gain_a, (size_t)n_streams * 4, hipMemcpyHostToDevice) != hipSuccess)
-               || ddn_dev_audio_s16(d_p, n_streams, n_frames, audio_gain, use_hpf_d, use_agsm, hpf_d_coef(), d_o, d_s, d_g,
-                                    nullptr) != hipSuccess
-               || hipMemcpy(out, d_o, np * 2, hipMemcpyDeviceToHost) != hipSuccess
-               || hipMemcpy(state32, d_s, ns, hipMemcpyDeviceToHost) != hipSuccess
-               || (gain_a && hipMemcpy(gain_a, d_g, (size_t)n_streams * 4, hipMemcpyDeviceToHost) != hipSuccess)) {
-        rc = DDN_EHIP;
-    }
-    (void)hipFree(d_p);
-    (void)hipFree(d_o);
-    (void)hipFree(d_s);
-    (void)hipFree(d_g);
-    return rc;
+    DDN_TRY(check_s16(__func__, pcm, n_streams, n_frames, use_agsm, out, state32, gain_a));
+    const size_t np = (size_t)n_streams * (size_t)n_frames * 160;
+    DdnStaged s;
+    const float* p = s.in(pcm, np * 4);
+    int16_t* o = s.out(out, np * 2);
+    float* st = s.inout(state32, (size_t)n_streams * DDN_S16_STATE_FLOATS * 4);
+    float* g = s.inout(gain_a, (size_t)n_streams * 4); // (a buffer without the caller's too)
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_audio_s16_batch(p, n_streams, n_frames, audio_gain, use_hpf_d, use_agsm, o, st, g, nullptr));
+    return s.finish();
 }

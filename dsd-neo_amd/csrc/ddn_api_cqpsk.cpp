@@ -11,16 +11,6 @@
 #include "ddn_api_util.h"
 #include "ddn_device.h"
 
-static int
-taps_have_zero(const float* taps, int n) {
-    for (int i = 0; i < n; i++) {
-        if (taps[i] == 0.0f) {
-            return 1;
-        }
-    }
-    return 0;
-}
-
 struct ddn_cqpsk_batch {
     ddn_cqpsk_config cfg;
     int sps, taps_len, fll_nt;
@@ -38,19 +28,12 @@ struct ddn_cqpsk_batch {
     void* d_sym;            // [B][sym_cap] complex Gardner output
     size_t sym_cap;
     int* d_cnt;
+    DdnPool pool;
 };
 
 static void
 cq_free(ddn_cqpsk_batch* b) {
-    (void)hipFree(b->d_taps);
-    (void)hipFree(b->d_fll_taps);
-    (void)hipFree(b->d_lpf_hist);
-    (void)hipFree(b->d_state);
-    (void)hipFree(b->d_delay);
-    (void)hipFree(b->d_a);
-    (void)hipFree(b->d_b);
-    (void)hipFree(b->d_sym);
-    (void)hipFree(b->d_cnt);
+    b->pool.release();
     if (b->ted) {
         ddn_ted_batch_destroy(b->ted);
     }
@@ -74,11 +57,7 @@ ddn_cqpsk_batch_create(const ddn_cqpsk_config* cfg, ddn_cqpsk_batch** out) {
         ddn_set_error("ddn_cqpsk_batch_create: bad configuration");
         return DDN_EINVAL;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        ddn_set_error("no HIP device available");
-        return DDN_ENODEV;
-    }
+    DDN_TRY(ddn_have_device());
     ddn_cqpsk_batch* b = new (std::nothrow) ddn_cqpsk_batch();
     if (!b) {
         return DDN_ENOMEM;
@@ -103,13 +82,10 @@ ddn_cqpsk_batch_create(const ddn_cqpsk_config* cfg, ddn_cqpsk_batch** out) {
     const int ted_rate_hz = (cfg->sample_rate_hz + b->sps / 2) / b->sps;
     b->fll_nt = ddn_design_fll_band_edge(b->sps, b->fll_taps, &b->fll_alpha, &b->fll_beta);
     const size_t B = (size_t)cfg->n_channels;
-    if (hipMalloc(&b->d_taps, sizeof(float) * (DDN_MAX_TAPS + 1)) != hipSuccess
-        || hipMalloc(&b->d_fll_taps, sizeof(b->fll_taps)) != hipSuccess
+    if (!b->pool.alloc(&b->d_taps, DDN_MAX_TAPS + 1) || !b->pool.alloc(&b->d_fll_taps, 4 * DDN_FLL_MAX_TAPS)
         || hipMemcpy(b->d_fll_taps, b->fll_taps, sizeof(b->fll_taps), hipMemcpyHostToDevice) != hipSuccess
-        || hipMalloc(&b->d_lpf_hist, sizeof(float) * 2 * DDN_MAX_TAPS * B) != hipSuccess
-        || hipMalloc(&b->d_state, sizeof(DdnCqpskState) * B) != hipSuccess
-        || hipMalloc(&b->d_delay, sizeof(float) * 4 * (size_t)b->fll_nt * B) != hipSuccess
-        || hipMalloc(&b->d_cnt, sizeof(int) * B) != hipSuccess
+        || b->pool.alloc_bytes(&b->d_lpf_hist, sizeof(float) * 2 * DDN_MAX_TAPS * B) != hipSuccess || !b->pool.alloc(&b->d_state, B)
+        || !b->pool.alloc(&b->d_delay, 4 * (size_t)b->fll_nt * B) || !b->pool.alloc(&b->d_cnt, B)
         || (b->taps_len >= 3
             && hipMemcpy(b->d_taps, b->taps, sizeof(float) * (size_t)b->taps_len, hipMemcpyHostToDevice) != hipSuccess)
         || ddn_ted_batch_create(cfg->n_channels, b->sps, ted_rate_hz, cfg->ted_gain, &b->ted) != DDN_OK
@@ -146,13 +122,15 @@ ddn_cqpsk_max_symbols(const ddn_cqpsk_batch* b, size_t n) {
     return b ? n / (size_t)b->sps + n / (size_t)(b->sps * 100) + 8 : 0;
 }
 
+static int
+check_cqpsk_run(const char* who, const ddn_cqpsk_batch* b, const void* iq, const float* symbols, const int32_t* counts) {
+    return (b && iq && symbols && counts) ? DDN_OK : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_cqpsk_run(ddn_cqpsk_batch* b, const void* d_iq, size_t n, float* d_symbols, size_t sym_stride, int32_t* d_counts,
               void* hip_stream) {
-    if (!b || !d_iq || !d_symbols || !d_counts) {
-        ddn_set_error("ddn_cqpsk_run: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_cqpsk_run(__func__, b, d_iq, d_symbols, d_counts));
     hipStream_t st = (hipStream_t)hip_stream;
     const int B = b->cfg.n_channels;
     if (n == 0) {
@@ -175,21 +153,16 @@ ddn_cqpsk_run(ddn_cqpsk_batch* b, const void* d_iq, size_t n, float* d_symbols, 
     const size_t need = sizeof(float) * 2 * (size_t)B * n;
     if (b->work_cap < need) {
         HIP_TRY(hipStreamSynchronize(st));
-        (void)hipFree(b->d_a);
-        (void)hipFree(b->d_b);
-        b->d_a = b->d_b = nullptr;
         b->work_cap = 0;
-        HIP_TRY(hipMalloc(&b->d_a, need));
-        HIP_TRY(hipMalloc(&b->d_b, need));
+        HIP_TRY(b->pool.realloc_bytes(&b->d_a, need));
+        HIP_TRY(b->pool.realloc_bytes(&b->d_b, need));
         b->work_cap = need;
     }
     const size_t scap = ddn_cqpsk_max_symbols(b, n);
     if (b->sym_cap < scap) {
         HIP_TRY(hipStreamSynchronize(st));
-        (void)hipFree(b->d_sym);
-        b->d_sym = nullptr;
         b->sym_cap = 0;
-        HIP_TRY(hipMalloc(&b->d_sym, sizeof(float) * 2 * (size_t)B * scap));
+        HIP_TRY(b->pool.realloc_bytes(&b->d_sym, sizeof(float) * 2 * (size_t)B * scap));
         b->sym_cap = scap;
     }
     const void* cur = d_iq;
@@ -216,42 +189,22 @@ ddn_cqpsk_run(ddn_cqpsk_batch* b, const void* d_iq, size_t n, float* d_symbols, 
 
 extern "C" int
 ddn_cqpsk_run_host(ddn_cqpsk_batch* b, const void* iq, size_t n, float* symbols, size_t sym_stride, int32_t* counts) {
-    if (!b || !iq || !symbols || !counts) {
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_cqpsk_run(__func__, b, iq, symbols, counts));
     const size_t B = (size_t)b->cfg.n_channels;
-    const size_t in_bytes = B * n * (b->cfg.input_format == DDN_IN_CU8 ? 2 : 8);
     const size_t scap = ddn_cqpsk_max_symbols(b, n);
     if (sym_stride < scap) {
         ddn_set_error("ddn_cqpsk_run_host: sym_stride %zu < %zu", sym_stride, scap);
         return DDN_ERANGE;
     }
-    void* d_in = nullptr;
-    float* d_out = nullptr;
-    int32_t* d_cnt = nullptr;
-    int rc;
-    if (hipMalloc(&d_in, in_bytes + 8) != hipSuccess || hipMalloc(&d_out, B * scap * 4 + 8) != hipSuccess
-        || hipMalloc(&d_cnt, B * 4) != hipSuccess) {
-        ddn_set_error("ddn_cqpsk_run_host: device allocation failed (no device?)");
-        rc = DDN_ENODEV;
-    } else if (hipMemcpy(d_in, iq, in_bytes, hipMemcpyHostToDevice) != hipSuccess
-               || hipMemset(d_out, 0, B * scap * 4) != hipSuccess) {
-        rc = DDN_EHIP;
-    } else {
-        rc = ddn_cqpsk_run(b, d_in, n, d_out, scap, d_cnt, nullptr);
-        if (rc == DDN_OK) {
-            if (hipDeviceSynchronize() != hipSuccess
-                || hipMemcpy2D(symbols, sym_stride * 4, d_out, scap * 4, scap * 4, B, hipMemcpyDeviceToHost) != hipSuccess
-                || hipMemcpy(counts, d_cnt, B * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-                ddn_set_error("ddn_cqpsk_run_host: %s", hipGetErrorString(hipGetLastError()));
-                rc = DDN_EHIP;
-            }
-        }
-    }
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    (void)hipFree(d_cnt);
-    return rc;
+    DdnStaged s;
+    const void* in = s.in(iq, B * n * (b->cfg.input_format == DDN_IN_CU8 ? 2 : 8));
+    float* o = s.out((float*)nullptr, B * scap * 4); // rows of scap symbols: they go into the caller's rows of sym_stride below
+    int32_t* c = s.out(counts, B * 4);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_cqpsk_run(b, in, n, o, scap, c, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy2D(symbols, sym_stride * 4, o, scap * 4, scap * 4, B, hipMemcpyDeviceToHost));
+    return s.finish();
 }
 
 extern "C" int

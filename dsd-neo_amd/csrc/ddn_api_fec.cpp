@@ -1,8 +1,9 @@
 // ddn_api_fec.cpp — C-ABI for the batched trellis / Viterbi decoders (include/ddn_hip.h, "FEC" section) and the
 // single-codeword drop-in symbols with the reference's names.
 //
-// Batched calls take DEVICE pointers and a stream; `_host` variants stage host buffers through the device
-// (synchronous).  Nothing here computes on the CPU: without a GPU every call fails with DDN_ENODEV/DDN_EHIP.
+// Batched calls take DEVICE pointers and a stream; `_host` variants check their arguments with their batched twin's check_*(),
+// stage host buffers through the device (DdnStaged, synchronous) and run the twin.  Nothing here computes on the CPU: without a
+// GPU every call with good arguments fails with DDN_ENODEV.
 
 #include <hip/hip_runtime.h>
 
@@ -14,27 +15,6 @@
 #include "ddn_device.h"
 
 namespace {
-struct Dev {
-    void* p = nullptr;
-    size_t bytes;
-    explicit Dev(size_t b) : bytes(b) {
-        if (hipMalloc(&p, b ? b : 4) != hipSuccess) {
-            p = nullptr;
-        }
-    }
-    ~Dev() { (void)hipFree(p); }
-    Dev(const Dev&) = delete;
-    Dev& operator=(const Dev&) = delete;
-    int up(const void* h) { return hipMemcpy(p, h, bytes, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1; }
-    int down(void* h) { return hipMemcpy(h, p, bytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1; }
-};
-
-int
-no_dev() {
-    ddn_set_error("device allocation/copy failed (no HIP device?)");
-    return DDN_ENODEV;
-}
-
 int
 build_puncture(const uint8_t* punct, int p_len, int in_len, DdnPuncture* pu, int* u_len) {
     memset(pu, 0, sizeof(*pu));
@@ -71,46 +51,53 @@ build_puncture(const uint8_t* punct, int p_len, int in_len, DdnPuncture* pu, int
 }
 } // namespace
 
+static int
+check_p25_12_soft(const char* who, const int16_t* llr196, const uint8_t* out12) {
+    return (llr196 && out12) ? DDN_OK : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_fec_p25_12_soft_batch(const int16_t* d_llr196, size_t n, uint8_t* d_out12, int32_t* d_metric, void* hip_stream) {
-    if (!d_llr196 || !d_out12) {
-        ddn_set_error("ddn_fec_p25_12_soft_batch: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_p25_12_soft(__func__, d_llr196, d_out12));
     HIP_TRY(ddn_dev_p25_half_rate(d_llr196, (int)n, d_out12, d_metric, (hipStream_t)hip_stream));
     return DDN_OK;
 }
 
+static int
+check_r34(const char* who, const uint8_t* dibits98, const uint8_t* out18) {
+    return (dibits98 && out18) ? DDN_OK : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_fec_r34_batch(const uint8_t* d_dibits98, const uint8_t* d_reliab98, size_t n, uint8_t* d_out18, void* hip_stream) {
-    if (!d_dibits98 || !d_out18) {
-        ddn_set_error("ddn_fec_r34_batch: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_r34(__func__, d_dibits98, d_out18));
     HIP_TRY(ddn_dev_r34(d_dibits98, d_reliab98, (int)n, d_out18, (hipStream_t)hip_stream));
     return DDN_OK;
+}
+
+static int
+check_nxdn_conv(const char* who, const uint8_t* sym, const uint8_t* out, int n_steps, int n_bits, int out_stride) {
+    return (sym && out && n_steps > 0 && n_steps <= 1024 && n_bits >= 0 && n_bits <= n_steps && out_stride >= (n_bits + 7) / 8) ? DDN_OK : ddn_bad_argument(who);
 }
 
 extern "C" int
 ddn_fec_nxdn_conv_batch(const uint8_t* d_sym, const uint8_t* d_rel, size_t n, int n_steps, int n_bits,
                         uint16_t* d_metrics_io, uint8_t* d_out, int out_stride, void* hip_stream) {
-    if (!d_sym || !d_out || n_steps <= 0 || n_steps > 1024 || n_bits < 0 || n_bits > n_steps
-        || out_stride < (n_bits + 7) / 8) {
-        ddn_set_error("ddn_fec_nxdn_conv_batch: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_nxdn_conv(__func__, d_sym, d_out, n_steps, n_bits, out_stride));
     HIP_TRY(ddn_dev_k5_nxdn(d_sym, d_rel, (int)n, n_steps, n_bits, d_metrics_io, d_out, out_stride,
                             (hipStream_t)hip_stream));
     return DDN_OK;
 }
 
+static int
+check_viterbi_k5(const char* who, const uint16_t* soft, const uint8_t* out, int in_len, int out_stride) {
+    return (soft && out && in_len >= 2 && out_stride > 0) ? DDN_OK : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_fec_viterbi_k5_batch(const uint16_t* d_soft, size_t n, int in_len, const uint8_t* punct, int p_len, uint8_t* d_out,
                          int out_stride, uint32_t* d_cost, void* hip_stream) {
-    if (!d_soft || !d_out || in_len < 2) {
-        ddn_set_error("ddn_fec_viterbi_k5_batch: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_viterbi_k5("ddn_fec_viterbi_k5_batch", d_soft, d_out, in_len, out_stride));
     DdnPuncture pu;
     int u_len = 0;
     int rc = build_puncture(punct, p_len, in_len, &pu, &u_len);
@@ -134,10 +121,7 @@ ddn_fec_viterbi_k5_batch(const uint16_t* d_soft, size_t n, int in_len, const uin
 extern "C" int
 ddn_fec_viterbi_k5_batch_wanted(const uint16_t* d_soft, size_t n, int in_len, const uint8_t* punct, int p_len, uint8_t* d_out,
                                 int out_stride, uint32_t* d_cost, const uint8_t* d_wanted, void* hip_stream) {
-    if (!d_soft || !d_out || in_len < 2) {
-        ddn_set_error("ddn_fec_viterbi_k5_batch: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_viterbi_k5("ddn_fec_viterbi_k5_batch", d_soft, d_out, in_len, out_stride));
     DdnPuncture pu;
     int u_len = 0;
     int rc = build_puncture(punct, p_len, in_len, &pu, &u_len);
@@ -152,25 +136,29 @@ ddn_fec_viterbi_k5_batch_wanted(const uint16_t* d_soft, size_t n, int in_len, co
     return DDN_OK;
 }
 
+static int
+check_nid_decode(const char* who, const uint8_t* bits63, const int32_t* out4) {
+    return (bits63 && out4) ? DDN_OK : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_p25p1_nid_decode_batch(const uint8_t* d_bits63, const uint8_t* d_rel63, const int32_t* d_observed_nac,
                            const uint8_t* d_parity, const uint8_t* d_parity_rel, int erasure_threshold, size_t n,
                            int32_t* d_out4, void* hip_stream) {
-    if (!d_bits63 || !d_out4) {
-        ddn_set_error("ddn_p25p1_nid_decode_batch: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_nid_decode(__func__, d_bits63, d_out4));
     HIP_TRY(ddn_dev_nid_decode(d_bits63, d_rel63, d_observed_nac, d_parity, d_parity_rel, erasure_threshold, (int)n,
                                d_out4, (hipStream_t)hip_stream));
     return DDN_OK;
 }
 
+static int
+check_hamming_10_6_3(const char* who, const uint8_t* bits10, const uint8_t* errs) {
+    return (bits10 && errs) ? DDN_OK : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_fec_hamming_10_6_3_batch(uint8_t* d_bits10, size_t n, uint8_t* d_errs, void* hip_stream) {
-    if (!d_bits10 || !d_errs) {
-        ddn_set_error("ddn_fec_hamming_10_6_3_batch: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_hamming_10_6_3(__func__, d_bits10, d_errs));
     HIP_TRY(ddn_dev_hamming_10_6_3(d_bits10, (int)n, d_errs, (hipStream_t)hip_stream));
     return DDN_OK;
 }
@@ -178,107 +166,81 @@ ddn_fec_hamming_10_6_3_batch(uint8_t* d_bits10, size_t n, uint8_t* d_errs, void*
 // ---- host-buffer variants ------------------------------------------------------------------------------
 extern "C" int
 ddn_fec_p25_12_soft_host(const int16_t* llr196, size_t n, uint8_t* out12, int32_t* metric) {
-    Dev a(n * 196 * 2), b(n * 12), m(n * 4);
-    if (!a.p || !b.p || !m.p || a.up(llr196)) {
-        return no_dev();
-    }
-    int rc = ddn_fec_p25_12_soft_batch((const int16_t*)a.p, n, (uint8_t*)b.p, (int32_t*)m.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    if (b.down(out12) || (metric && m.down(metric))) {
-        return no_dev();
-    }
-    return DDN_OK;
+    DDN_TRY(check_p25_12_soft(__func__, llr196, out12));
+    DdnStaged s;
+    const int16_t* a = s.in(llr196, n * 196 * 2);
+    uint8_t* b = s.out(out12, n * 12);
+    int32_t* m = s.out(metric, n * 4);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_p25_12_soft_batch(a, n, b, m, nullptr));
+    return s.finish();
 }
 
 extern "C" int
 ddn_fec_r34_host(const uint8_t* dibits98, const uint8_t* reliab98, size_t n, uint8_t* out18) {
-    Dev a(n * 98), r(n * 98), b(n * 18);
-    if (!a.p || !r.p || !b.p || a.up(dibits98) || (reliab98 && r.up(reliab98))) {
-        return no_dev();
-    }
-    int rc = ddn_fec_r34_batch((const uint8_t*)a.p, reliab98 ? (const uint8_t*)r.p : nullptr, n, (uint8_t*)b.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return b.down(out18) ? no_dev() : DDN_OK;
+    DDN_TRY(check_r34(__func__, dibits98, out18));
+    DdnStaged s;
+    const uint8_t* a = s.in(dibits98, n * 98);
+    const uint8_t* r = s.in_opt(reliab98, n * 98);
+    uint8_t* b = s.out(out18, n * 18);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_r34_batch(a, r, n, b, nullptr));
+    return s.finish();
 }
 
 extern "C" int
 ddn_fec_nxdn_conv_host(const uint8_t* sym, const uint8_t* rel, size_t n, int n_steps, int n_bits, uint16_t* metrics_io,
                        uint8_t* out, int out_stride) {
-    if (n_steps <= 0 || out_stride <= 0) {
-        return DDN_EINVAL;
-    }
-    Dev a(n * 2 * (size_t)n_steps), r(n * 2 * (size_t)n_steps), m(n * 32), b(n * (size_t)out_stride);
-    if (!a.p || !r.p || !m.p || !b.p || a.up(sym) || (rel && r.up(rel)) || (metrics_io && m.up(metrics_io))
-        || hipMemset(b.p, 0, b.bytes) != hipSuccess) {
-        return no_dev();
-    }
-    int rc = ddn_fec_nxdn_conv_batch((const uint8_t*)a.p, rel ? (const uint8_t*)r.p : nullptr, n, n_steps, n_bits,
-                                     metrics_io ? (uint16_t*)m.p : nullptr, (uint8_t*)b.p, out_stride, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    if (b.down(out) || (metrics_io && m.down(metrics_io))) {
-        return no_dev();
-    }
-    return DDN_OK;
+    DDN_TRY(check_nxdn_conv(__func__, sym, out, n_steps, n_bits, out_stride));
+    DdnStaged s;
+    const uint8_t* a = s.in(sym, n * 2 * (size_t)n_steps);
+    const uint8_t* r = s.in_opt(rel, n * 2 * (size_t)n_steps);
+    uint16_t* m = metrics_io ? s.inout(metrics_io, n * 32) : nullptr;
+    uint8_t* b = s.out(out, n * (size_t)out_stride);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_nxdn_conv_batch(a, r, n, n_steps, n_bits, m, b, out_stride, nullptr));
+    return s.finish();
 }
 
 extern "C" int
 ddn_fec_viterbi_k5_host(const uint16_t* soft, size_t n, int in_len, const uint8_t* punct, int p_len, uint8_t* out,
                         int out_stride, uint32_t* cost) {
-    if (in_len < 2 || out_stride <= 0) {
-        return DDN_EINVAL;
-    }
-    Dev a(n * (size_t)in_len * 2), b(n * (size_t)out_stride), c(n * 4);
-    if (!a.p || !b.p || !c.p || a.up(soft)) {
-        return no_dev();
-    }
-    int rc = ddn_fec_viterbi_k5_batch((const uint16_t*)a.p, n, in_len, punct, p_len, (uint8_t*)b.p, out_stride,
-                                      (uint32_t*)c.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    if (b.down(out) || (cost && c.down(cost))) {
-        return no_dev();
-    }
-    return DDN_OK;
+    DDN_TRY(check_viterbi_k5(__func__, soft, out, in_len, out_stride));
+    DdnStaged s;
+    const uint16_t* a = s.in(soft, n * (size_t)in_len * 2);
+    uint8_t* b = s.out(out, n * (size_t)out_stride);
+    uint32_t* c = s.out(cost, n * 4);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_viterbi_k5_batch(a, n, in_len, punct, p_len, b, out_stride, c, nullptr));
+    return s.finish();
 }
 
 extern "C" int
 ddn_p25p1_nid_decode_host(const uint8_t* bits63, const uint8_t* rel63, const int32_t* observed_nac,
                           const uint8_t* parity, const uint8_t* parity_rel, int erasure_threshold, size_t n,
                           int32_t* out4) {
-    Dev a(n * 63), r(n * 63), o(n * 4), p(n), q(n), out(n * 16);
-    if (!a.p || !r.p || !o.p || !p.p || !q.p || !out.p || a.up(bits63) || (rel63 && r.up(rel63))
-        || (observed_nac && o.up(observed_nac)) || (parity && p.up(parity)) || (parity_rel && q.up(parity_rel))) {
-        return no_dev();
-    }
-    int rc = ddn_p25p1_nid_decode_batch((const uint8_t*)a.p, rel63 ? (const uint8_t*)r.p : nullptr,
-                                        observed_nac ? (const int32_t*)o.p : nullptr,
-                                        parity ? (const uint8_t*)p.p : nullptr,
-                                        parity_rel ? (const uint8_t*)q.p : nullptr, erasure_threshold, n,
-                                        (int32_t*)out.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return out.down(out4) ? no_dev() : DDN_OK;
+    DDN_TRY(check_nid_decode(__func__, bits63, out4));
+    DdnStaged s;
+    const uint8_t* a = s.in(bits63, n * 63);
+    const uint8_t* r = s.in_opt(rel63, n * 63);
+    const int32_t* o = s.in_opt(observed_nac, n * 4);
+    const uint8_t* p = s.in_opt(parity, n);
+    const uint8_t* q = s.in_opt(parity_rel, n);
+    int32_t* out = s.out(out4, n * 16);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_p25p1_nid_decode_batch(a, r, o, p, q, erasure_threshold, n, out, nullptr));
+    return s.finish();
 }
 
 extern "C" int
 ddn_fec_hamming_10_6_3_host(uint8_t* bits10, size_t n, uint8_t* errs) {
-    Dev a(n * 10), e(n);
-    if (!a.p || !e.p || a.up(bits10)) {
-        return no_dev();
-    }
-    int rc = ddn_fec_hamming_10_6_3_batch((uint8_t*)a.p, n, (uint8_t*)e.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return (a.down(bits10) || e.down(errs)) ? no_dev() : DDN_OK;
+    DDN_TRY(check_hamming_10_6_3(__func__, bits10, errs));
+    DdnStaged s;
+    uint8_t* a = s.inout(bits10, n * 10);
+    uint8_t* e = s.out(errs, n);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_hamming_10_6_3_batch(a, n, e, nullptr));
+    return s.finish();
 }
 
 // reference: int hamming_10_6_3_decode(char* data, const char* parity)  (include/dsd-neo/fec/block_codes.h)
@@ -509,13 +471,15 @@ rs_code_params(int code, int* n_par, int* n_data, int* t) {
     }
 }
 
+static int
+check_golay24(const char* who, int data_len, const uint8_t* data_bits, const uint8_t* parity12, const uint8_t* status) {
+    return ((data_len == 6 || data_len == 12) && data_bits && parity12 && status) ? DDN_OK : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_fec_golay24_batch(int data_len, uint8_t* d_data_bits, const uint8_t* d_parity12, size_t n, uint8_t* d_status,
                       int32_t* d_fixed, void* hip_stream) {
-    if ((data_len != 6 && data_len != 12) || !d_data_bits || !d_parity12 || !d_status) {
-        ddn_set_error("ddn_fec_golay24_batch: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_golay24(__func__, data_len, d_data_bits, d_parity12, d_status));
     HIP_TRY(ddn_dev_golay24(d_data_bits, d_parity12, data_len, (int)n, d_status, d_fixed, (hipStream_t)hip_stream));
     return DDN_OK;
 }
@@ -523,32 +487,29 @@ ddn_fec_golay24_batch(int data_len, uint8_t* d_data_bits, const uint8_t* d_parit
 extern "C" int
 ddn_fec_golay24_host(int data_len, uint8_t* data_bits, const uint8_t* parity12, size_t n, uint8_t* status,
                      int32_t* fixed) {
-    if ((data_len != 6 && data_len != 12) || !data_bits || !parity12 || !status) {
-        return DDN_EINVAL;
-    }
-    Dev a(n * (size_t)data_len), p(n * 12), s(n), f(n * 4);
-    if (!a.p || !p.p || !s.p || !f.p || a.up(data_bits) || p.up(parity12)) {
-        return no_dev();
-    }
-    int rc = ddn_fec_golay24_batch(data_len, (uint8_t*)a.p, (const uint8_t*)p.p, n, (uint8_t*)s.p, (int32_t*)f.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return (a.down(data_bits) || s.down(status) || (fixed && f.down(fixed))) ? no_dev() : DDN_OK;
+    DDN_TRY(check_golay24(__func__, data_len, data_bits, parity12, status));
+    DdnStaged s;
+    uint8_t* a = s.inout(data_bits, n * (size_t)data_len);
+    const uint8_t* p = s.in(parity12, n * 12);
+    uint8_t* st = s.out(status, n);
+    int32_t* f = s.out(fixed, n * 4);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_golay24_batch(data_len, a, p, n, st, f, nullptr));
+    return s.finish();
+}
+
+static int
+check_p25_rs(const char* who, int code, const uint8_t* data_bits, const uint8_t* parity_bits, const uint8_t* status, int* n_par, int* n_data,
+             int* t) {
+    DDN_TRY(rs_code_params(code, n_par, n_data, t));
+    return (data_bits && parity_bits && status) ? DDN_OK : ddn_bad_argument(who);
 }
 
 extern "C" int
 ddn_fec_p25_rs_batch(int code, uint8_t* d_data_bits, const uint8_t* d_parity_bits, size_t n, uint8_t* d_status,
                      void* hip_stream) {
     int n_par, n_data, t;
-    int rc = rs_code_params(code, &n_par, &n_data, &t);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    if (!d_data_bits || !d_parity_bits || !d_status) {
-        ddn_set_error("ddn_fec_p25_rs_batch: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_p25_rs(__func__, code, d_data_bits, d_parity_bits, d_status, &n_par, &n_data, &t));
     HIP_TRY(ddn_dev_rs63(d_data_bits, d_parity_bits, n_par, n_data, t, (int)n, d_status, (hipStream_t)hip_stream));
     return DDN_OK;
 }
@@ -556,22 +517,14 @@ ddn_fec_p25_rs_batch(int code, uint8_t* d_data_bits, const uint8_t* d_parity_bit
 extern "C" int
 ddn_fec_p25_rs_host(int code, uint8_t* data_bits, const uint8_t* parity_bits, size_t n, uint8_t* status) {
     int n_par, n_data, t;
-    int rc = rs_code_params(code, &n_par, &n_data, &t);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    if (!data_bits || !parity_bits || !status) {
-        return DDN_EINVAL;
-    }
-    Dev a(n * (size_t)n_data * 6), p(n * (size_t)n_par * 6), s(n);
-    if (!a.p || !p.p || !s.p || a.up(data_bits) || p.up(parity_bits)) {
-        return no_dev();
-    }
-    rc = ddn_fec_p25_rs_batch(code, (uint8_t*)a.p, (const uint8_t*)p.p, n, (uint8_t*)s.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return (a.down(data_bits) || s.down(status)) ? no_dev() : DDN_OK;
+    DDN_TRY(check_p25_rs(__func__, code, data_bits, parity_bits, status, &n_par, &n_data, &t));
+    DdnStaged s;
+    uint8_t* a = s.inout(data_bits, n * (size_t)n_data * 6);
+    const uint8_t* p = s.in(parity_bits, n * (size_t)n_par * 6);
+    uint8_t* st = s.out(status, n);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_p25_rs_batch(code, a, p, n, st, nullptr));
+    return s.finish();
 }
 
 // reference names, one codeword per call (include/dsd-neo/protocol/p25/p25p1_check_hdu.h, p25p1_check_ldu.h).
@@ -641,18 +594,18 @@ rs28_sizes(int kind, int* n_data, int* n_par) {
     return DDN_OK;
 }
 
+static int
+check_rs28(const char* who, int kind, const uint8_t* payload_bits, const uint8_t* parity_bits, const int8_t* erasures28,
+           const uint8_t* n_erasures, const int32_t* status, int* n_data, int* n_par) {
+    DDN_TRY(rs28_sizes(kind, n_data, n_par));
+    return (payload_bits && parity_bits && status && (!n_erasures || erasures28)) ? DDN_OK : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_fec_rs28_batch(int kind, uint8_t* d_payload_bits, const uint8_t* d_parity_bits, const int8_t* d_erasures28,
                    const uint8_t* d_n_erasures, size_t n, int32_t* d_status, void* hip_stream) {
     int nd, np;
-    int rc = rs28_sizes(kind, &nd, &np);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    if (!d_payload_bits || !d_parity_bits || !d_status || (d_n_erasures && !d_erasures28)) {
-        ddn_set_error("ddn_fec_rs28_batch: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_rs28(__func__, kind, d_payload_bits, d_parity_bits, d_erasures28, d_n_erasures, d_status, &nd, &np));
     HIP_TRY(ddn_dev_rs28(kind, d_payload_bits, d_parity_bits, d_erasures28, d_n_erasures, (int)n, d_status,
                          (hipStream_t)hip_stream));
     return DDN_OK;
@@ -662,79 +615,73 @@ extern "C" int
 ddn_fec_rs28_host(int kind, uint8_t* payload_bits, const uint8_t* parity_bits, const int8_t* erasures28,
                   const uint8_t* n_erasures, size_t n, int32_t* status) {
     int nd, np;
-    int rc = rs28_sizes(kind, &nd, &np);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    if (!payload_bits || !parity_bits || !status || (n_erasures && !erasures28)) {
-        return DDN_EINVAL;
-    }
-    Dev a(n * (size_t)nd * 6), p(n * (size_t)np * 6), e(n * 28), c(n), s(n * sizeof(int32_t));
-    if (!a.p || !p.p || !e.p || !c.p || !s.p || a.up(payload_bits) || p.up(parity_bits)) {
-        return no_dev();
-    }
-    if (n_erasures && (e.up(erasures28) || c.up(n_erasures))) {
-        return no_dev();
-    }
-    rc = ddn_fec_rs28_batch(kind, (uint8_t*)a.p, (const uint8_t*)p.p, (const int8_t*)e.p,
-                            n_erasures ? (const uint8_t*)c.p : nullptr, n, (int32_t*)s.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return (a.down(payload_bits) || s.down(status)) ? no_dev() : DDN_OK;
+    DDN_TRY(check_rs28(__func__, kind, payload_bits, parity_bits, erasures28, n_erasures, status, &nd, &np));
+    DdnStaged s;
+    uint8_t* a = s.inout(payload_bits, n * (size_t)nd * 6);
+    const uint8_t* p = s.in(parity_bits, n * (size_t)np * 6);
+    const int8_t* e = s.in(erasures28, n * 28); // (a buffer also where no list is given)
+    const uint8_t* c = s.in_opt(n_erasures, n);
+    int32_t* st = s.out(status, n * sizeof(int32_t));
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_rs28_batch(kind, a, p, e, c, n, st, nullptr));
+    return s.finish();
+}
+
+static int
+check_xcch(const char* who, int kind, const uint8_t* bits360, const int16_t* llr360, const uint8_t* payload_bits, const int32_t* ec,
+           const uint8_t* used_dynamic) {
+    return ((kind == 0 || kind == 1) && bits360 && llr360 && payload_bits && ec && used_dynamic) ? DDN_OK : ddn_bad_argument(who);
 }
 
 // P25 Phase 2 FACCH / SACCH burst stage (include/ddn_hip.h): gather + ranked soft erasures + RS(63,35) with retries
 extern "C" int
 ddn_p25p2_xcch_batch(int kind, const uint8_t* d_bits360, const int16_t* d_llr360, size_t n, int threshold, uint8_t* d_payload_bits,
                      int32_t* d_ec, uint8_t* d_used_dynamic, void* hip_stream) {
-    if ((kind != 0 && kind != 1) || !d_bits360 || !d_llr360 || !d_payload_bits || !d_ec || !d_used_dynamic) {
-        ddn_set_error("ddn_p25p2_xcch_batch: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_xcch(__func__, kind, d_bits360, d_llr360, d_payload_bits, d_ec, d_used_dynamic));
     if (n == 0) {
         return DDN_OK;
     }
     hipStream_t st = (hipStream_t)hip_stream;
-    // scratch (parity bits, erasure lists and their lengths), stream-ordered so concurrent calls never share it
-    uint8_t* scratch = nullptr;
+    DdnScratch s(st); // parity bits, erasure lists and their lengths
     const size_t n_pa = kind == 0 ? 114 : 132;
-    HIP_TRY(hipMallocAsync((void**)&scratch, n * (n_pa + 28 + 1) + 64, st));
-    uint8_t* parity = scratch;
-    int8_t* er = (int8_t*)(scratch + n * n_pa);
-    uint8_t* n_total = scratch + n * (n_pa + 28);
-    const hipError_t e = ddn_dev_p25p2_xcch(kind, d_bits360, d_llr360, (int)n, threshold, d_payload_bits, parity, er, n_total, d_ec,
-                                            d_used_dynamic, st);
-    HIP_TRY(hipFreeAsync(scratch, st));
-    HIP_TRY(e);
+    uint8_t *parity, *n_total;
+    int8_t* er;
+    HIP_TRY(s.arena(n * (n_pa + 28 + 1) + 3 * 256));
+    HIP_TRY(s.get(&parity, n * n_pa));
+    HIP_TRY(s.get(&er, n * 28));
+    HIP_TRY(s.get(&n_total, n));
+    HIP_TRY(ddn_dev_p25p2_xcch(kind, d_bits360, d_llr360, (int)n, threshold, d_payload_bits, parity, er, n_total, d_ec, d_used_dynamic, st));
     return DDN_OK;
+}
+
+static int
+check_mac_crc(const char* who, int kind, const uint8_t* payload_bits, const uint8_t* crc12_ok) {
+    return ((kind == 0 || kind == 1) && payload_bits && crc12_ok) ? DDN_OK : ddn_bad_argument(who);
 }
 
 extern "C" int
 ddn_p25p2_mac_crc_batch(int kind, const uint8_t* d_payload_bits, size_t n, uint8_t* d_crc12_ok, uint8_t* d_crc16_ok, void* hip_stream) {
-    if ((kind != 0 && kind != 1) || !d_payload_bits || !d_crc12_ok) {
-        ddn_set_error("ddn_p25p2_mac_crc_batch: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_mac_crc(__func__, kind, d_payload_bits, d_crc12_ok));
     HIP_TRY(ddn_dev_p25p2_mac_crc(kind, d_payload_bits, (int)n, d_crc12_ok, d_crc16_ok, (hipStream_t)hip_stream));
     return DDN_OK;
 }
 
 extern "C" int
 ddn_p25p2_mac_crc_host(int kind, const uint8_t* payload_bits, size_t n, uint8_t* crc12_ok, uint8_t* crc16_ok) {
-    if ((kind != 0 && kind != 1) || !payload_bits || !crc12_ok) {
-        return DDN_EINVAL;
-    }
-    const size_t n_pl = kind == 0 ? 156 : 180;
-    Dev a(n * n_pl), b(n), c(n);
-    if (!a.p || !b.p || !c.p || a.up(payload_bits)) {
-        return no_dev();
-    }
-    const int rc = ddn_p25p2_mac_crc_batch(kind, (const uint8_t*)a.p, n, (uint8_t*)b.p, crc16_ok ? (uint8_t*)c.p : nullptr, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return (b.down(crc12_ok) || (crc16_ok && c.down(crc16_ok))) ? no_dev() : DDN_OK;
+    DDN_TRY(check_mac_crc(__func__, kind, payload_bits, crc12_ok));
+    DdnStaged s;
+    const uint8_t* a = s.in(payload_bits, n * (kind == 0 ? 156 : 180));
+    uint8_t* b = s.out(crc12_ok, n);
+    uint8_t* c = crc16_ok ? s.out(crc16_ok, n) : nullptr;
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_p25p2_mac_crc_batch(kind, a, n, b, c, nullptr));
+    return s.finish();
+}
+
+static int
+check_ess(const char* who, const uint8_t* payload_bits96, const int16_t* payload_llr96, const uint8_t* parity_bits168, const int16_t* parity_llr168,
+          const uint8_t* payload_out96, const int32_t* ec, const uint8_t* used_dynamic) {
+    return (payload_bits96 && payload_llr96 && parity_bits168 && parity_llr168 && payload_out96 && ec && used_dynamic) ? DDN_OK : ddn_bad_argument(who);
 }
 
 // P25 Phase 2 ESS and voice bursts (include/ddn_hip.h)
@@ -742,40 +689,37 @@ extern "C" int
 ddn_p25p2_ess_batch(const uint8_t* d_payload_bits96, const int16_t* d_payload_llr96, const uint8_t* d_parity_bits168,
                     const int16_t* d_parity_llr168, size_t n, int threshold, uint8_t* d_payload_out96, int32_t* d_ec, uint8_t* d_used_dynamic,
                     void* hip_stream) {
-    if (!d_payload_bits96 || !d_payload_llr96 || !d_parity_bits168 || !d_parity_llr168 || !d_payload_out96 || !d_ec || !d_used_dynamic) {
-        ddn_set_error("ddn_p25p2_ess_batch: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_ess(__func__, d_payload_bits96, d_payload_llr96, d_parity_bits168, d_parity_llr168, d_payload_out96, d_ec, d_used_dynamic));
     if (n == 0) {
         return DDN_OK;
     }
     hipStream_t st = (hipStream_t)hip_stream;
-    uint8_t* scratch = nullptr;
-    HIP_TRY(hipMallocAsync((void**)&scratch, n * 29 + 64, st));
-    const hipError_t e = ddn_dev_p25p2_ess(d_payload_bits96, d_payload_llr96, d_parity_bits168, d_parity_llr168, (int)n, threshold,
-                                           d_payload_out96, (int8_t*)scratch, scratch + n * 28, d_ec, d_used_dynamic, st);
-    HIP_TRY(hipFreeAsync(scratch, st));
-    HIP_TRY(e);
+    DdnScratch s(st); // erasure lists and their lengths
+    int8_t* er;
+    uint8_t* n_total;
+    HIP_TRY(s.arena(n * 29 + 2 * 256));
+    HIP_TRY(s.get(&er, n * 28));
+    HIP_TRY(s.get(&n_total, n));
+    HIP_TRY(ddn_dev_p25p2_ess(d_payload_bits96, d_payload_llr96, d_parity_bits168, d_parity_llr168, (int)n, threshold, d_payload_out96, er, n_total,
+                              d_ec, d_used_dynamic, st));
     return DDN_OK;
 }
 
 extern "C" int
 ddn_p25p2_ess_host(const uint8_t* payload_bits96, const int16_t* payload_llr96, const uint8_t* parity_bits168, const int16_t* parity_llr168,
                    size_t n, int threshold, uint8_t* payload_out96, int32_t* ec, uint8_t* used_dynamic) {
-    if (!payload_bits96 || !payload_llr96 || !parity_bits168 || !parity_llr168 || !payload_out96 || !ec || !used_dynamic) {
-        return DDN_EINVAL;
-    }
-    Dev a(n * 96), al(n * 96 * 2), b(n * 168), bl(n * 168 * 2), o(n * 96), s(n * sizeof(int32_t)), u(n);
-    if (!a.p || !al.p || !b.p || !bl.p || !o.p || !s.p || !u.p || a.up(payload_bits96) || al.up(payload_llr96) || b.up(parity_bits168)
-        || bl.up(parity_llr168)) {
-        return no_dev();
-    }
-    const int rc = ddn_p25p2_ess_batch((const uint8_t*)a.p, (const int16_t*)al.p, (const uint8_t*)b.p, (const int16_t*)bl.p, n, threshold,
-                                       (uint8_t*)o.p, (int32_t*)s.p, (uint8_t*)u.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return (o.down(payload_out96) || s.down(ec) || u.down(used_dynamic)) ? no_dev() : DDN_OK;
+    DDN_TRY(check_ess(__func__, payload_bits96, payload_llr96, parity_bits168, parity_llr168, payload_out96, ec, used_dynamic));
+    DdnStaged s;
+    const uint8_t* a = s.in(payload_bits96, n * 96);
+    const int16_t* al = s.in(payload_llr96, n * 96 * 2);
+    const uint8_t* b = s.in(parity_bits168, n * 168);
+    const int16_t* bl = s.in(parity_llr168, n * 168 * 2);
+    uint8_t* o = s.out(payload_out96, n * 96);
+    int32_t* e = s.out(ec, n * sizeof(int32_t));
+    uint8_t* u = s.out(used_dynamic, n);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_p25p2_ess_batch(a, al, b, bl, n, threshold, o, e, u, nullptr));
+    return s.finish();
 }
 
 extern "C" int
@@ -820,70 +764,64 @@ p25p2_generate_scramble_bits(uint64_t wacn, uint64_t sysid, uint64_t nac, uint8_
         return;
     }
     const uint64_t seed = (wacn * 16777216ULL) + (sysid * 4096ULL) + nac;
-    Dev a(8), o(bit_count);
-    if (!a.p || !o.p || a.up(&seed) || ddn_p25p2_scramble_bits_batch((const uint64_t*)a.p, 1, bit_count, (uint8_t*)o.p, nullptr) != DDN_OK
-        || o.down(out_bits)) {
-        (void)no_dev(); // (the reference's function cannot fail: the error is in ddn_last_error())
+    DdnStaged s;
+    const uint64_t* a = s.in(&seed, 8);
+    uint8_t* o = s.out(out_bits, bit_count);
+    if (s.staged() == DDN_OK && ddn_p25p2_scramble_bits_batch(a, 1, bit_count, o, nullptr) == DDN_OK) {
+        (void)s.finish(); // (the reference's function cannot fail: the error is in ddn_last_error())
     }
+}
+
+static int
+check_burst_fields(const char* who, const uint8_t* bits360, const int16_t* llr360, const int32_t* duid, const int32_t* isch) {
+    return (bits360 && llr360 && duid && isch) ? DDN_OK : ddn_bad_argument(who);
 }
 
 extern "C" int
 ddn_p25p2_burst_fields_batch(const uint8_t* d_bits360, const int16_t* d_llr360, size_t n, int threshold, int32_t* d_duid, int32_t* d_isch,
                              void* hip_stream) {
-    if (!d_bits360 || !d_llr360 || !d_duid || !d_isch) {
-        ddn_set_error("ddn_p25p2_burst_fields_batch: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_burst_fields(__func__, d_bits360, d_llr360, d_duid, d_isch));
     if (n == 0) {
         return DDN_OK;
     }
     hipStream_t st = (hipStream_t)hip_stream;
-    uint8_t* scratch = nullptr; // the I-ISCH words and their reliability rows
-    HIP_TRY(hipMallocAsync((void**)&scratch, n * 48 + 64, st));
-    uint64_t* words = (uint64_t*)scratch;
-    uint8_t* rel = scratch + n * 8;
-    hipError_t e = ddn_dev_p25p2_burst_fields(d_bits360, d_llr360, (int)n, threshold, d_duid, words, rel, st);
-    if (e == hipSuccess) {
-        e = ddn_dev_isch_lookup(words, rel, (int)n, d_isch, st);
-    }
-    HIP_TRY(hipFreeAsync(scratch, st));
-    HIP_TRY(e);
+    DdnScratch s(st); // the I-ISCH words and their reliability rows
+    uint64_t* words;
+    uint8_t* rel;
+    HIP_TRY(s.arena(n * 48 + 2 * 256));
+    HIP_TRY(s.get(&words, n));
+    HIP_TRY(s.get(&rel, n * 40));
+    HIP_TRY(ddn_dev_p25p2_burst_fields(d_bits360, d_llr360, (int)n, threshold, d_duid, words, rel, st));
+    HIP_TRY(ddn_dev_isch_lookup(words, rel, (int)n, d_isch, st));
     return DDN_OK;
 }
 
 extern "C" int
 ddn_p25p2_burst_fields_host(const uint8_t* bits360, const int16_t* llr360, size_t n, int threshold, int32_t* duid, int32_t* isch) {
-    if (!bits360 || !llr360 || !duid || !isch) {
-        return DDN_EINVAL;
-    }
-    Dev b(n * 360), l(n * 360 * 2), d(n * sizeof(int32_t)), q(n * sizeof(int32_t));
-    if (!b.p || !l.p || !d.p || !q.p || b.up(bits360) || l.up(llr360)) {
-        return no_dev();
-    }
-    const int rc = ddn_p25p2_burst_fields_batch((const uint8_t*)b.p, (const int16_t*)l.p, n, threshold, (int32_t*)d.p, (int32_t*)q.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return (d.down(duid) || q.down(isch)) ? no_dev() : DDN_OK;
+    DDN_TRY(check_burst_fields(__func__, bits360, llr360, duid, isch));
+    DdnStaged s;
+    const uint8_t* b = s.in(bits360, n * 360);
+    const int16_t* l = s.in(llr360, n * 360 * 2);
+    int32_t* d = s.out(duid, n * sizeof(int32_t));
+    int32_t* q = s.out(isch, n * sizeof(int32_t));
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_p25p2_burst_fields_batch(b, l, n, threshold, d, q, nullptr));
+    return s.finish();
 }
 
 extern "C" int
 ddn_p25p2_xcch_host(int kind, const uint8_t* bits360, const int16_t* llr360, size_t n, int threshold, uint8_t* payload_bits, int32_t* ec,
                     uint8_t* used_dynamic) {
-    if ((kind != 0 && kind != 1) || !bits360 || !llr360 || !payload_bits || !ec || !used_dynamic) {
-        return DDN_EINVAL;
-    }
-    const size_t n_pl = kind == 0 ? 156 : 180;
-    Dev b(n * 360), l(n * 360 * 2), p(n * n_pl), s(n * sizeof(int32_t)), u(n);
-    if (!b.p || !l.p || !p.p || !s.p || !u.p || b.up(bits360) || l.up(llr360)) {
-        return no_dev();
-    }
-    const int rc = ddn_p25p2_xcch_batch(kind, (const uint8_t*)b.p, (const int16_t*)l.p, n, threshold, (uint8_t*)p.p, (int32_t*)s.p,
-                                        (uint8_t*)u.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return (p.down(payload_bits) || s.down(ec) || u.down(used_dynamic)) ? no_dev() : DDN_OK;
+    DDN_TRY(check_xcch(__func__, kind, bits360, llr360, payload_bits, ec, used_dynamic));
+    DdnStaged s;
+    const uint8_t* b = s.in(bits360, n * 360);
+    const int16_t* l = s.in(llr360, n * 360 * 2);
+    uint8_t* p = s.out(payload_bits, n * (kind == 0 ? 156 : 180));
+    int32_t* e = s.out(ec, n * sizeof(int32_t));
+    uint8_t* u = s.out(used_dynamic, n);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_p25p2_xcch_batch(kind, b, l, n, threshold, p, e, u, nullptr));
+    return s.finish();
 }
 
 // reference names (include/dsd-neo/fec/ez.h:29-31): one section per call, int-per-bit arrays.  -2 when the device path is
@@ -931,32 +869,29 @@ ez_rs28_sacch(int payload[180], int parity[132], const int* erasures, int n_eras
     return rs28_one(2, payload, parity, erasures, n_erasures);
 }
 
+static int
+check_isch_lookup(const char* who, const uint64_t* words, const int32_t* out) {
+    return (words && out) ? DDN_OK : ddn_bad_argument(who);
+}
+
 // ---- P25 Phase 2 I-ISCH lookup ----------------------------------------------------------------------------------------------
 extern "C" int
 ddn_fec_isch_lookup_batch(const uint64_t* d_words, const uint8_t* d_reliab40, size_t n, int32_t* d_out, void* stream) {
-    if (!d_words || !d_out) {
-        ddn_set_error("ddn_fec_isch_lookup_batch: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_isch_lookup(__func__, d_words, d_out));
     HIP_TRY(ddn_dev_isch_lookup(d_words, d_reliab40, (int)n, d_out, (hipStream_t)stream));
     return DDN_OK;
 }
 
 extern "C" int
 ddn_fec_isch_lookup_host(const uint64_t* words, const uint8_t* reliab40, size_t n, int32_t* out) {
-    if (!words || !out) {
-        return DDN_EINVAL;
-    }
-    Dev w(n * sizeof(uint64_t)), r(n * 40), o(n * sizeof(int32_t));
-    if (!w.p || !r.p || !o.p || w.up(words) || (reliab40 && r.up(reliab40))) {
-        return no_dev();
-    }
-    int rc = ddn_fec_isch_lookup_batch((const uint64_t*)w.p, reliab40 ? (const uint8_t*)r.p : nullptr, n, (int32_t*)o.p,
-                                       nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return o.down(out) ? no_dev() : DDN_OK;
+    DDN_TRY(check_isch_lookup(__func__, words, out));
+    DdnStaged s;
+    const uint64_t* w = s.in(words, n * sizeof(uint64_t));
+    const uint8_t* r = s.in_opt(reliab40, n * 40);
+    int32_t* o = s.out(out, n * sizeof(int32_t));
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_isch_lookup_batch(w, r, n, o, nullptr));
+    return s.finish();
 }
 
 // reference names (include/dsd-neo/fec/ez.h): one word per call; -2 (the "nothing found" answer) when no device is there
@@ -972,14 +907,16 @@ isch_lookup_soft(uint64_t isch, const uint8_t reliab40[40]) {
     return ddn_fec_isch_lookup_host(&isch, reliab40, 1, &v) == DDN_OK ? v : -2;
 }
 
+static int
+check_soft_list(const char* who, const void* in, const void* candidates, const int32_t* counts, int max_candidates) {
+    return (in && candidates && counts && max_candidates > 0) ? DDN_OK : ddn_bad_argument(who);
+}
+
 // ---- P25 1/2-rate list decoder -------------------------------------------------------------------------------------
 extern "C" int
 ddn_fec_p25_12_soft_list_batch(const int16_t* d_llr196, size_t n, int max_candidates, ddn_p25_12_candidate* d_candidates8,
                                int32_t* d_counts, void* hip_stream) {
-    if (!d_llr196 || !d_candidates8 || !d_counts || max_candidates <= 0) {
-        ddn_set_error("ddn_fec_p25_12_soft_list_batch: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_soft_list(__func__, d_llr196, d_candidates8, d_counts, max_candidates));
     HIP_TRY(ddn_dev_p25_half_rate_list(d_llr196, (int)n, max_candidates, (uint32_t*)d_candidates8, d_counts,
                                        (hipStream_t)hip_stream));
     return DDN_OK;
@@ -988,19 +925,14 @@ ddn_fec_p25_12_soft_list_batch(const int16_t* d_llr196, size_t n, int max_candid
 extern "C" int
 ddn_fec_p25_12_soft_list_host(const int16_t* llr196, size_t n, int max_candidates, ddn_p25_12_candidate* candidates8,
                               int32_t* counts) {
-    if (!llr196 || !candidates8 || !counts || max_candidates <= 0) {
-        return DDN_EINVAL;
-    }
-    Dev a(n * 196 * 2), c(n * 8 * sizeof(ddn_p25_12_candidate)), k(n * 4);
-    if (!a.p || !c.p || !k.p || a.up(llr196)) {
-        return no_dev();
-    }
-    int rc = ddn_fec_p25_12_soft_list_batch((const int16_t*)a.p, n, max_candidates, (ddn_p25_12_candidate*)c.p,
-                                            (int32_t*)k.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return (c.down(candidates8) || k.down(counts)) ? no_dev() : DDN_OK;
+    DDN_TRY(check_soft_list(__func__, llr196, candidates8, counts, max_candidates));
+    DdnStaged s;
+    const int16_t* a = s.in(llr196, n * 196 * 2);
+    ddn_p25_12_candidate* c = s.out(candidates8, n * 8 * sizeof(ddn_p25_12_candidate));
+    int32_t* k = s.out(counts, n * 4);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_p25_12_soft_list_batch(a, n, max_candidates, c, k, nullptr));
+    return s.finish();
 }
 
 // reference: int p25_12_soft_llr_list(const uint8_t* input, const int16_t* bit_llr196, p25_12_candidate_t* candidates,
@@ -1027,10 +959,7 @@ p25_12_soft_llr_list(const uint8_t* input, const int16_t* bit_llr196, ddn_p25_12
 extern "C" int
 ddn_fec_p25_mbf34_list_batch(const int16_t* d_llr196, size_t n, int max_candidates, const uint8_t* d_wanted,
                              ddn_p25_mbf34_candidate* d_candidates8, int32_t* d_counts, void* hip_stream) {
-    if (!d_llr196 || !d_candidates8 || !d_counts || max_candidates <= 0) {
-        ddn_set_error("ddn_fec_p25_mbf34_list_batch: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_soft_list(__func__, d_llr196, d_candidates8, d_counts, max_candidates));
     if (n == 0) {
         return DDN_OK;
     }
@@ -1040,18 +969,14 @@ ddn_fec_p25_mbf34_list_batch(const int16_t* d_llr196, size_t n, int max_candidat
 
 extern "C" int
 ddn_fec_p25_mbf34_list_host(const int16_t* llr196, size_t n, int max_candidates, ddn_p25_mbf34_candidate* candidates8, int32_t* counts) {
-    if (!llr196 || !candidates8 || !counts || max_candidates <= 0) {
-        return DDN_EINVAL;
-    }
-    Dev a(n * 196 * 2), c(n * 8 * sizeof(ddn_p25_mbf34_candidate)), k(n * 4);
-    if (!a.p || !c.p || !k.p || a.up(llr196)) {
-        return no_dev();
-    }
-    const int rc = ddn_fec_p25_mbf34_list_batch((const int16_t*)a.p, n, max_candidates, nullptr, (ddn_p25_mbf34_candidate*)c.p, (int32_t*)k.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return (c.down(candidates8) || k.down(counts)) ? no_dev() : DDN_OK;
+    DDN_TRY(check_soft_list(__func__, llr196, candidates8, counts, max_candidates));
+    DdnStaged s;
+    const int16_t* a = s.in(llr196, n * 196 * 2);
+    ddn_p25_mbf34_candidate* c = s.out(candidates8, n * 8 * sizeof(ddn_p25_mbf34_candidate));
+    int32_t* k = s.out(counts, n * 4);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_p25_mbf34_list_batch(a, n, max_candidates, nullptr, c, k, nullptr));
+    return s.finish();
 }
 
 // reference: p25_mbf34_decode_soft_list (include/dsd-neo/protocol/p25/p25p1_mbf34.h:28-29); dibits is unused there too
@@ -1075,10 +1000,7 @@ p25_mbf34_decode_soft_list(const uint8_t dibits[98], const int16_t bit_llr[196],
 extern "C" int
 ddn_fec_r34_list_batch(const uint8_t* d_dibits98, const uint8_t* d_reliab98, size_t n, int max_candidates,
                        ddn_r34_candidate* d_candidates32, int32_t* d_counts, void* hip_stream) {
-    if (!d_dibits98 || !d_candidates32 || !d_counts || max_candidates <= 0) {
-        ddn_set_error("ddn_fec_r34_list_batch: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_soft_list(__func__, d_dibits98, d_candidates32, d_counts, max_candidates));
     if (n == 0) {
         return DDN_OK;
     }
@@ -1095,19 +1017,15 @@ ddn_fec_r34_list_batch(const uint8_t* d_dibits98, const uint8_t* d_reliab98, siz
 extern "C" int
 ddn_fec_r34_list_host(const uint8_t* dibits98, const uint8_t* reliab98, size_t n, int max_candidates,
                       ddn_r34_candidate* candidates32, int32_t* counts) {
-    if (!dibits98 || !candidates32 || !counts || max_candidates <= 0) {
-        return DDN_EINVAL;
-    }
-    Dev a(n * 98), r(n * 98), c(n * 32 * sizeof(ddn_r34_candidate)), k(n * 4);
-    if (!a.p || !r.p || !c.p || !k.p || a.up(dibits98) || (reliab98 && r.up(reliab98))) {
-        return no_dev();
-    }
-    int rc = ddn_fec_r34_list_batch((const uint8_t*)a.p, reliab98 ? (const uint8_t*)r.p : nullptr, n, max_candidates,
-                                    (ddn_r34_candidate*)c.p, (int32_t*)k.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return (c.down(candidates32) || k.down(counts)) ? no_dev() : DDN_OK;
+    DDN_TRY(check_soft_list(__func__, dibits98, candidates32, counts, max_candidates));
+    DdnStaged s;
+    const uint8_t* a = s.in(dibits98, n * 98);
+    const uint8_t* r = s.in_opt(reliab98, n * 98);
+    ddn_r34_candidate* c = s.out(candidates32, n * 32 * sizeof(ddn_r34_candidate));
+    int32_t* k = s.out(counts, n * 4);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_r34_list_batch(a, r, n, max_candidates, c, k, nullptr));
+    return s.finish();
 }
 
 // reference: dmr_r34_viterbi_decode_list (include/dsd-neo/protocol/dmr/r34_viterbi.h:51-70)
@@ -1129,14 +1047,17 @@ dmr_r34_viterbi_decode_list(const uint8_t* dibits98, const uint8_t* reliab98, dd
     return 0;
 }
 
+static int
+check_golay24_soft(const char* who, int data_len, const uint8_t* data_bits, const uint8_t* parity12, const int32_t* reliab, const uint8_t* status) {
+    DDN_TRY(check_golay24(who, data_len, data_bits, parity12, status));
+    return reliab ? DDN_OK : ddn_bad_argument(who);
+}
+
 // ---- soft (Chase) Golay / Hamming ------------------------------------------------------------------------------------
 extern "C" int
 ddn_fec_golay24_soft_batch(int data_len, uint8_t* d_data_bits, const uint8_t* d_parity12, const int32_t* d_reliab,
                            size_t n, uint8_t* d_status, int32_t* d_fixed, void* hip_stream) {
-    if ((data_len != 6 && data_len != 12) || !d_data_bits || !d_parity12 || !d_reliab || !d_status) {
-        ddn_set_error("ddn_fec_golay24_soft_batch: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_golay24_soft(__func__, data_len, d_data_bits, d_parity12, d_reliab, d_status));
     HIP_TRY(ddn_dev_golay24_soft(d_data_bits, d_parity12, d_reliab, data_len, (int)n, d_status, d_fixed,
                                  (hipStream_t)hip_stream));
     return DDN_OK;
@@ -1145,28 +1066,27 @@ ddn_fec_golay24_soft_batch(int data_len, uint8_t* d_data_bits, const uint8_t* d_
 extern "C" int
 ddn_fec_golay24_soft_host(int data_len, uint8_t* data_bits, const uint8_t* parity12, const int32_t* reliab, size_t n,
                           uint8_t* status, int32_t* fixed) {
-    if ((data_len != 6 && data_len != 12) || !data_bits || !parity12 || !reliab || !status) {
-        return DDN_EINVAL;
-    }
-    Dev a(n * (size_t)data_len), p(n * 12), r(n * (size_t)(data_len + 12) * 4), s(n), f(n * 4);
-    if (!a.p || !p.p || !r.p || !s.p || !f.p || a.up(data_bits) || p.up(parity12) || r.up(reliab)) {
-        return no_dev();
-    }
-    int rc = ddn_fec_golay24_soft_batch(data_len, (uint8_t*)a.p, (const uint8_t*)p.p, (const int32_t*)r.p, n,
-                                        (uint8_t*)s.p, (int32_t*)f.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return (a.down(data_bits) || s.down(status) || (fixed && f.down(fixed))) ? no_dev() : DDN_OK;
+    DDN_TRY(check_golay24_soft(__func__, data_len, data_bits, parity12, reliab, status));
+    DdnStaged s;
+    uint8_t* a = s.inout(data_bits, n * (size_t)data_len);
+    const uint8_t* p = s.in(parity12, n * 12);
+    const int32_t* r = s.in(reliab, n * (size_t)(data_len + 12) * 4);
+    uint8_t* st = s.out(status, n);
+    int32_t* f = s.out(fixed, n * 4);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_golay24_soft_batch(data_len, a, p, r, n, st, f, nullptr));
+    return s.finish();
+}
+
+static int
+check_hamming_soft(const char* who, const uint8_t* bits10, const int32_t* reliab10, const uint8_t* out10, const uint8_t* status) {
+    return (bits10 && reliab10 && out10 && status) ? DDN_OK : ddn_bad_argument(who);
 }
 
 extern "C" int
 ddn_fec_hamming_10_6_3_soft_batch(const uint8_t* d_bits10, const int32_t* d_reliab10, size_t n, uint8_t* d_out10,
                                   uint8_t* d_status, void* hip_stream) {
-    if (!d_bits10 || !d_reliab10 || !d_out10 || !d_status) {
-        ddn_set_error("ddn_fec_hamming_10_6_3_soft_batch: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_hamming_soft(__func__, d_bits10, d_reliab10, d_out10, d_status));
     HIP_TRY(ddn_dev_hamming_10_6_3_soft(d_bits10, d_reliab10, (int)n, d_out10, d_status, (hipStream_t)hip_stream));
     return DDN_OK;
 }
@@ -1174,19 +1094,15 @@ ddn_fec_hamming_10_6_3_soft_batch(const uint8_t* d_bits10, const int32_t* d_reli
 extern "C" int
 ddn_fec_hamming_10_6_3_soft_host(const uint8_t* bits10, const int32_t* reliab10, size_t n, uint8_t* out10,
                                  uint8_t* status) {
-    if (!bits10 || !reliab10 || !out10 || !status) {
-        return DDN_EINVAL;
-    }
-    Dev a(n * 10), r(n * 40), o(n * 10), s(n);
-    if (!a.p || !r.p || !o.p || !s.p || a.up(bits10) || r.up(reliab10)) {
-        return no_dev();
-    }
-    int rc = ddn_fec_hamming_10_6_3_soft_batch((const uint8_t*)a.p, (const int32_t*)r.p, n, (uint8_t*)o.p, (uint8_t*)s.p,
-                                               nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return (o.down(out10) || s.down(status)) ? no_dev() : DDN_OK;
+    DDN_TRY(check_hamming_soft(__func__, bits10, reliab10, out10, status));
+    DdnStaged s;
+    const uint8_t* a = s.in(bits10, n * 10);
+    const int32_t* r = s.in(reliab10, n * 40);
+    uint8_t* o = s.out(out10, n * 10);
+    uint8_t* st = s.out(status, n);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_hamming_10_6_3_soft_batch(a, r, n, o, st, nullptr));
+    return s.finish();
 }
 
 // reference names (include/dsd-neo/protocol/p25/p25p1_soft.h): one codeword per call
@@ -1233,19 +1149,19 @@ hamming_10_6_3_soft(const char* bits, const int* reliab, char* out_bits) {
     return st;
 }
 
+static int
+check_p25_rs_soft(const char* who, int code, const uint8_t* data_bits, const uint8_t* parity_bits, const uint8_t* data_reliab,
+                  const uint8_t* parity_reliab, const uint8_t* status, int* n_par, int* n_data, int* t) {
+    DDN_TRY(check_p25_rs(who, code, data_bits, parity_bits, status, n_par, n_data, t));
+    return (data_reliab && parity_reliab) ? DDN_OK : ddn_bad_argument(who);
+}
+
 // ---- RS with reliability-ranked erasures -------------------------------------------------------------------------------
 extern "C" int
 ddn_fec_p25_rs_soft_batch(int code, uint8_t* d_data_bits, const uint8_t* d_parity_bits, const uint8_t* d_data_reliab,
                           const uint8_t* d_parity_reliab, size_t n, uint8_t* d_status, void* hip_stream) {
     int n_par, n_data, t;
-    int rc = rs_code_params(code, &n_par, &n_data, &t);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    if (!d_data_bits || !d_parity_bits || !d_data_reliab || !d_parity_reliab || !d_status) {
-        ddn_set_error("ddn_fec_p25_rs_soft_batch: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_p25_rs_soft(__func__, code, d_data_bits, d_parity_bits, d_data_reliab, d_parity_reliab, d_status, &n_par, &n_data, &t));
     HIP_TRY(ddn_dev_rs63_soft(d_data_bits, d_parity_bits, d_data_reliab, d_parity_reliab, n_par, n_data, t,
                               /*P25P1_SOFT_ERASURE_THRESHOLD*/ 64, (int)n, d_status, (hipStream_t)hip_stream));
     return DDN_OK;
@@ -1255,24 +1171,16 @@ extern "C" int
 ddn_fec_p25_rs_soft_host(int code, uint8_t* data_bits, const uint8_t* parity_bits, const uint8_t* data_reliab,
                          const uint8_t* parity_reliab, size_t n, uint8_t* status) {
     int n_par, n_data, t;
-    int rc = rs_code_params(code, &n_par, &n_data, &t);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    if (!data_bits || !parity_bits || !data_reliab || !parity_reliab || !status) {
-        return DDN_EINVAL;
-    }
-    Dev a(n * (size_t)n_data * 6), p(n * (size_t)n_par * 6), dr(n * (size_t)n_data), pr(n * (size_t)n_par), s(n);
-    if (!a.p || !p.p || !dr.p || !pr.p || !s.p || a.up(data_bits) || p.up(parity_bits) || dr.up(data_reliab)
-        || pr.up(parity_reliab)) {
-        return no_dev();
-    }
-    rc = ddn_fec_p25_rs_soft_batch(code, (uint8_t*)a.p, (const uint8_t*)p.p, (const uint8_t*)dr.p, (const uint8_t*)pr.p, n,
-                                   (uint8_t*)s.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return (a.down(data_bits) || s.down(status)) ? no_dev() : DDN_OK;
+    DDN_TRY(check_p25_rs_soft(__func__, code, data_bits, parity_bits, data_reliab, parity_reliab, status, &n_par, &n_data, &t));
+    DdnStaged s;
+    uint8_t* a = s.inout(data_bits, n * (size_t)n_data * 6);
+    const uint8_t* p = s.in(parity_bits, n * (size_t)n_par * 6);
+    const uint8_t* dr = s.in(data_reliab, n * (size_t)n_data);
+    const uint8_t* pr = s.in(parity_reliab, n * (size_t)n_par);
+    uint8_t* st = s.out(status, n);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_p25_rs_soft_batch(code, a, p, dr, pr, n, st, nullptr));
+    return s.finish();
 }
 
 static int
@@ -1306,17 +1214,19 @@ p25p1_rs_36_20_17_soft_reliability(char* data, const char* parity, const uint8_t
 }
 
 
+static int
+check_imbe_deinterleave(const char* who, const uint8_t* records10, const int64_t* first_record, const int32_t* status_count, const uint8_t* imbe_fr,
+                        const uint8_t* imbe_soft, const uint8_t* flags, const int32_t* status_count_out) {
+    return (records10 && first_record && status_count && imbe_fr && imbe_soft && flags && status_count_out) ? DDN_OK : ddn_bad_argument(who);
+}
+
 // ---- IMBE de-interleave (process_IMBE) ------------------------------------------------------------------------------
 extern "C" int
 ddn_p25p1_imbe_deinterleave_batch(const uint8_t* d_records10, size_t n_records, const int64_t* d_first_record,
                                   const int32_t* d_status_count, size_t n_frames, uint8_t* d_imbe_fr,
                                   uint8_t* d_imbe_soft, uint8_t* d_flags, int32_t* d_status_count_out,
                                   void* hip_stream) {
-    if (!d_records10 || !d_first_record || !d_status_count || !d_imbe_fr || !d_imbe_soft || !d_flags
-        || !d_status_count_out) {
-        ddn_set_error("ddn_p25p1_imbe_deinterleave_batch: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_imbe_deinterleave(__func__, d_records10, d_first_record, d_status_count, d_imbe_fr, d_imbe_soft, d_flags, d_status_count_out));
     HIP_TRY(ddn_dev_imbe_deinterleave(d_records10, (long)n_records, d_first_record, d_status_count, (int)n_frames,
                                       d_imbe_fr, d_imbe_soft, d_flags, d_status_count_out, (hipStream_t)hip_stream));
     return DDN_OK;
@@ -1326,50 +1236,44 @@ extern "C" int
 ddn_p25p1_imbe_deinterleave_host(const uint8_t* records10, size_t n_records, const int64_t* first_record,
                                  const int32_t* status_count, size_t n_frames, uint8_t* imbe_fr, uint8_t* imbe_soft,
                                  uint8_t* flags, int32_t* status_count_out) {
-    if (!records10 || !first_record || !status_count || !imbe_fr || !imbe_soft || !flags || !status_count_out) {
-        return DDN_EINVAL;
-    }
-    Dev r(n_records * 10), f(n_frames * 8), c(n_frames * 4), o(n_frames * 184), so(n_frames * 368), fl(n_frames),
-        co(n_frames * 4);
-    if (!r.p || !f.p || !c.p || !o.p || !so.p || !fl.p || !co.p || r.up(records10) || f.up(first_record)
-        || c.up(status_count)) {
-        return no_dev();
-    }
-    int rc = ddn_p25p1_imbe_deinterleave_batch((const uint8_t*)r.p, n_records, (const int64_t*)f.p, (const int32_t*)c.p,
-                                               n_frames, (uint8_t*)o.p, (uint8_t*)so.p, (uint8_t*)fl.p, (int32_t*)co.p,
-                                               nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return (o.down(imbe_fr) || so.down(imbe_soft) || fl.down(flags) || co.down(status_count_out)) ? no_dev() : DDN_OK;
+    DDN_TRY(check_imbe_deinterleave(__func__, records10, first_record, status_count, imbe_fr, imbe_soft, flags, status_count_out));
+    DdnStaged s;
+    const uint8_t* r = s.in(records10, n_records * 10);
+    const int64_t* f = s.in(first_record, n_frames * 8);
+    const int32_t* c = s.in(status_count, n_frames * 4);
+    uint8_t* o = s.out(imbe_fr, n_frames * 184);
+    uint8_t* so = s.out(imbe_soft, n_frames * 368);
+    uint8_t* fl = s.out(flags, n_frames);
+    int32_t* co = s.out(status_count_out, n_frames * 4);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_p25p1_imbe_deinterleave_batch(r, n_records, f, c, n_frames, o, so, fl, co, nullptr));
+    return s.finish();
 }
 
+
+static int
+check_p25_lsd(const char* who, const uint8_t* bits16, const uint8_t* ok) {
+    return (bits16 && ok) ? DDN_OK : ddn_bad_argument(who);
+}
 
 // ---- P25p1 low speed data (16,8) -----------------------------------------------------------------------------------------
 extern "C" int
 ddn_fec_p25_lsd_batch(uint8_t* d_bits16, const int16_t* d_llr16, size_t n, uint8_t* d_ok, void* hip_stream) {
-    if (!d_bits16 || !d_ok) {
-        ddn_set_error("ddn_fec_p25_lsd_batch: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_p25_lsd(__func__, d_bits16, d_ok));
     HIP_TRY(ddn_dev_p25_lsd(d_bits16, d_llr16, (int)n, d_ok, (hipStream_t)hip_stream));
     return DDN_OK;
 }
 
 extern "C" int
 ddn_fec_p25_lsd_host(uint8_t* bits16, const int16_t* llr16, size_t n, uint8_t* ok) {
-    if (!bits16 || !ok) {
-        return DDN_EINVAL;
-    }
-    Dev b(n * 16), l(n * 32), o(n);
-    if (!b.p || !l.p || !o.p || b.up(bits16) || (llr16 && l.up(llr16))) {
-        return no_dev();
-    }
-    int rc = ddn_fec_p25_lsd_batch((uint8_t*)b.p, llr16 ? (const int16_t*)l.p : nullptr, n, (uint8_t*)o.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return (b.down(bits16) || o.down(ok)) ? no_dev() : DDN_OK;
+    DDN_TRY(check_p25_lsd(__func__, bits16, ok));
+    DdnStaged s;
+    uint8_t* b = s.inout(bits16, n * 16);
+    const int16_t* l = s.in_opt(llr16, n * 32);
+    uint8_t* o = s.out(ok, n);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_p25_lsd_batch(b, l, n, o, nullptr));
+    return s.finish();
 }
 
 // reference names (include/dsd-neo/protocol/p25/p25_lsd.h): 1 = valid or corrected, 0 = uncorrectable (also on failure)
@@ -1392,31 +1296,28 @@ p25_lsd_fec_16x8_soft(uint8_t* bits16, const int16_t llr16[16]) {
 }
 
 
+static int
+check_p25_crc16(const char* who, const uint8_t* bytes, int item_bytes, const uint8_t* ok) {
+    return (bytes && ok && item_bytes >= 3) ? DDN_OK : ddn_bad_argument(who);
+}
+
 // ---- CRC-CCITT16 of decoded trunking blocks ---------------------------------------------------------------------------------
 extern "C" int
 ddn_fec_p25_crc16_batch(const uint8_t* d_bytes, int item_bytes, size_t n, uint8_t* d_ok, void* hip_stream) {
-    if (!d_bytes || !d_ok || item_bytes < 3) {
-        ddn_set_error("ddn_fec_p25_crc16_batch: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_p25_crc16(__func__, d_bytes, item_bytes, d_ok));
     HIP_TRY(ddn_dev_p25_crc16(d_bytes, item_bytes, (int)n, d_ok, (hipStream_t)hip_stream));
     return DDN_OK;
 }
 
 extern "C" int
 ddn_fec_p25_crc16_host(const uint8_t* bytes, int item_bytes, size_t n, uint8_t* ok) {
-    if (!bytes || !ok || item_bytes < 3) {
-        return DDN_EINVAL;
-    }
-    Dev b(n * (size_t)item_bytes), o(n);
-    if (!b.p || !o.p || b.up(bytes)) {
-        return no_dev();
-    }
-    int rc = ddn_fec_p25_crc16_batch((const uint8_t*)b.p, item_bytes, n, (uint8_t*)o.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    return o.down(ok) ? no_dev() : DDN_OK;
+    DDN_TRY(check_p25_crc16(__func__, bytes, item_bytes, ok));
+    DdnStaged s;
+    const uint8_t* b = s.in(bytes, n * (size_t)item_bytes);
+    uint8_t* o = s.out(ok, n);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_p25_crc16_batch(b, item_bytes, n, o, nullptr));
+    return s.finish();
 }
 
 // reference name (include/dsd-neo/protocol/p25/p25_crc.h): payload = len + 16 ints holding one bit each; 0 good, 65535 bad

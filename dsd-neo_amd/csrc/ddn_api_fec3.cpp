@@ -23,26 +23,16 @@ code_shape(int code, int* n, int* k) {
 }
 
 static int
-have_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        ddn_set_error("no HIP device available");
-        return DDN_ENODEV;
-    }
-    return DDN_OK;
+check_block_code(const char* who, int code, const uint8_t* bits, size_t n_items, int nb_codewords, int* n, int* k) {
+    return (code_shape(code, n, k) == DDN_OK && nb_codewords >= 1 && (!n_items || bits)) ? DDN_OK : ddn_bad_argument(who);
 }
 
 extern "C" int
 ddn_fec_block_code_batch(int code, uint8_t* d_bits, size_t n_items, int nb_codewords, uint8_t* d_decoded, uint8_t* d_ok,
                          void* hip_stream) {
     int n, k;
-    if (code_shape(code, &n, &k) != DDN_OK || nb_codewords < 1 || (n_items && !d_bits)) {
-        ddn_set_error("ddn_fec_block_code_batch: bad argument");
-        return DDN_EINVAL;
-    }
-    if (have_device() != DDN_OK) {
-        return DDN_ENODEV;
-    }
+    DDN_TRY(check_block_code(__func__, code, d_bits, n_items, nb_codewords, &n, &k));
+    DDN_TRY(ddn_have_device());
     const bool multi = code >= DDN_CODE_HAMMING_12_8 && code <= DDN_CODE_HAMMING_16_11_4;
     HIP_TRY(ddn_dev_block_code(code, d_bits, n_items, multi ? nb_codewords : 1, multi ? d_decoded : nullptr, d_ok,
                                (hipStream_t)hip_stream));
@@ -52,79 +42,50 @@ ddn_fec_block_code_batch(int code, uint8_t* d_bits, size_t n_items, int nb_codew
 extern "C" int
 ddn_fec_block_code_host(int code, uint8_t* bits, size_t n_items, int nb_codewords, uint8_t* decoded, uint8_t* ok) {
     int n, k;
-    if (code_shape(code, &n, &k) != DDN_OK || nb_codewords < 1 || (n_items && !bits)) {
-        return DDN_EINVAL;
-    }
-    if (have_device() != DDN_OK) {
-        return DDN_ENODEV;
-    }
+    DDN_TRY(check_block_code(__func__, code, bits, n_items, nb_codewords, &n, &k));
     const bool multi = code >= DDN_CODE_HAMMING_12_8 && code <= DDN_CODE_HAMMING_16_11_4;
     const int nb = multi ? nb_codewords : 1;
-    const size_t nbits = n_items * (size_t)n * (size_t)nb, ndec = n_items * (size_t)k * (size_t)nb;
-    uint8_t *d_b = nullptr, *d_d = nullptr, *d_o = nullptr;
-    int rc = DDN_OK;
-    if (hipMalloc(&d_b, nbits + 4) != hipSuccess || hipMalloc(&d_d, ndec + 4) != hipSuccess
-        || hipMalloc(&d_o, n_items + 4) != hipSuccess) {
-        rc = DDN_ENOMEM;
-    } else if (hipMemcpy(d_b, bits, nbits, hipMemcpyHostToDevice) != hipSuccess
-               || hipMemset(d_d, 0, ndec + 4) != hipSuccess
-               || ddn_dev_block_code(code, d_b, n_items, nb, (multi && decoded) ? d_d : nullptr, d_o, nullptr) != hipSuccess
-               || hipMemcpy(bits, d_b, nbits, hipMemcpyDeviceToHost) != hipSuccess
-               || (multi && decoded && hipMemcpy(decoded, d_d, ndec, hipMemcpyDeviceToHost) != hipSuccess)
-               || (ok && hipMemcpy(ok, d_o, n_items, hipMemcpyDeviceToHost) != hipSuccess)) {
-        rc = DDN_EHIP;
-    }
-    (void)hipFree(d_b);
-    (void)hipFree(d_d);
-    (void)hipFree(d_o);
-    return rc;
+    DdnStaged s;
+    uint8_t* b = s.inout(bits, n_items * (size_t)n * (size_t)nb);
+    uint8_t* d = (multi && decoded) ? s.out(decoded, n_items * (size_t)k * (size_t)nb) : nullptr;
+    uint8_t* o = s.out(ok, n_items);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_block_code_batch(code, b, n_items, nb_codewords, d, o, nullptr));
+    return s.finish();
+}
+
+// (the other pairs of this file: with items to decode, the input and the required output are there)
+static int
+check_in_out(const char* who, size_t n, const uint8_t* in, const uint8_t* out) {
+    return (!n || (in && out)) ? DDN_OK : ddn_bad_argument(who);
 }
 
 extern "C" int
 ddn_fec_bptc_196x96_batch(const uint8_t* d_in196, int deinterleave, size_t n, uint8_t* d_out96, uint8_t* d_r3,
                           uint32_t* d_errs, void* hip_stream) {
-    if (n && (!d_in196 || !d_out96)) {
-        ddn_set_error("ddn_fec_bptc_196x96_batch: null argument");
-        return DDN_EINVAL;
-    }
-    if (have_device() != DDN_OK) {
-        return DDN_ENODEV;
-    }
+    DDN_TRY(check_in_out(__func__, n, d_in196, d_out96));
+    DDN_TRY(ddn_have_device());
     HIP_TRY(ddn_dev_bptc_196x96(d_in196, deinterleave, n, d_out96, d_r3, d_errs, (hipStream_t)hip_stream));
     return DDN_OK;
 }
 
 extern "C" int
 ddn_fec_bptc_196x96_host(const uint8_t* in196, int deinterleave, size_t n, uint8_t* out96, uint8_t* r3, uint32_t* errs) {
-    if (n && (!in196 || !out96)) {
-        return DDN_EINVAL;
-    }
-    if (have_device() != DDN_OK) {
-        return DDN_ENODEV;
-    }
-    uint8_t *d_i = nullptr, *d_o = nullptr, *d_r = nullptr;
-    uint32_t* d_e = nullptr;
-    int rc = DDN_OK;
-    if (hipMalloc(&d_i, n * 196 + 4) != hipSuccess || hipMalloc(&d_o, n * 96 + 4) != hipSuccess
-        || hipMalloc(&d_r, n * 3 + 4) != hipSuccess || hipMalloc(&d_e, n * 4 + 4) != hipSuccess) {
-        rc = DDN_ENOMEM;
-    } else if (hipMemcpy(d_i, in196, n * 196, hipMemcpyHostToDevice) != hipSuccess
-               || ddn_dev_bptc_196x96(d_i, deinterleave, n, d_o, d_r, d_e, nullptr) != hipSuccess
-               || hipMemcpy(out96, d_o, n * 96, hipMemcpyDeviceToHost) != hipSuccess
-               || (r3 && hipMemcpy(r3, d_r, n * 3, hipMemcpyDeviceToHost) != hipSuccess)
-               || (errs && hipMemcpy(errs, d_e, n * 4, hipMemcpyDeviceToHost) != hipSuccess)) {
-        rc = DDN_EHIP;
-    }
-    (void)hipFree(d_i);
-    (void)hipFree(d_o);
-    (void)hipFree(d_r);
-    (void)hipFree(d_e);
-    return rc;
+    DDN_TRY(check_in_out(__func__, n, in196, out96));
+    DdnStaged s;
+    const uint8_t* i = s.in(in196, n * 196);
+    uint8_t* o = s.out(out96, n * 96);
+    uint8_t* r = s.out(r3, n * 3);
+    uint32_t* e = s.out(errs, n * 4);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_bptc_196x96_batch(i, deinterleave, n, o, r, e, nullptr));
+    return s.finish();
 }
 
 // BPTC 128x77 (kind 0: item 128 bytes -> 77) and reverse-channel BPTC 16x2 (kind 1 even / 2 odd parity: 32 -> 32)
 static int
-bptc_small(int kind, const uint8_t* d_in, size_t n, uint8_t* d_out, uint32_t* d_errs, hipStream_t st) {
+bptc_small(const char* who, int kind, const uint8_t* d_in, size_t n, uint8_t* d_out, uint32_t* d_errs, hipStream_t st) {
+    DDN_TRY(check_in_out(who, n, d_in, d_out));
     hipError_t e = kind == 0 ? ddn_dev_bptc_128x77(d_in, n, d_out, d_errs, st) : ddn_dev_bptc_16x2(d_in, n, kind == 2, d_out, d_errs, st);
     if (e != hipSuccess) {
         ddn_set_error("bptc kernel launch failed: %s", hipGetErrorString(e));
@@ -134,64 +95,42 @@ bptc_small(int kind, const uint8_t* d_in, size_t n, uint8_t* d_out, uint32_t* d_
 }
 
 static int
-bptc_small_host(int kind, const uint8_t* in, size_t n, uint8_t* out, uint32_t* errs) {
-    const size_t ni = kind == 0 ? 128 : 32, no = kind == 0 ? 77 : 32;
-    if (n && (!in || !out)) {
-        return DDN_EINVAL;
-    }
-    if (have_device() != DDN_OK) {
-        return DDN_ENODEV;
-    }
-    uint8_t *d_i = nullptr, *d_o = nullptr;
-    uint32_t* d_e = nullptr;
-    int rc = DDN_OK;
-    if (hipMalloc(&d_i, n * ni + 4) != hipSuccess || hipMalloc(&d_o, n * no + 4) != hipSuccess
-        || hipMalloc(&d_e, n * 4 + 4) != hipSuccess) {
-        rc = DDN_ENOMEM;
-    } else if (hipMemcpy(d_i, in, n * ni, hipMemcpyHostToDevice) != hipSuccess || bptc_small(kind, d_i, n, d_o, d_e, nullptr) != DDN_OK
-               || hipMemcpy(out, d_o, n * no, hipMemcpyDeviceToHost) != hipSuccess
-               || (errs && hipMemcpy(errs, d_e, n * 4, hipMemcpyDeviceToHost) != hipSuccess)) {
-        rc = DDN_EHIP;
-    }
-    (void)hipFree(d_i);
-    (void)hipFree(d_o);
-    (void)hipFree(d_e);
-    return rc;
+bptc_small_host(const char* who, int kind, const uint8_t* in, size_t n, uint8_t* out, uint32_t* errs) {
+    DDN_TRY(check_in_out(who, n, in, out));
+    DdnStaged s;
+    const uint8_t* i = s.in(in, n * (kind == 0 ? 128 : 32));
+    uint8_t* o = s.out(out, n * (kind == 0 ? 77 : 32));
+    uint32_t* e = s.out(errs, n * 4);
+    DDN_TRY(s.staged());
+    DDN_TRY(bptc_small(who, kind, i, n, o, e, nullptr));
+    return s.finish();
 }
 
 extern "C" int
 ddn_fec_bptc_128x77_batch(const uint8_t* d_in128, size_t n, uint8_t* d_out77, uint32_t* d_errs, void* stream) {
-    if (n && (!d_in128 || !d_out77)) {
-        ddn_set_error("ddn_fec_bptc_128x77_batch: null argument");
-        return DDN_EINVAL;
-    }
-    return bptc_small(0, d_in128, n, d_out77, d_errs, (hipStream_t)stream);
+    return bptc_small(__func__, 0, d_in128, n, d_out77, d_errs, (hipStream_t)stream);
 }
 
 extern "C" int
 ddn_fec_bptc_128x77_host(const uint8_t* in128, size_t n, uint8_t* out77, uint32_t* errs) {
-    return bptc_small_host(0, in128, n, out77, errs);
+    return bptc_small_host(__func__, 0, in128, n, out77, errs);
 }
 
 extern "C" int
 ddn_fec_bptc_16x2_batch(const uint8_t* d_in32, size_t n, int parity_odd, uint8_t* d_out32, uint32_t* d_errs, void* stream) {
-    if (n && (!d_in32 || !d_out32)) {
-        ddn_set_error("ddn_fec_bptc_16x2_batch: null argument");
-        return DDN_EINVAL;
-    }
-    return bptc_small(parity_odd ? 2 : 1, d_in32, n, d_out32, d_errs, (hipStream_t)stream);
+    return bptc_small(__func__, parity_odd ? 2 : 1, d_in32, n, d_out32, d_errs, (hipStream_t)stream);
 }
 
 extern "C" int
 ddn_fec_bptc_16x2_host(const uint8_t* in32, size_t n, int parity_odd, uint8_t* out32, uint32_t* errs) {
-    return bptc_small_host(parity_odd ? 2 : 1, in32, n, out32, errs);
+    return bptc_small_host(__func__, parity_odd ? 2 : 1, in32, n, out32, errs);
 }
 
 extern "C" uint32_t
 BPTC_128x77_Extract_Data(uint8_t InputDataMatrix[8][16], uint8_t DMRDataExtracted[77]) {
     uint32_t errs = 0xFFFFFFFFu;
     if (!InputDataMatrix || !DMRDataExtracted
-        || bptc_small_host(0, &InputDataMatrix[0][0], 1, DMRDataExtracted, &errs) != DDN_OK) {
+        || bptc_small_host(__func__, 0, &InputDataMatrix[0][0], 1, DMRDataExtracted, &errs) != DDN_OK) {
         return 0xFFFFFFFFu;
     }
     return errs;
@@ -201,26 +140,28 @@ extern "C" uint32_t
 BPTC_16x2_Extract_Data(uint8_t InputInterleavedData[32], uint8_t DMRDataExtracted[32], uint32_t ParityCheckTypeOdd) {
     uint32_t errs = 0xFFFFFFFFu;
     if (!InputInterleavedData || !DMRDataExtracted
-        || bptc_small_host(ParityCheckTypeOdd ? 2 : 1, InputInterleavedData, 1, DMRDataExtracted, &errs) != DDN_OK) {
+        || bptc_small_host(__func__, ParityCheckTypeOdd ? 2 : 1, InputInterleavedData, 1, DMRDataExtracted, &errs) != DDN_OK) {
         return 0xFFFFFFFFu;
     }
     return errs;
 }
 
+static int
+check_trellis(const char* who, const uint8_t* source_bits, int source_stride, size_t n, int result_len, const uint8_t* result_bits,
+              int result_stride) {
+    DDN_TRY(check_in_out(who, n, source_bits, result_bits));
+    if (result_len <= 0 || source_stride < 2 * result_len + 6 || result_stride < result_len) {
+        ddn_set_error("%s: a row needs 2 * result_len + 6 source bits (the last bit looks 8 ahead)", who);
+        return DDN_ERANGE;
+    }
+    return DDN_OK;
+}
+
 extern "C" int
 ddn_fec_trellis_decode_batch(const uint8_t* d_source_bits, int source_stride, size_t n, int result_len, uint8_t* d_result_bits,
                              int result_stride, void* hip_stream) {
-    if (n && (!d_source_bits || !d_result_bits)) {
-        ddn_set_error("ddn_fec_trellis_decode_batch: null argument");
-        return DDN_EINVAL;
-    }
-    if (result_len <= 0 || source_stride < 2 * result_len + 6 || result_stride < result_len) {
-        ddn_set_error("ddn_fec_trellis_decode_batch: a row needs 2 * result_len + 6 source bits (the last bit looks 8 ahead)");
-        return DDN_ERANGE;
-    }
-    if (have_device() != DDN_OK) {
-        return DDN_ENODEV;
-    }
+    DDN_TRY(check_trellis(__func__, d_source_bits, source_stride, n, result_len, d_result_bits, result_stride));
+    DDN_TRY(ddn_have_device());
     HIP_TRY(ddn_dev_trellis_greedy(d_source_bits, source_stride, n, result_len, d_result_bits, result_stride, (hipStream_t)hip_stream));
     return DDN_OK;
 }
@@ -228,28 +169,13 @@ ddn_fec_trellis_decode_batch(const uint8_t* d_source_bits, int source_stride, si
 extern "C" int
 ddn_fec_trellis_decode_host(const uint8_t* source_bits, int source_stride, size_t n, int result_len, uint8_t* result_bits,
                             int result_stride) {
-    if (n && (!source_bits || !result_bits)) {
-        return DDN_EINVAL;
-    }
-    if (result_len <= 0 || source_stride < 2 * result_len + 6 || result_stride < result_len) {
-        return DDN_ERANGE;
-    }
-    if (have_device() != DDN_OK) {
-        return DDN_ENODEV;
-    }
-    uint8_t *d_s = nullptr, *d_o = nullptr;
-    int rc = DDN_OK;
-    if (hipMalloc(&d_s, n * (size_t)source_stride + 4) != hipSuccess || hipMalloc(&d_o, n * (size_t)result_stride + 4) != hipSuccess) {
-        rc = DDN_ENOMEM;
-    } else if (hipMemcpy(d_s, source_bits, n * (size_t)source_stride, hipMemcpyHostToDevice) != hipSuccess
-               || hipMemset(d_o, 0, n * (size_t)result_stride) != hipSuccess
-               || ddn_dev_trellis_greedy(d_s, source_stride, n, result_len, d_o, result_stride, nullptr) != hipSuccess
-               || hipMemcpy(result_bits, d_o, n * (size_t)result_stride, hipMemcpyDeviceToHost) != hipSuccess) {
-        rc = DDN_EHIP;
-    }
-    (void)hipFree(d_s);
-    (void)hipFree(d_o);
-    return rc;
+    DDN_TRY(check_trellis(__func__, source_bits, source_stride, n, result_len, result_bits, result_stride));
+    DdnStaged s;
+    const uint8_t* i = s.in(source_bits, n * (size_t)source_stride);
+    uint8_t* o = s.out(result_bits, n * (size_t)result_stride);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_trellis_decode_batch(i, source_stride, n, result_len, o, result_stride, nullptr));
+    return s.finish();
 }
 
 // drop-in: include/dsd-neo/fec/trellis.h:22.  The reference reads source[2p .. 2p+7] for p < result_len, i.e. the caller's buffer
@@ -265,43 +191,23 @@ trellis_decode(uint8_t result[], const uint8_t source[], int result_len) {
 extern "C" int
 ddn_fec_rs_12_9_batch(uint8_t* d_codewords12, size_t n, uint8_t* d_result, uint8_t* d_errors_found, uint8_t* d_syndrome3,
                       void* hip_stream) {
-    if (n && (!d_codewords12 || !d_result)) {
-        ddn_set_error("ddn_fec_rs_12_9_batch: null argument");
-        return DDN_EINVAL;
-    }
-    if (have_device() != DDN_OK) {
-        return DDN_ENODEV;
-    }
+    DDN_TRY(check_in_out(__func__, n, d_codewords12, d_result));
+    DDN_TRY(ddn_have_device());
     HIP_TRY(ddn_dev_rs_12_9(d_codewords12, n, d_result, d_errors_found, d_syndrome3, (hipStream_t)hip_stream));
     return DDN_OK;
 }
 
 extern "C" int
 ddn_fec_rs_12_9_host(uint8_t* codewords12, size_t n, uint8_t* result, uint8_t* errors_found, uint8_t* syndrome3) {
-    if (n && (!codewords12 || !result)) {
-        return DDN_EINVAL;
-    }
-    if (have_device() != DDN_OK) {
-        return DDN_ENODEV;
-    }
-    uint8_t *d_c = nullptr, *d_r = nullptr, *d_f = nullptr, *d_s = nullptr;
-    int rc = DDN_OK;
-    if (hipMalloc(&d_c, n * 12 + 4) != hipSuccess || hipMalloc(&d_r, n + 4) != hipSuccess
-        || hipMalloc(&d_f, n + 4) != hipSuccess || hipMalloc(&d_s, n * 3 + 4) != hipSuccess) {
-        rc = DDN_ENOMEM;
-    } else if (hipMemcpy(d_c, codewords12, n * 12, hipMemcpyHostToDevice) != hipSuccess
-               || ddn_dev_rs_12_9(d_c, n, d_r, d_f, d_s, nullptr) != hipSuccess
-               || hipMemcpy(codewords12, d_c, n * 12, hipMemcpyDeviceToHost) != hipSuccess
-               || hipMemcpy(result, d_r, n, hipMemcpyDeviceToHost) != hipSuccess
-               || (errors_found && hipMemcpy(errors_found, d_f, n, hipMemcpyDeviceToHost) != hipSuccess)
-               || (syndrome3 && hipMemcpy(syndrome3, d_s, n * 3, hipMemcpyDeviceToHost) != hipSuccess)) {
-        rc = DDN_EHIP;
-    }
-    (void)hipFree(d_c);
-    (void)hipFree(d_r);
-    (void)hipFree(d_f);
-    (void)hipFree(d_s);
-    return rc;
+    DDN_TRY(check_in_out(__func__, n, codewords12, result));
+    DdnStaged s;
+    uint8_t* c = s.inout(codewords12, n * 12);
+    uint8_t* r = s.out(result, n);
+    uint8_t* f = s.out(errors_found, n);
+    uint8_t* y = s.out(syndrome3, n * 3);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fec_rs_12_9_batch(c, n, r, f, y, nullptr));
+    return s.finish();
 }
 
 // ---- the reference's names ---------------------------------------------------------------------------------------------

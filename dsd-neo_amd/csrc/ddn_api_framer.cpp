@@ -20,6 +20,7 @@ struct ddn_p25p1_framer {
     int32_t* d_tab[T_COUNT];
     int n_off[T_COUNT], max_off[T_COUNT];
     int32_t *d_first9, *d_status9;
+    DdnPool pool;
 };
 
 extern "C" int
@@ -28,11 +29,7 @@ ddn_p25p1_framer_create(int n_channels, int max_frames_per_channel, ddn_p25p1_fr
         ddn_set_error("ddn_p25p1_framer_create: bad argument");
         return DDN_EINVAL;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        ddn_set_error("no HIP device available");
-        return DDN_ENODEV;
-    }
+    DDN_TRY(ddn_have_device());
     ddn_p25p1_framer* f = new (std::nothrow) ddn_p25p1_framer();
     if (!f) {
         return DDN_ENOMEM;
@@ -60,13 +57,8 @@ ddn_p25p1_framer_create(int n_channels, int max_frames_per_channel, ddn_p25p1_fr
     int32_t first9[9], status9[9];
     ddn_p25p1_layout_ldu_imbe(first9, status9);
     const size_t slots = (size_t)n_channels * (size_t)max_frames_per_channel;
-    bool ok = hipMalloc(&f->d_sync_pos, sizeof(int32_t) * slots) == hipSuccess
-              && hipMalloc(&f->d_n_syncs, sizeof(int32_t) * (size_t)n_channels) == hipSuccess
-              && hipMemset(f->d_n_syncs, 0, sizeof(int32_t) * (size_t)n_channels) == hipSuccess
-              && hipMalloc(&f->d_dropped, sizeof(int32_t) * (size_t)n_channels) == hipSuccess
-              && hipMemset(f->d_dropped, 0, sizeof(int32_t) * (size_t)n_channels) == hipSuccess
-              && hipMalloc(&f->d_first9, sizeof(first9)) == hipSuccess
-              && hipMalloc(&f->d_status9, sizeof(status9)) == hipSuccess
+    bool ok = f->pool.alloc(&f->d_sync_pos, slots) && f->pool.alloc(&f->d_n_syncs, (size_t)n_channels)
+              && f->pool.alloc(&f->d_dropped, (size_t)n_channels) && f->pool.alloc(&f->d_first9, 9) && f->pool.alloc(&f->d_status9, 9)
               && hipMemcpy(f->d_first9, first9, sizeof(first9), hipMemcpyHostToDevice) == hipSuccess
               && hipMemcpy(f->d_status9, status9, sizeof(status9), hipMemcpyHostToDevice) == hipSuccess;
     for (int t = 0; ok && t < T_COUNT; t++) {
@@ -74,7 +66,7 @@ ddn_p25p1_framer_create(int n_channels, int max_frames_per_channel, ddn_p25p1_fr
         for (int i = 0; i < f->n_off[t]; i++) {
             f->max_off[t] = tab[t][i] > f->max_off[t] ? tab[t][i] : f->max_off[t];
         }
-        ok = hipMalloc(&f->d_tab[t], sizeof(int32_t) * (size_t)f->n_off[t]) == hipSuccess
+        ok = f->pool.alloc(&f->d_tab[t], (size_t)f->n_off[t])
              && hipMemcpy(f->d_tab[t], tab[t], sizeof(int32_t) * (size_t)f->n_off[t], hipMemcpyHostToDevice) == hipSuccess;
     }
     if (!ok) {
@@ -91,14 +83,7 @@ ddn_p25p1_framer_destroy(ddn_p25p1_framer* f) {
     if (!f) {
         return;
     }
-    (void)hipFree(f->d_sync_pos);
-    (void)hipFree(f->d_n_syncs);
-    (void)hipFree(f->d_dropped);
-    (void)hipFree(f->d_first9);
-    (void)hipFree(f->d_status9);
-    for (int t = 0; t < T_COUNT; t++) {
-        (void)hipFree(f->d_tab[t]);
-    }
+    f->pool.release();
     delete f;
 }
 

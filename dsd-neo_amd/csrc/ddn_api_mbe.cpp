@@ -28,16 +28,6 @@ struct ddn_mbe_batch {
     float last_ms[2];
 };
 
-static int
-have_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        ddn_set_error("no HIP device available");
-        return DDN_ENODEV;
-    }
-    return DDN_OK;
-}
-
 extern "C" int
 ddn_mbe_frame_decode_batch(int codec, const uint8_t* d_frames, const uint8_t* d_soft, size_t n, uint8_t* d_bits,
                            int32_t* d_result, void* hip_stream) {
@@ -45,9 +35,7 @@ ddn_mbe_frame_decode_batch(int codec, const uint8_t* d_frames, const uint8_t* d_
         ddn_set_error("ddn_mbe_frame_decode_batch: bad argument");
         return DDN_EINVAL;
     }
-    if (have_device() != DDN_OK) {
-        return DDN_ENODEV;
-    }
+    DDN_TRY(ddn_have_device());
     HIP_TRY(ddn_dev_mbe_frame_decode(codec, d_frames, d_soft, n, d_bits, d_result, (hipStream_t)hip_stream));
     return DDN_OK;
 }
@@ -81,9 +69,7 @@ ddn_mbe_batch_create(int codec, int n_streams, ddn_mbe_batch** out) {
         ddn_set_error("ddn_mbe_batch_create: bad argument");
         return DDN_EINVAL;
     }
-    if (have_device() != DDN_OK) {
-        return DDN_ENODEV;
-    }
+    DDN_TRY(ddn_have_device());
     ddn_mbe_batch* b = new (std::nothrow) ddn_mbe_batch();
     if (!b) {
         return DDN_ENOMEM;
@@ -405,9 +391,7 @@ scratch_ready(Scratch& s) {
     if (s.ok) {
         return DDN_OK;
     }
-    if (have_device() != DDN_OK) {
-        return DDN_ENODEV;
-    }
+    DDN_TRY(ddn_have_device());
     if (hipMalloc(&s.d_in, 256) != hipSuccess || hipMalloc(&s.d_soft, 256) != hipSuccess
         || hipMalloc(&s.d_bits, 128) != hipSuccess || hipMalloc(&s.d_res, sizeof(int32_t) * 10) != hipSuccess
         || hipMalloc(&s.d_pcm, sizeof(float) * 160) != hipSuccess) {

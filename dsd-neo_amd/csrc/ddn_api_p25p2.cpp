@@ -12,43 +12,6 @@
 #include "ddn_p25p2_seq.h"
 
 namespace {
-// stream-ordered scratch: arenas (one hipMallocAsync each, carved by get()), released when the call leaves (also on its error paths)
-struct Scratch {
-    hipStream_t st;
-    void* p[4];
-    int n = 0;
-    uint8_t* cur = nullptr;
-    size_t left = 0;
-    explicit Scratch(hipStream_t s) : st(s) {}
-    ~Scratch() {
-        for (int i = 0; i < n; i++) {
-            (void)hipFreeAsync(p[i], st);
-        }
-    }
-    hipError_t arena(size_t bytes) {
-        void* q = nullptr;
-        const hipError_t e = n < 4 ? hipMallocAsync(&q, bytes + 256, st) : hipErrorOutOfMemory;
-        if (e == hipSuccess) {
-            p[n++] = q;
-            cur = (uint8_t*)q;
-            left = bytes + 256;
-        }
-        return e;
-    }
-    static size_t pad(size_t b) { return (b + 255) & ~(size_t)255; }
-    template <class T>
-    hipError_t get(T** out, size_t count) {
-        const size_t b = pad((count ? count : 1) * sizeof(T));
-        if (b > left) {
-            *out = nullptr;
-            return hipErrorOutOfMemory;
-        }
-        *out = (T*)cur;
-        cur += b;
-        left -= b;
-        return hipSuccess;
-    }
-};
 // The decoder classes of a call are independent of each other and each is a chain of latency-bound launches (an RS decode is ~0.5 ms
 // deep for its thread): FACCH, SACCH / LCCH and the voice bursts (with the ESS) run on three streams of the calling thread's own,
 // side by side, between the call's host wait and its last kernel.
@@ -100,21 +63,27 @@ struct AuxGuard {
 };
 } // namespace
 
+static int
+check_groups(const char* who, const uint8_t* bits1400, const int16_t* llr1400, int n_channels, int n_groups, const uint64_t* seed44,
+             const ddn_p25p2_seq_state* state, const int32_t* info, const uint8_t* payload, const uint8_t* ambe_fr, const uint8_t* ambe_rel,
+             const uint8_t* ess) {
+    return (bits1400 && llr1400 && seed44 && state && info && payload && ambe_fr && ambe_rel && ess && n_channels >= 0 && n_groups >= 0
+            && (size_t)n_channels * (size_t)n_groups * 4 <= 0x7fffffffu / 360)
+               ? DDN_OK
+               : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_p25p2_groups_batch(const uint8_t* d_bits1400, const int16_t* d_llr1400, int n_channels, int n_groups, const int32_t* d_groups_of,
                        const uint64_t* d_seed44, ddn_p25p2_seq_state* d_state, int threshold, int32_t* d_info, uint8_t* d_payload, uint8_t* d_ambe_fr,
                        uint8_t* d_ambe_rel, uint8_t* d_ess, void* hip_stream) {
-    if (!d_bits1400 || !d_llr1400 || !d_seed44 || !d_state || !d_info || !d_payload || !d_ambe_fr || !d_ambe_rel || !d_ess || n_channels < 0
-        || n_groups < 0 || (size_t)n_channels * (size_t)n_groups * 4 > 0x7fffffffu / 360) {
-        ddn_set_error("ddn_p25p2_groups_batch: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_groups(__func__, d_bits1400, d_llr1400, n_channels, n_groups, d_seed44, d_state, d_info, d_payload, d_ambe_fr, d_ambe_rel, d_ess));
     if (n_channels == 0 || n_groups == 0) {
         return DDN_OK;
     }
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t n_gr = (size_t)n_channels * n_groups, n_rows = n_gr * 4;
-    Scratch s(st);
+    DdnScratch s(st);
     uint8_t *rb, *xb, *seq;
     int16_t *rl, *xl;
     int32_t *duid, *isch, *row_off, *counts, *list, *ess_src, *final_src, *seq_of;
@@ -228,15 +197,20 @@ ddn_p25p2_groups_batch(const uint8_t* d_bits1400, const int16_t* d_llr1400, int 
     return DDN_OK;
 }
 
+static int
+check_sync_cut(const char* who, const uint8_t* dibits, const int16_t* llr2, int n_channels, int n, size_t stride, int max_groups,
+               const int32_t* n_groups, const int32_t* group_pos, const int32_t* cursor_out, const uint8_t* bits1400, const int16_t* llr1400) {
+    return (dibits && llr2 && n_groups && group_pos && cursor_out && bits1400 && llr1400 && n_channels >= 0 && n >= 0 && max_groups >= 0
+            && stride >= (size_t)n && max_groups <= 65535)
+               ? DDN_OK
+               : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_p25p2_sync_cut_batch(const uint8_t* d_dibits, const int16_t* d_llr2, int n_channels, int n, size_t stride, const int32_t* d_cursor_in,
                          int max_groups, int32_t* d_n_groups, int32_t* d_group_pos, int32_t* d_cursor_out, uint8_t* d_bits1400, int16_t* d_llr1400,
                          void* hip_stream) {
-    if (!d_dibits || !d_llr2 || !d_n_groups || !d_group_pos || !d_cursor_out || !d_bits1400 || !d_llr1400 || n_channels < 0 || n < 0
-        || max_groups < 0 || stride < (size_t)n || max_groups > 65535) {
-        ddn_set_error("ddn_p25p2_sync_cut_batch: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_sync_cut(__func__, d_dibits, d_llr2, n_channels, n, stride, max_groups, d_n_groups, d_group_pos, d_cursor_out, d_bits1400, d_llr1400));
     if (n_channels == 0) {
         return DDN_OK;
     }
@@ -245,86 +219,51 @@ ddn_p25p2_sync_cut_batch(const uint8_t* d_dibits, const int16_t* d_llr2, int n_c
     return DDN_OK;
 }
 
-namespace {
-struct Dev {
-    void* p = nullptr;
-    size_t bytes;
-    explicit Dev(size_t b) : bytes(b) {
-        if (hipMalloc(&p, b ? b : 4) != hipSuccess) {
-            p = nullptr;
-        }
-    }
-    ~Dev() { (void)hipFree(p); }
-    Dev(const Dev&) = delete;
-    Dev& operator=(const Dev&) = delete;
-    int up(const void* h) { return hipMemcpy(p, h, bytes, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1; }
-    int down(void* h) { return hipMemcpy(h, p, bytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1; }
-};
-
-int
-no_dev() {
-    ddn_set_error("device allocation/copy failed (no HIP device?)");
-    return DDN_ENODEV;
-}
-} // namespace
-
 extern "C" int
 ddn_p25p2_groups_host(const uint8_t* bits1400, const int16_t* llr1400, int n_channels, int n_groups, const int32_t* groups_of,
                       const uint64_t* seed44, ddn_p25p2_seq_state* state, int threshold, int32_t* info, uint8_t* payload, uint8_t* ambe_fr,
                       uint8_t* ambe_rel, uint8_t* ess) {
-    if (!bits1400 || !llr1400 || !seed44 || !state || !info || !payload || !ambe_fr || !ambe_rel || !ess || n_channels < 0 || n_groups < 0) {
-        ddn_set_error("ddn_p25p2_groups_host: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_groups(__func__, bits1400, llr1400, n_channels, n_groups, seed44, state, info, payload, ambe_fr, ambe_rel, ess));
     if (n_channels == 0 || n_groups == 0) {
         return DDN_OK;
     }
     const size_t ng = (size_t)n_channels * n_groups, nr = ng * 4;
-    Dev b(ng * 1400), l(ng * 2800), go((size_t)n_channels * 4), sd((size_t)n_channels * 8), st((size_t)n_channels * sizeof(ddn_p25p2_seq_state));
-    Dev oi(nr * 32), op(nr * 180), of(nr * 384), orl(nr * 384), oe(nr * 96);
-    if (!b.p || !l.p || !go.p || !sd.p || !st.p || !oi.p || !op.p || !of.p || !orl.p || !oe.p || b.up(bits1400) || l.up(llr1400)
-        || (groups_of && go.up(groups_of)) || sd.up(seed44) || st.up(state) || oi.up(info) || op.up(payload) || of.up(ambe_fr) || orl.up(ambe_rel)
-        || oe.up(ess)) {
-        return no_dev();
-    }
-    const int rc = ddn_p25p2_groups_batch((const uint8_t*)b.p, (const int16_t*)l.p, n_channels, n_groups, groups_of ? (const int32_t*)go.p : nullptr,
-                                          (const uint64_t*)sd.p, (ddn_p25p2_seq_state*)st.p, threshold, (int32_t*)oi.p, (uint8_t*)op.p,
-                                          (uint8_t*)of.p, (uint8_t*)orl.p, (uint8_t*)oe.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    if (st.down(state) || oi.down(info) || op.down(payload) || of.down(ambe_fr) || orl.down(ambe_rel) || oe.down(ess)) {
-        return no_dev();
-    }
-    return DDN_OK;
+    DdnStaged s;
+    const uint8_t* b = s.in(bits1400, ng * 1400);
+    const int16_t* l = s.in(llr1400, ng * 2800);
+    const int32_t* go = s.in_opt(groups_of, (size_t)n_channels * 4);
+    const uint64_t* sd = s.in(seed44, (size_t)n_channels * 8);
+    ddn_p25p2_seq_state* st = s.inout(state, (size_t)n_channels * sizeof(ddn_p25p2_seq_state));
+    int32_t* oi = s.inout(info, nr * 32);
+    uint8_t* op = s.inout(payload, nr * 180);
+    uint8_t* of = s.inout(ambe_fr, nr * 384);
+    uint8_t* orl = s.inout(ambe_rel, nr * 384);
+    uint8_t* oe = s.inout(ess, nr * 96);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_p25p2_groups_batch(b, l, n_channels, n_groups, go, sd, st, threshold, oi, op, of, orl, oe, nullptr));
+    HIP_TRY(hipDeviceSynchronize()); // (the call's side streams do not block the null stream)
+    return s.finish();
 }
 
 extern "C" int
 ddn_p25p2_sync_cut_host(const uint8_t* dibits, const int16_t* llr2, int n_channels, int n, size_t stride, const int32_t* cursor_in, int max_groups,
                         int32_t* n_groups, int32_t* group_pos, int32_t* cursor_out, uint8_t* bits1400, int16_t* llr1400) {
-    if (!dibits || !llr2 || !n_groups || !group_pos || !cursor_out || !bits1400 || !llr1400 || n_channels < 0 || n < 0 || max_groups < 0
-        || stride < (size_t)n) {
-        ddn_set_error("ddn_p25p2_sync_cut_host: bad argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_sync_cut(__func__, dibits, llr2, n_channels, n, stride, max_groups, n_groups, group_pos, cursor_out, bits1400, llr1400));
     if (n_channels == 0) {
         return DDN_OK;
     }
     const size_t C = (size_t)n_channels, G = (size_t)max_groups;
-    Dev d(C * stride), l(C * stride * 4), ci(C * 4), ng(C * 4), gp(C * G * 4), co(C * 4), gb(C * G * 1400), gl(C * G * 2800);
-    if (!d.p || !l.p || !ci.p || !ng.p || !gp.p || !co.p || !gb.p || !gl.p || d.up(dibits) || l.up(llr2) || (cursor_in && ci.up(cursor_in))
-        || gp.up(group_pos) || gb.up(bits1400) || gl.up(llr1400)) {
-        return no_dev();
-    }
-    const int rc = ddn_p25p2_sync_cut_batch((const uint8_t*)d.p, (const int16_t*)l.p, n_channels, n, stride, cursor_in ? (const int32_t*)ci.p : nullptr,
-                                            max_groups, (int32_t*)ng.p, (int32_t*)gp.p, (int32_t*)co.p, (uint8_t*)gb.p, (int16_t*)gl.p, nullptr);
-    if (rc != DDN_OK) {
-        return rc;
-    }
+    DdnStaged s;
+    const uint8_t* d = s.in(dibits, C * stride);
+    const int16_t* l = s.in(llr2, C * stride * 4);
+    const int32_t* ci = s.in_opt(cursor_in, C * 4);
+    int32_t* ng = s.out(n_groups, C * 4);
+    int32_t* gp = s.inout(group_pos, C * G * 4);
+    int32_t* co = s.out(cursor_out, C * 4);
+    uint8_t* gb = s.inout(bits1400, C * G * 1400);
+    int16_t* gl = s.inout(llr1400, C * G * 2800);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_p25p2_sync_cut_batch(d, l, n_channels, n, stride, ci, max_groups, ng, gp, co, gb, gl, nullptr));
     HIP_TRY(hipDeviceSynchronize());
-    if (ng.down(n_groups) || gp.down(group_pos) || co.down(cursor_out) || gb.down(bits1400) || gl.down(llr1400)) {
-        return no_dev();
-    }
-    return DDN_OK;
+    return s.finish();
 }

@@ -16,6 +16,7 @@ struct ddn_resampler {
     int n_channels, L, M, phase;
     float* d_taps; // [L][16]
     float* d_hist; // [B][15], oldest first
+    DdnPool pool;
 };
 
 static long long
@@ -30,11 +31,7 @@ ddn_resampler_create(int n_channels, int L, int M, ddn_resampler** out) {
         ddn_set_error("ddn_resampler_create: bad argument (1 <= L <= %d, 1 <= M <= 2^22)", DDN_RESAMP_MAX_L);
         return DDN_EINVAL;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        ddn_set_error("no HIP device available");
-        return DDN_ENODEV;
-    }
+    DDN_TRY(ddn_have_device());
     ddn_resampler* b = new (std::nothrow) ddn_resampler();
     float* taps = new (std::nothrow) float[(size_t)16 * L];
     if (!b || !taps) {
@@ -47,16 +44,12 @@ ddn_resampler_create(int n_channels, int L, int M, ddn_resampler** out) {
     b->L = L;
     b->M = M;
     ddn_design_resampler(L, M, taps);
-    const size_t hb = sizeof(float) * 15 * (size_t)n_channels;
-    const bool ok = hipMalloc(&b->d_taps, sizeof(float) * 16 * (size_t)L) == hipSuccess
-                    && hipMalloc(&b->d_hist, hb) == hipSuccess && hipMemset(b->d_hist, 0, hb) == hipSuccess
+    const bool ok = b->pool.alloc(&b->d_taps, 16 * (size_t)L) && b->pool.alloc(&b->d_hist, 15 * (size_t)n_channels)
                     && hipMemcpy(b->d_taps, taps, sizeof(float) * 16 * (size_t)L, hipMemcpyHostToDevice) == hipSuccess;
     delete[] taps;
     if (!ok) {
         ddn_set_error("ddn_resampler_create: device allocation failed");
-        (void)hipFree(b->d_taps);
-        (void)hipFree(b->d_hist);
-        delete b;
+        ddn_resampler_destroy(b);
         return DDN_ENOMEM;
     }
     *out = b;
@@ -68,8 +61,7 @@ ddn_resampler_destroy(ddn_resampler* b) {
     if (!b) {
         return;
     }
-    (void)hipFree(b->d_taps);
-    (void)hipFree(b->d_hist);
+    b->pool.release();
     delete b;
 }
 
@@ -97,12 +89,14 @@ ddn_resampler_get_taps(const ddn_resampler* b, float* taps, int cap) {
     return 16 * b->L;
 }
 
+static int
+check_resampler_run(const char* who, const ddn_resampler* b, const float* in, const float* out) {
+    return (b && in && out) ? DDN_OK : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_resampler_run(ddn_resampler* b, const float* d_in, size_t n, float* d_out, size_t out_stride, void* hip_stream) {
-    if (!b || !d_in || !d_out) {
-        ddn_set_error("ddn_resampler_run: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_resampler_run(__func__, b, d_in, d_out));
     const long long n_out = out_len_for((long long)n, b->L, b->M, b->phase);
     if ((size_t)n_out > out_stride) {
         ddn_set_error("ddn_resampler_run: out_stride %zu < %lld outputs (state unchanged)", out_stride, n_out);
@@ -116,29 +110,15 @@ ddn_resampler_run(ddn_resampler* b, const float* d_in, size_t n, float* d_out, s
 
 extern "C" int
 ddn_resampler_run_host(ddn_resampler* b, const float* in, size_t n, float* out, size_t out_stride) {
-    if (!b || !in || !out) {
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_resampler_run(__func__, b, in, out));
     const size_t B = (size_t)b->n_channels;
-    float *d_in = nullptr, *d_out = nullptr;
-    if (hipMalloc(&d_in, sizeof(float) * (B * n + 1)) != hipSuccess
-        || hipMalloc(&d_out, sizeof(float) * (B * out_stride + 1)) != hipSuccess) {
-        (void)hipFree(d_in);
-        ddn_set_error("ddn_resampler_run_host: device allocation failed (no device?)");
-        return DDN_ENODEV;
-    }
-    int rc = DDN_EHIP;
-    if (hipMemcpy(d_in, in, sizeof(float) * B * n, hipMemcpyHostToDevice) == hipSuccess) {
-        rc = ddn_resampler_run(b, d_in, n, d_out, out_stride, nullptr);
-        if (rc == DDN_OK
-            && (hipDeviceSynchronize() != hipSuccess
-                || hipMemcpy(out, d_out, sizeof(float) * B * out_stride, hipMemcpyDeviceToHost) != hipSuccess)) {
-            rc = DDN_EHIP;
-        }
-    }
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return rc;
+    DdnStaged s;
+    const float* i = s.in(in, sizeof(float) * B * n);
+    float* o = s.out(out, sizeof(float) * B * out_stride);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_resampler_run(b, i, n, o, out_stride, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    return s.finish();
 }
 
 // ---- drop-in: dsd_resampler_process_block() on a caller-owned reference state (one stream) ------------------------------
@@ -168,24 +148,16 @@ dsd_resampler_process_block(ddn_dsd_resampler_state* state, const float* in, int
     if (in_len == 0) {
         return 0;
     }
-    float *d_taps = nullptr, *d_hist = nullptr, *d_in = nullptr, *d_out = nullptr;
-    bool ok = hipMalloc(&d_taps, sizeof(float) * 16 * (size_t)L) == hipSuccess
-              && hipMalloc(&d_hist, sizeof(float) * 15) == hipSuccess
-              && hipMalloc(&d_in, sizeof(float) * (size_t)in_len) == hipSuccess
-              && hipMalloc(&d_out, sizeof(float) * (size_t)(n_out + 1)) == hipSuccess;
+    DdnStaged s;
+    const float* d_taps = s.in(state->taps, sizeof(float) * 16 * (size_t)L);
     // the window is hist[head .. head + 15], oldest first; the newest 15 are what the next outputs can still see
-    ok = ok && hipMemcpy(d_taps, state->taps, sizeof(float) * 16 * (size_t)L, hipMemcpyHostToDevice) == hipSuccess
-         && hipMemcpy(d_hist, state->hist + state->hist_head + 1, sizeof(float) * 15, hipMemcpyHostToDevice) == hipSuccess
-         && hipMemcpy(d_in, in, sizeof(float) * (size_t)in_len, hipMemcpyHostToDevice) == hipSuccess
-         && ddn_dev_resample(d_in, in_len, (size_t)in_len, 1, d_hist, d_taps, L, M, state->phase, (long)n_out, d_out,
-                             (size_t)n_out + 1, nullptr) == hipSuccess
-         && hipDeviceSynchronize() == hipSuccess
-         && (n_out == 0 || hipMemcpy(out, d_out, sizeof(float) * (size_t)n_out, hipMemcpyDeviceToHost) == hipSuccess);
-    (void)hipFree(d_taps);
-    (void)hipFree(d_hist);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    if (!ok) {
+    float* d_hist = s.in(state->hist + state->hist_head + 1, sizeof(float) * 15);
+    const float* d_in = s.in(in, sizeof(float) * (size_t)in_len);
+    float* d_out = s.out(out, sizeof(float) * (size_t)n_out);
+    if (s.staged() != DDN_OK
+        || ddn_dev_resample(d_in, in_len, (size_t)in_len, 1, d_hist, d_taps, L, M, state->phase, (long)n_out, d_out, (size_t)n_out + 1, nullptr)
+               != hipSuccess
+        || hipDeviceSynchronize() != hipSuccess || s.finish() != DDN_OK) {
         ddn_set_error("dsd_resampler_process_block: HIP path failed (no device?)");
         return -1;
     }

@@ -39,25 +39,13 @@ struct ddn_p25_rx {
     hipEvent_t ring[64][3];
     int ring_n, ring_head;
     hipEvent_t gate_event; // the next run's loop kernel waits for it (ddn_p25_rx_gate_loop)
+    DdnPool pool;
     hipEvent_t loop_event; // recorded between the matched filter and the loop kernel of the next run (ddn_p25_rx_mark_loop_start)
 };
 
 static void
 rx_free(ddn_p25_rx* b) {
-    (void)hipFree(b->d_state);
-    (void)hipFree(b->d_sbuf);
-    (void)hipFree(b->d_lbuf);
-    (void)hipFree(b->d_shist);
-    (void)hipFree(b->d_minring);
-    (void)hipFree(b->d_maxring);
-    (void)hipFree(b->d_fhist);
-    (void)hipFree(b->d_fstale);
-    (void)hipFree(b->d_filt);
-    (void)hipFree(b->d_lock);
-    (void)hipFree(b->d_hstate);
-    (void)hipFree(b->d_hh);
-    (void)hipFree(b->d_ev_dummy);
-    (void)hipFree(b->d_nev_dummy);
+    b->pool.release();
     for (int i = 0; i < 3; i++) {
         if (b->ev[i]) {
             (void)hipEventDestroy(b->ev[i]);
@@ -124,11 +112,7 @@ ddn_p25_rx_create(const ddn_p25_rx_config* cfg, ddn_p25_rx** out) {
         ddn_set_error("ddn_p25_rx_create: matched filter needs out_rate == 10 * sym_rate");
         return DDN_ERANGE;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        ddn_set_error("no HIP device available");
-        return DDN_ENODEV;
-    }
+    DDN_TRY(ddn_have_device());
     ddn_p25_rx* b = new (std::nothrow) ddn_p25_rx();
     if (!b) {
         return DDN_ENOMEM;
@@ -136,19 +120,11 @@ ddn_p25_rx_create(const ddn_p25_rx_config* cfg, ddn_p25_rx** out) {
     memset(b, 0, sizeof(*b));
     b->cfg = *cfg;
     const size_t B = (size_t)cfg->n_channels;
-    if (hipMalloc(&b->d_state, sizeof(DdnRxState) * B) != hipSuccess
-        || hipMalloc(&b->d_sbuf, sizeof(float) * 128 * B) != hipSuccess
-        || hipMalloc(&b->d_lbuf, sizeof(float) * 24 * B) != hipSuccess
-        || hipMalloc(&b->d_shist, sizeof(float) * 24 * B) != hipSuccess
-        || hipMalloc(&b->d_minring, sizeof(float) * 1024 * B) != hipSuccess
-        || hipMalloc(&b->d_maxring, sizeof(float) * 1024 * B) != hipSuccess
-        || hipMalloc(&b->d_fhist, sizeof(float) * 90 * B) != hipSuccess
-        || hipMalloc(&b->d_fstale, sizeof(float) * 90 * B) != hipSuccess
-        || hipMalloc(&b->d_hstate, sizeof(DdnP25HState) * B) != hipSuccess
-        || hipMalloc(&b->d_hh, sizeof(float) * 3 * 104 * B) != hipSuccess
-        || hipMalloc(&b->d_ev_dummy, sizeof(int32_t) * 4 * B) != hipSuccess
-        || hipMalloc(&b->d_nev_dummy, sizeof(int32_t) * B) != hipSuccess
-        || hipMalloc(&b->d_lock, sizeof(int32_t) * B) != hipSuccess || rx_fill(b) != DDN_OK
+    DdnPool& p = b->pool;
+    if (!p.alloc(&b->d_state, B) || !p.alloc(&b->d_sbuf, 128 * B) || !p.alloc(&b->d_lbuf, 24 * B) || !p.alloc(&b->d_shist, 24 * B)
+        || !p.alloc(&b->d_minring, 1024 * B) || !p.alloc(&b->d_maxring, 1024 * B) || !p.alloc(&b->d_fhist, 90 * B)
+        || !p.alloc(&b->d_fstale, 90 * B) || !p.alloc(&b->d_hstate, B) || !p.alloc(&b->d_hh, 3 * 104 * B) || !p.alloc(&b->d_ev_dummy, 4 * B)
+        || !p.alloc(&b->d_nev_dummy, B) || !p.alloc(&b->d_lock, B) || rx_fill(b) != DDN_OK
         || ddn_p25_rx_set_lock_symbols(b, nullptr) != DDN_OK) {
         ddn_set_error("ddn_p25_rx_create: device allocation failed");
         rx_free(b);
@@ -273,13 +249,15 @@ ddn_p25_rx_max_symbols(const ddn_p25_rx* b, size_t n) {
     return n / (size_t)(whole - 1) + 2;
 }
 
+static int
+check_p25_rx_run(const char* who, const ddn_p25_rx* b, const float* disc, const uint8_t* records10, const uint8_t* flags, const int32_t* counts) {
+    return (b && disc && records10 && flags && counts) ? DDN_OK : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_p25_rx_run(ddn_p25_rx* b, const float* d_disc, size_t n, uint8_t* d_records10, uint8_t* d_flags, int32_t* d_counts,
                size_t max_symbols, void* hip_stream) {
-    if (!b || !d_disc || !d_records10 || !d_flags || !d_counts) {
-        ddn_set_error("ddn_p25_rx_run: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_p25_rx_run(__func__, b, d_disc, d_records10, d_flags, d_counts));
     hipStream_t st = (hipStream_t)hip_stream;
     const int B = b->cfg.n_channels;
     if (n == 0) {
@@ -316,10 +294,8 @@ ddn_p25_rx_run(ddn_p25_rx* b, const float* d_disc, size_t n, uint8_t* d_records1
     if (b->cfg.use_matched_filter && !fused) {
         if (b->filt_cap < n) {
             HIP_TRY(hipStreamSynchronize(st));
-            (void)hipFree(b->d_filt);
-            b->d_filt = nullptr;
             b->filt_cap = 0;
-            HIP_TRY(hipMalloc(&b->d_filt, sizeof(float) * (size_t)B * n));
+            HIP_TRY(b->pool.realloc_bytes(&b->d_filt, sizeof(float) * (size_t)B * n));
             b->filt_cap = n;
         }
         HIP_TRY(ddn_dev_p25_matched_filter_only(d_disc, (long)n, n, B, b->d_fhist, b->d_filt, st));
@@ -430,65 +406,40 @@ ddn_p25_rx_get_timing(ddn_p25_rx* b, float* ms2) {
 extern "C" int
 ddn_p25_rx_run_host_ev(ddn_p25_rx* b, const float* disc, size_t n, uint8_t* records10, uint8_t* flags, int32_t* counts,
                        size_t max_symbols, int32_t* events, int32_t* n_events, size_t max_events, int32_t* event_data) {
-    if (!b || !disc || !records10 || !flags || !counts || ((events == nullptr) != (n_events == nullptr))
-        || (events && max_events == 0) || (event_data && !events)) {
-        return DDN_EINVAL;
+    DDN_TRY(check_p25_rx_run(__func__, b, disc, records10, flags, counts));
+    if (((events == nullptr) != (n_events == nullptr)) || (events && max_events == 0) || (event_data && !events)) {
+        return ddn_bad_argument(__func__);
     }
     const size_t B = (size_t)b->cfg.n_channels;
-    float* d_in = nullptr;
-    uint8_t *d_rec = nullptr, *d_fl = nullptr;
-    int32_t *d_cnt = nullptr, *d_ev = nullptr, *d_nev = nullptr, *d_evd = nullptr;
-    int32_t* const keep_evd = b->d_event_data;
+    DdnStaged s;
+    const float* in = s.in(disc, B * n * 4);
+    uint8_t* rec = s.out(records10, B * max_symbols * 10);
+    uint8_t* fl = s.out(flags, B * max_symbols);
+    int32_t* cnt = s.out(counts, B * 4);
+    int32_t* ev = events ? s.out(events, B * max_events * 16) : nullptr;
+    int32_t* nev = events ? s.out(n_events, B * 4) : nullptr;
+    int32_t* evd = event_data ? s.out(event_data, B * max_events * 16) : nullptr;
+    DDN_TRY(s.staged());
+    // the call's own event lists stand in for the object's during this one run
     int32_t* const keep_ev = b->d_events;
     int32_t* const keep_nev = b->d_n_events;
+    int32_t* const keep_evd = b->d_event_data;
     const size_t keep_max = b->max_events;
-    int rc;
-    if (hipMalloc(&d_in, B * n * 4 + 4) != hipSuccess || hipMalloc(&d_rec, B * max_symbols * 10 + 4) != hipSuccess
-        || hipMalloc(&d_fl, B * max_symbols + 4) != hipSuccess || hipMalloc(&d_cnt, B * 4) != hipSuccess
-        || (events && (hipMalloc(&d_ev, B * max_events * 16) != hipSuccess || hipMalloc(&d_nev, B * 4) != hipSuccess))
-        || (event_data && hipMalloc(&d_evd, B * max_events * 16) != hipSuccess)) {
-        ddn_set_error("ddn_p25_rx_run_host: device allocation failed (no device?)");
-        rc = DDN_ENODEV;
-    } else if (hipMemcpy(d_in, disc, B * n * 4, hipMemcpyHostToDevice) != hipSuccess
-               || hipMemset(d_rec, 0, B * max_symbols * 10) != hipSuccess
-               || hipMemset(d_fl, 0, B * max_symbols) != hipSuccess
-               || (events && (hipMemset(d_ev, 0, B * max_events * 16) != hipSuccess || hipMemset(d_nev, 0, B * 4) != hipSuccess))
-               || (event_data && hipMemset(d_evd, 0, B * max_events * 16) != hipSuccess)) {
-        rc = DDN_EHIP;
-    } else {
-        if (events) {
-            b->d_events = d_ev;
-            b->d_n_events = d_nev;
-            b->max_events = max_events;
-            b->d_event_data = d_evd;
-        }
-        rc = ddn_p25_rx_run(b, d_in, n, d_rec, d_fl, d_cnt, max_symbols, nullptr);
-        if (rc == DDN_OK
-            && (hipDeviceSynchronize() != hipSuccess
-                || hipMemcpy(records10, d_rec, B * max_symbols * 10, hipMemcpyDeviceToHost) != hipSuccess
-                || hipMemcpy(flags, d_fl, B * max_symbols, hipMemcpyDeviceToHost) != hipSuccess
-                || hipMemcpy(counts, d_cnt, B * 4, hipMemcpyDeviceToHost) != hipSuccess
-                || (events
-                    && (hipMemcpy(events, d_ev, B * max_events * 16, hipMemcpyDeviceToHost) != hipSuccess
-                        || hipMemcpy(n_events, d_nev, B * 4, hipMemcpyDeviceToHost) != hipSuccess))
-                || (event_data && hipMemcpy(event_data, d_evd, B * max_events * 16, hipMemcpyDeviceToHost) != hipSuccess))) {
-            ddn_set_error("ddn_p25_rx_run_host: %s", hipGetErrorString(hipGetLastError()));
-            rc = DDN_EHIP;
-        }
+    if (events) {
+        b->d_events = ev;
+        b->d_n_events = nev;
+        b->max_events = max_events;
+        b->d_event_data = evd;
     }
+    const int rc = ddn_p25_rx_run(b, in, n, rec, fl, cnt, max_symbols, nullptr);
     b->d_events = keep_ev;
     b->d_n_events = keep_nev;
     b->max_events = keep_max;
     b->d_event_data = keep_evd;
-    (void)hipDeviceSynchronize();
-    (void)hipFree(d_evd);
-    (void)hipFree(d_in);
-    (void)hipFree(d_rec);
-    (void)hipFree(d_fl);
-    (void)hipFree(d_cnt);
-    (void)hipFree(d_ev);
-    (void)hipFree(d_nev);
-    return rc;
+    const hipError_t e = hipDeviceSynchronize(); // (also on a failed run: nothing queued reads the staged buffers when they go)
+    DDN_TRY(rc);
+    HIP_TRY(e);
+    return s.finish();
 }
 
 extern "C" int

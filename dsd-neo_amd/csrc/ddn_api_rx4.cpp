@@ -73,25 +73,12 @@ struct ddn_fsk4_rx {
     int tap_set;                   // the matched filter's tap table (0 DMR, 1 NXDN48, 2 dPMR): the taps create() uploaded
     bool timing;
     hipEvent_t ev[3];
+    DdnPool pool;
 };
 
 static void
 rx4_free(ddn_fsk4_rx* b) {
-    (void)hipFree(b->d_state);
-    (void)hipFree(b->d_lbuf);
-    (void)hipFree(b->d_shist);
-    (void)hipFree(b->d_phist);
-    (void)hipFree(b->d_rhist);
-    (void)hipFree(b->d_fhist);
-    (void)hipFree(b->d_fstale);
-    (void)hipFree(b->d_filt);
-    (void)hipFree(b->d_taps);
-    (void)hipFree(b->d_cfg);
-    (void)hipFree(b->d_lock);
-    (void)hipFree(b->d_hwords);
-    (void)hipFree(b->d_hpay);
-    (void)hipFree(b->d_ev_own);
-    (void)hipFree(b->d_nev_own);
+    b->pool.release();
     for (int i = 0; i < 3; i++) {
         if (b->ev[i]) {
             (void)hipEventDestroy(b->ev[i]);
@@ -166,11 +153,7 @@ ddn_fsk4_rx_create(const ddn_fsk4_rx_config* cfg, ddn_fsk4_rx** out) {
             return DDN_ERANGE;
         }
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        ddn_set_error("ddn_fsk4_rx_create: no HIP device");
-        return DDN_ENODEV;
-    }
+    DDN_TRY(ddn_have_device());
     ddn_fsk4_rx* b = new (std::nothrow) ddn_fsk4_rx();
     if (!b) {
         return DDN_ENOMEM;
@@ -393,14 +376,12 @@ ddn_fsk4_rx_create(const ddn_fsk4_rx_config* cfg, ddn_fsk4_rx** out) {
     }
     float taps[DDN_FSK4_MAX_TAPS] = {0};
     memcpy(taps, tap_bits, sizeof(float) * (size_t)d.nt);
-    if (hipMalloc(&b->d_state, sizeof(DdnFsk4State) * B) != hipSuccess || hipMalloc(&b->d_lbuf, sizeof(float) * 24 * B) != hipSuccess
-        || hipMalloc(&b->d_shist, sizeof(float) * DDN_FSK4_HIST * B) != hipSuccess
-        || hipMalloc(&b->d_phist, DDN_FSK4_HIST * B) != hipSuccess || hipMalloc(&b->d_rhist, DDN_FSK4_HIST * B) != hipSuccess
-        || hipMalloc(&b->d_fhist, sizeof(float) * (DDN_FSK4_MAX_TAPS - 1) * B) != hipSuccess
-        || hipMalloc(&b->d_fstale, sizeof(float) * (DDN_FSK4_MAX_TAPS - 1) * B) != hipSuccess
-        || hipMalloc(&b->d_taps, sizeof(taps)) != hipSuccess || hipMalloc(&b->d_cfg, sizeof(DdnFsk4Config)) != hipSuccess
-        || hipMemcpy(b->d_cfg, &b->dc, sizeof(DdnFsk4Config), hipMemcpyHostToDevice) != hipSuccess || hipMalloc(&b->d_lock, sizeof(int32_t) * 4 * B) != hipSuccess
-        || hipMalloc(&b->d_hwords, sizeof(int32_t) * 32 * B) != hipSuccess || hipMalloc(&b->d_hpay, 144 * B) != hipSuccess
+    DdnPool& p = b->pool;
+    if (!p.alloc(&b->d_state, B) || !p.alloc(&b->d_lbuf, 24 * B) || !p.alloc(&b->d_shist, DDN_FSK4_HIST * B) || !p.alloc(&b->d_phist, DDN_FSK4_HIST * B)
+        || !p.alloc(&b->d_rhist, DDN_FSK4_HIST * B) || !p.alloc(&b->d_fhist, (DDN_FSK4_MAX_TAPS - 1) * B)
+        || !p.alloc(&b->d_fstale, (DDN_FSK4_MAX_TAPS - 1) * B) || !p.alloc(&b->d_taps, DDN_FSK4_MAX_TAPS) || !p.alloc(&b->d_cfg, 1)
+        || hipMemcpy(b->d_cfg, &b->dc, sizeof(DdnFsk4Config), hipMemcpyHostToDevice) != hipSuccess || !p.alloc(&b->d_lock, 4 * B)
+        || !p.alloc(&b->d_hwords, 32 * B) || !p.alloc(&b->d_hpay, 144 * B)
         || hipMemcpy(b->d_taps, taps, sizeof(taps), hipMemcpyHostToDevice) != hipSuccess
         || hipMemcpy(b->d_lock, lock.data(), sizeof(int32_t) * 4 * B, hipMemcpyHostToDevice) != hipSuccess) {
         ddn_set_error("ddn_fsk4_rx_create: device allocation failed");
@@ -475,11 +456,8 @@ ddn_fsk4_rx_events_host_arm(ddn_fsk4_rx* b, size_t max_events) {
     }
     const size_t B = (size_t)b->cfg.n_channels;
     HIP_TRY(hipDeviceSynchronize());
-    (void)hipFree(b->d_ev_own);
-    (void)hipFree(b->d_nev_own);
-    b->d_ev_own = b->d_nev_own = nullptr;
-    HIP_TRY(hipMalloc(&b->d_ev_own, B * max_events * 16));
-    HIP_TRY(hipMalloc(&b->d_nev_own, B * 4));
+    HIP_TRY(b->pool.realloc_bytes(&b->d_ev_own, B * max_events * 16));
+    HIP_TRY(b->pool.realloc_bytes(&b->d_nev_own, B * 4));
     HIP_TRY(hipMemset(b->d_ev_own, 0, B * max_events * 16));
     HIP_TRY(hipMemset(b->d_nev_own, 0, B * 4));
     return ddn_fsk4_rx_set_events(b, b->d_ev_own, b->d_nev_own, max_events);
@@ -535,15 +513,19 @@ ddn_fsk4_rx_set_lock_symbols(ddn_fsk4_rx* b, const int32_t* lock4) {
     return DDN_OK;
 }
 
+static int
+check_fsk4_rx_run(const char* who, const ddn_fsk4_rx* b, const float* disc, const uint8_t* records10, const uint8_t* flags, const uint8_t* payload2,
+                  const int32_t* counts, const int32_t* sync_pos, const uint8_t* sync_pat, const uint8_t* pre, const uint8_t* pre_rel,
+                  const int32_t* n_sync) {
+    return (b && disc && records10 && flags && payload2 && counts && sync_pos && sync_pat && pre && pre_rel && n_sync) ? DDN_OK
+                                                                                                                        : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_fsk4_rx_run(ddn_fsk4_rx* b, const float* d_disc, size_t n, uint8_t* d_records10, uint8_t* d_flags, uint8_t* d_payload2,
                 int32_t* d_counts, size_t max_symbols, int32_t* d_sync_pos, uint8_t* d_sync_pat, uint8_t* d_pre,
                 uint8_t* d_pre_rel, int32_t* d_n_sync, size_t max_syncs, void* hip_stream) {
-    if (!b || !d_disc || !d_records10 || !d_flags || !d_payload2 || !d_counts || !d_sync_pos || !d_sync_pat || !d_pre || !d_pre_rel
-        || !d_n_sync) {
-        ddn_set_error("ddn_fsk4_rx_run: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_fsk4_rx_run(__func__, b, d_disc, d_records10, d_flags, d_payload2, d_counts, d_sync_pos, d_sync_pat, d_pre, d_pre_rel, d_n_sync));
     hipStream_t st = (hipStream_t)hip_stream;
     const int B = b->cfg.n_channels;
     if (n == 0) {
@@ -562,10 +544,8 @@ ddn_fsk4_rx_run(ddn_fsk4_rx* b, const float* d_disc, size_t n, uint8_t* d_record
     if (b->dc.use_filter) {
         if (b->filt_cap < n) {
             HIP_TRY(hipStreamSynchronize(st));
-            (void)hipFree(b->d_filt);
-            b->d_filt = nullptr;
             b->filt_cap = 0;
-            HIP_TRY(hipMalloc(&b->d_filt, sizeof(float) * (size_t)B * n));
+            HIP_TRY(b->pool.realloc_bytes(&b->d_filt, sizeof(float) * (size_t)B * n));
             b->filt_cap = n;
         }
         HIP_TRY(ddn_dev_fsk4_matched_filter(b->dc.nt, b->tap_set, d_disc, (long)n, n, B, b->d_fhist, b->d_filt, st));
@@ -672,54 +652,23 @@ extern "C" int
 ddn_fsk4_rx_run_host(ddn_fsk4_rx* b, const float* disc, size_t n, uint8_t* records10, uint8_t* flags, uint8_t* payload2,
                      int32_t* counts, size_t max_symbols, int32_t* sync_pos, uint8_t* sync_pat, uint8_t* pre, uint8_t* pre_rel,
                      int32_t* n_sync, size_t max_syncs) {
-    if (!b || !disc || !records10 || !flags || !payload2 || !counts || !sync_pos || !sync_pat || !pre || !pre_rel || !n_sync) {
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_fsk4_rx_run(__func__, b, disc, records10, flags, payload2, counts, sync_pos, sync_pat, pre, pre_rel, n_sync));
     const size_t B = (size_t)b->cfg.n_channels, S = B * max_symbols, Y = B * max_syncs;
-    float* d_in = nullptr;
-    uint8_t *d_rec = nullptr, *d_fl = nullptr, *d_pay = nullptr, *d_spat = nullptr, *d_pre = nullptr, *d_prel = nullptr;
-    int32_t *d_cnt = nullptr, *d_spos = nullptr, *d_ns = nullptr;
-    int rc = DDN_OK;
-    if (hipMalloc(&d_in, B * n * 4 + 4) != hipSuccess || hipMalloc(&d_rec, S * 10 + 4) != hipSuccess
-        || hipMalloc(&d_fl, S + 4) != hipSuccess || hipMalloc(&d_pay, S * 2 + 4) != hipSuccess
-        || hipMalloc(&d_cnt, B * 4) != hipSuccess || hipMalloc(&d_spos, Y * 4 + 4) != hipSuccess
-        || hipMalloc(&d_spat, Y + 4) != hipSuccess || hipMalloc(&d_pre, Y * DDN_FSK4_PRE + 4) != hipSuccess
-        || hipMalloc(&d_prel, Y * DDN_FSK4_PRE + 4) != hipSuccess || hipMalloc(&d_ns, B * 4) != hipSuccess) {
-        ddn_set_error("ddn_fsk4_rx_run_host: device allocation failed (no device?)");
-        rc = DDN_ENODEV;
-    } else if (hipMemcpy(d_in, disc, B * n * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d_rec, 0, S * 10) != hipSuccess
-               || hipMemset(d_fl, 0, S) != hipSuccess || hipMemset(d_pay, 0, S * 2) != hipSuccess
-               || hipMemset(d_spos, 0, Y * 4) != hipSuccess || hipMemset(d_spat, 0, Y) != hipSuccess
-               || hipMemset(d_pre, 0, Y * DDN_FSK4_PRE) != hipSuccess || hipMemset(d_prel, 0, Y * DDN_FSK4_PRE) != hipSuccess) {
-        rc = DDN_EHIP;
-    } else {
-        rc = ddn_fsk4_rx_run(b, d_in, n, d_rec, d_fl, d_pay, d_cnt, max_symbols, d_spos, d_spat, d_pre, d_prel, d_ns, max_syncs,
-                             nullptr);
-        if (rc == DDN_OK
-            && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(records10, d_rec, S * 10, hipMemcpyDeviceToHost) != hipSuccess
-                || hipMemcpy(flags, d_fl, S, hipMemcpyDeviceToHost) != hipSuccess
-                || hipMemcpy(payload2, d_pay, S * 2, hipMemcpyDeviceToHost) != hipSuccess
-                || hipMemcpy(counts, d_cnt, B * 4, hipMemcpyDeviceToHost) != hipSuccess
-                || hipMemcpy(sync_pos, d_spos, Y * 4, hipMemcpyDeviceToHost) != hipSuccess
-                || hipMemcpy(sync_pat, d_spat, Y, hipMemcpyDeviceToHost) != hipSuccess
-                || hipMemcpy(pre, d_pre, Y * DDN_FSK4_PRE, hipMemcpyDeviceToHost) != hipSuccess
-                || hipMemcpy(pre_rel, d_prel, Y * DDN_FSK4_PRE, hipMemcpyDeviceToHost) != hipSuccess
-                || hipMemcpy(n_sync, d_ns, B * 4, hipMemcpyDeviceToHost) != hipSuccess)) {
-            ddn_set_error("ddn_fsk4_rx_run_host: %s", hipGetErrorString(hipGetLastError()));
-            rc = DDN_EHIP;
-        }
-    }
-    (void)hipFree(d_in);
-    (void)hipFree(d_rec);
-    (void)hipFree(d_fl);
-    (void)hipFree(d_pay);
-    (void)hipFree(d_cnt);
-    (void)hipFree(d_spos);
-    (void)hipFree(d_spat);
-    (void)hipFree(d_pre);
-    (void)hipFree(d_prel);
-    (void)hipFree(d_ns);
-    return rc;
+    DdnStaged s;
+    const float* in = s.in(disc, B * n * 4);
+    uint8_t* rec = s.out(records10, S * 10);
+    uint8_t* fl = s.out(flags, S);
+    uint8_t* pay = s.out(payload2, S * 2);
+    int32_t* cnt = s.out(counts, B * 4);
+    int32_t* spos = s.out(sync_pos, Y * 4);
+    uint8_t* spat = s.out(sync_pat, Y);
+    uint8_t* p = s.out(pre, Y * DDN_FSK4_PRE);
+    uint8_t* pr = s.out(pre_rel, Y * DDN_FSK4_PRE);
+    int32_t* ns = s.out(n_sync, B * 4);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_fsk4_rx_run(b, in, n, rec, fl, pay, cnt, max_symbols, spos, spat, p, pr, ns, max_syncs, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    return s.finish();
 }
 
 extern "C" int

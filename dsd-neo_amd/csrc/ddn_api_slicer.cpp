@@ -16,6 +16,7 @@ struct ddn_slicer_batch {
     int n_channels, negative;
     DdnSlicerState* d_state;
     float *d_sbuf, *d_minring, *d_maxring, *d_fhist;
+    DdnPool pool;
 };
 
 static int
@@ -47,11 +48,7 @@ ddn_slicer_batch_create(int n_channels, int negative_polarity, ddn_slicer_batch*
     if (!out || n_channels <= 0) {
         return DDN_EINVAL;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        ddn_set_error("no HIP device available");
-        return DDN_ENODEV;
-    }
+    DDN_TRY(ddn_have_device());
     ddn_slicer_batch* b = new (std::nothrow) ddn_slicer_batch();
     if (!b) {
         return DDN_ENOMEM;
@@ -60,18 +57,10 @@ ddn_slicer_batch_create(int n_channels, int negative_polarity, ddn_slicer_batch*
     b->n_channels = n_channels;
     b->negative = negative_polarity ? 1 : 0;
     const size_t B = (size_t)n_channels;
-    if (hipMalloc(&b->d_state, sizeof(DdnSlicerState) * B) != hipSuccess
-        || hipMalloc(&b->d_sbuf, sizeof(float) * 128 * B) != hipSuccess
-        || hipMalloc(&b->d_minring, sizeof(float) * 1024 * B) != hipSuccess
-        || hipMalloc(&b->d_maxring, sizeof(float) * 1024 * B) != hipSuccess
-        || hipMalloc(&b->d_fhist, sizeof(float) * 90 * B) != hipSuccess || slicer_fill(b) != DDN_OK) {
+    if (!b->pool.alloc(&b->d_state, B) || !b->pool.alloc(&b->d_sbuf, 128 * B) || !b->pool.alloc(&b->d_minring, 1024 * B)
+        || !b->pool.alloc(&b->d_maxring, 1024 * B) || !b->pool.alloc(&b->d_fhist, 90 * B) || slicer_fill(b) != DDN_OK) {
         ddn_set_error("ddn_slicer_batch_create: device allocation failed");
-        (void)hipFree(b->d_state);
-        (void)hipFree(b->d_sbuf);
-        (void)hipFree(b->d_minring);
-        (void)hipFree(b->d_maxring);
-        (void)hipFree(b->d_fhist);
-        delete b;
+        ddn_slicer_batch_destroy(b);
         return DDN_ENOMEM;
     }
     *out = b;
@@ -83,11 +72,7 @@ ddn_slicer_batch_destroy(ddn_slicer_batch* b) {
     if (!b) {
         return;
     }
-    (void)hipFree(b->d_state);
-    (void)hipFree(b->d_sbuf);
-    (void)hipFree(b->d_minring);
-    (void)hipFree(b->d_maxring);
-    (void)hipFree(b->d_fhist);
+    b->pool.release();
     delete b;
 }
 
@@ -100,24 +85,24 @@ ddn_slicer_batch_reset(ddn_slicer_batch* b) {
     return slicer_fill(b);
 }
 
+static int
+check_run(const char* who, const ddn_slicer_batch* b, const void* in, const void* out) {
+    return (b && in && out) ? DDN_OK : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_p25_slicer_run(ddn_slicer_batch* b, const float* d_symbols, size_t n, uint8_t* d_records10, void* hip_stream) {
-    if (!b || !d_symbols || !d_records10) {
-        ddn_set_error("ddn_p25_slicer_run: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_run(__func__, b, d_symbols, d_records10));
     // The sequential kernel (one lane per channel walking every symbol) remains for short calls; from a few hundred
     // symbols on the parallel decomposition (ddn_slicer_par.hip) wins.  DDN_SLICER_SEQ forces the sequential one (A/B).
     static const bool force_seq = DDN_EXP_ENV("DDN_SLICER_SEQ") != nullptr;
     if (n >= 256 && !force_seq) {
-        const size_t need = sizeof(float) * 4 * n * (size_t)b->n_channels;
-        float* scratch = nullptr;
-        HIP_TRY(hipMallocAsync((void**)&scratch, need, (hipStream_t)hip_stream));
-        const hipError_t e = ddn_dev_p25_slicer_par(d_symbols, (long)n, n, b->n_channels, b->negative, b->d_state, b->d_sbuf,
-                                                    b->d_minring, b->d_maxring, scratch, d_records10, n * 10,
-                                                    (hipStream_t)hip_stream);
-        HIP_TRY(hipFreeAsync(scratch, (hipStream_t)hip_stream));
-        HIP_TRY(e);
+        DdnScratch s((hipStream_t)hip_stream);
+        float* scratch;
+        HIP_TRY(s.arena(sizeof(float) * 4 * n * (size_t)b->n_channels));
+        HIP_TRY(s.get(&scratch, 4 * n * (size_t)b->n_channels));
+        HIP_TRY(ddn_dev_p25_slicer_par(d_symbols, (long)n, n, b->n_channels, b->negative, b->d_state, b->d_sbuf, b->d_minring, b->d_maxring,
+                                       scratch, d_records10, n * 10, (hipStream_t)hip_stream));
         return DDN_OK;
     }
     HIP_TRY(ddn_dev_p25_slicer(d_symbols, (long)n, n, b->n_channels, b->negative, b->d_state, b->d_sbuf, b->d_minring,
@@ -127,27 +112,14 @@ ddn_p25_slicer_run(ddn_slicer_batch* b, const float* d_symbols, size_t n, uint8_
 
 extern "C" int
 ddn_p25_slicer_run_host(ddn_slicer_batch* b, const float* symbols, size_t n, uint8_t* records10) {
-    if (!b || !symbols || !records10) {
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_run(__func__, b, symbols, records10));
     const size_t B = (size_t)b->n_channels;
-    float* d_in = nullptr;
-    uint8_t* d_out = nullptr;
-    int rc;
-    if (hipMalloc(&d_in, B * n * 4 + 4) != hipSuccess || hipMalloc(&d_out, B * n * 10 + 4) != hipSuccess) {
-        ddn_set_error("ddn_p25_slicer_run_host: device allocation failed (no device?)");
-        rc = DDN_ENODEV;
-    } else if (hipMemcpy(d_in, symbols, B * n * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        rc = DDN_EHIP;
-    } else {
-        rc = ddn_p25_slicer_run(b, d_in, n, d_out, nullptr);
-        if (rc == DDN_OK && hipMemcpy(records10, d_out, B * n * 10, hipMemcpyDeviceToHost) != hipSuccess) {
-            rc = DDN_EHIP;
-        }
-    }
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return rc;
+    DdnStaged s;
+    const float* i = s.in(symbols, B * n * 4);
+    uint8_t* o = s.out(records10, B * n * 10);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_p25_slicer_run(b, i, n, o, nullptr));
+    return s.finish();
 }
 
 extern "C" int
@@ -168,10 +140,7 @@ ddn_slicer_batch_get_thresholds(ddn_slicer_batch* b, int channel, float out5[5])
 
 extern "C" int
 ddn_p25_matched_filter_run(ddn_slicer_batch* b, const float* d_in, size_t n, float* d_out, void* hip_stream) {
-    if (!b || !d_in || !d_out) {
-        ddn_set_error("ddn_p25_matched_filter_run: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_run(__func__, b, d_in, d_out));
     if (d_in == d_out) {
         ddn_set_error("ddn_p25_matched_filter_run: in-place operation is not supported");
         return DDN_EINVAL;
@@ -182,24 +151,12 @@ ddn_p25_matched_filter_run(ddn_slicer_batch* b, const float* d_in, size_t n, flo
 
 extern "C" int
 ddn_p25_matched_filter_run_host(ddn_slicer_batch* b, const float* in, size_t n, float* out) {
-    if (!b || !in || !out) {
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_run(__func__, b, in, out));
     const size_t B = (size_t)b->n_channels;
-    float *d_in = nullptr, *d_out = nullptr;
-    int rc;
-    if (hipMalloc(&d_in, B * n * 4 + 4) != hipSuccess || hipMalloc(&d_out, B * n * 4 + 4) != hipSuccess) {
-        ddn_set_error("ddn_p25_matched_filter_run_host: device allocation failed (no device?)");
-        rc = DDN_ENODEV;
-    } else if (hipMemcpy(d_in, in, B * n * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        rc = DDN_EHIP;
-    } else {
-        rc = ddn_p25_matched_filter_run(b, d_in, n, d_out, nullptr);
-        if (rc == DDN_OK && hipMemcpy(out, d_out, B * n * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-            rc = DDN_EHIP;
-        }
-    }
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return rc;
+    DdnStaged s;
+    const float* i = s.in(in, B * n * 4);
+    float* o = s.out(out, B * n * 4);
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_p25_matched_filter_run(b, i, n, o, nullptr));
+    return s.finish();
 }

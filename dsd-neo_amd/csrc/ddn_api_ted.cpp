@@ -17,6 +17,7 @@ struct ddn_ted_batch {
     DdnTedState* d_state;
     float* d_dl;
     int* d_count;
+    DdnPool pool;
 };
 
 extern "C" int
@@ -25,11 +26,7 @@ ddn_ted_batch_create(int n_channels, int sps, int symbol_rate_hz, float ted_gain
         ddn_set_error("ddn_ted_batch_create: bad argument (sps must be 2..49 for the %d-entry delay line)", DDN_TED_DL);
         return DDN_EINVAL;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        ddn_set_error("no HIP device available");
-        return DDN_ENODEV;
-    }
+    DDN_TRY(ddn_have_device());
     ddn_ted_batch* b = new (std::nothrow) ddn_ted_batch();
     if (!b) {
         return DDN_ENOMEM;
@@ -40,16 +37,9 @@ ddn_ted_batch_create(int n_channels, int sps, int symbol_rate_hz, float ted_gain
     b->symbol_rate_hz = symbol_rate_hz;
     b->ted_gain = ted_gain;
     const size_t B = (size_t)n_channels;
-    if (hipMalloc(&b->d_state, sizeof(DdnTedState) * B) != hipSuccess
-        || hipMalloc(&b->d_dl, sizeof(float) * DDN_TED_DL * 4 * B) != hipSuccess
-        || hipMalloc(&b->d_count, sizeof(int) * B) != hipSuccess
-        || hipMemset(b->d_state, 0, sizeof(DdnTedState) * B) != hipSuccess
-        || hipMemset(b->d_dl, 0, sizeof(float) * DDN_TED_DL * 4 * B) != hipSuccess) {
+    if (!b->pool.alloc(&b->d_state, B) || !b->pool.alloc(&b->d_dl, DDN_TED_DL * 4 * B) || !b->pool.alloc(&b->d_count, B)) {
         ddn_set_error("ddn_ted_batch_create: device allocation failed");
-        (void)hipFree(b->d_state);
-        (void)hipFree(b->d_dl);
-        (void)hipFree(b->d_count);
-        delete b;
+        ddn_ted_batch_destroy(b);
         return DDN_ENOMEM;
     }
     *out = b;
@@ -61,9 +51,7 @@ ddn_ted_batch_destroy(ddn_ted_batch* b) {
     if (!b) {
         return;
     }
-    (void)hipFree(b->d_state);
-    (void)hipFree(b->d_dl);
-    (void)hipFree(b->d_count);
+    b->pool.release();
     delete b;
 }
 
@@ -88,13 +76,15 @@ ddn_ted_batch_set_block_len(ddn_ted_batch* b, size_t block_len) {
     return DDN_OK;
 }
 
+static int
+check_gardner(const char* who, const ddn_ted_batch* b, const float* iq, const float* sym, bool count_ok) {
+    return (b && iq && sym && count_ok) ? DDN_OK : ddn_bad_argument(who);
+}
+
 extern "C" int
 ddn_gardner_run(ddn_ted_batch* b, const float* d_iq, size_t n, float* d_sym, size_t sym_stride, int* d_sym_count,
                 void* hip_stream) {
-    if (!b || !d_iq || !d_sym) {
-        ddn_set_error("ddn_gardner_run: null argument");
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_gardner(__func__, b, d_iq, d_sym, true));
     HIP_TRY(ddn_dev_gardner(d_iq, (long)n, n, b->n_channels, b->sps, b->ted_gain, b->symbol_rate_hz, b->block_len,
                             b->d_state, b->d_dl, d_sym, sym_stride, d_sym_count ? d_sym_count : b->d_count,
                             (hipStream_t)hip_stream));
@@ -103,28 +93,15 @@ ddn_gardner_run(ddn_ted_batch* b, const float* d_iq, size_t n, float* d_sym, siz
 
 extern "C" int
 ddn_gardner_run_host(ddn_ted_batch* b, const float* iq, size_t n, float* sym, size_t sym_stride, int* sym_count) {
-    if (!b || !iq || !sym || !sym_count) {
-        return DDN_EINVAL;
-    }
+    DDN_TRY(check_gardner(__func__, b, iq, sym, sym_count != nullptr));
     const size_t B = (size_t)b->n_channels;
-    float *d_in = nullptr, *d_out = nullptr;
-    int rc = DDN_OK;
-    if (hipMalloc(&d_in, B * n * 8 + 8) != hipSuccess || hipMalloc(&d_out, B * sym_stride * 8 + 8) != hipSuccess) {
-        ddn_set_error("ddn_gardner_run_host: device allocation failed (no device?)");
-        rc = DDN_ENODEV;
-    } else if (hipMemcpy(d_in, iq, B * n * 8, hipMemcpyHostToDevice) != hipSuccess) {
-        rc = DDN_EHIP;
-    } else {
-        rc = ddn_gardner_run(b, d_in, n, d_out, sym_stride, nullptr, nullptr);
-        if (rc == DDN_OK
-            && (hipMemcpy(sym, d_out, B * sym_stride * 8, hipMemcpyDeviceToHost) != hipSuccess
-                || hipMemcpy(sym_count, b->d_count, B * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)) {
-            rc = DDN_EHIP;
-        }
-    }
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return rc;
+    DdnStaged s;
+    const float* in = s.in(iq, B * n * 8);
+    float* o = s.out(sym, B * sym_stride * 8);
+    int* c = s.out(sym_count, B * sizeof(int));
+    DDN_TRY(s.staged());
+    DDN_TRY(ddn_gardner_run(b, in, n, o, sym_stride, c, nullptr));
+    return s.finish();
 }
 
 extern "C" int

@@ -180,3 +180,81 @@ def test_node_configuration_is_checked_before_any_device_is_touched(built):
     if not torch.cuda.is_available():
         assert create() == -2 and l.ddn_last_error()
         assert create(kind=ddn.NODE_MIXED, n_dmr=4, n_nxdn48=4) == -2
+
+
+# ---- host-buffer variants: arguments are checked before the device is touched ------------------------------------------------------
+# One line per `_host` function without an object handle: its smallest valid call on three items.  An (dtype, count) pair stands for a
+# pointer to that many zeroed elements, anything else is a scalar.  None is an optional pointer left out (a zeroed puncture pattern
+# would keep nothing).
+_N = 3
+_U8, _I8, _I16, _U16, _I32, _U32, _I64, _U64, _F32 = "u1", "i1", "i2", "u2", "i4", "u4", "i8", "u8", "f4"
+HOST_CALLS = {
+    "ddn_fec_p25_12_soft_host": [(_I16, _N * 196), _N, (_U8, _N * 12), (_I32, _N)],
+    "ddn_fec_r34_host": [(_U8, _N * 98), (_U8, _N * 98), _N, (_U8, _N * 18)],
+    "ddn_fec_nxdn_conv_host": [(_U8, _N * 2 * 16), (_U8, _N * 2 * 16), _N, 16, 12, (_U16, _N * 16), (_U8, _N * 2), 2],
+    "ddn_fec_viterbi_k5_host": [(_U16, _N * 16), _N, 16, None, 0, (_U8, _N * 2), 2, (_U32, _N)],
+    "ddn_p25p1_nid_decode_host": [(_U8, _N * 63), (_U8, _N * 63), (_I32, _N), (_U8, _N), (_U8, _N), 64, _N, (_I32, _N * 4)],
+    "ddn_p25p1_imbe_deinterleave_host": [(_U8, 1000 * 10), 1000, (_I64, _N), (_I32, _N), _N, (_U8, _N * 184), (_U8, _N * 368), (_U8, _N),
+                                         (_I32, _N)],
+    "ddn_fec_p25_crc16_host": [(_U8, _N * 12), 12, _N, (_U8, _N)],
+    "ddn_fec_p25_lsd_host": [(_U8, _N * 16), (_I16, _N * 16), _N, (_U8, _N)],
+    "ddn_fec_hamming_10_6_3_host": [(_U8, _N * 10), _N, (_U8, _N)],
+    "ddn_fec_golay24_host": [12, (_U8, _N * 12), (_U8, _N * 12), _N, (_U8, _N), (_I32, _N)],
+    "ddn_fec_p25_rs_host": [0, (_U8, _N * 12 * 6), (_U8, _N * 12 * 6), _N, (_U8, _N)],
+    "ddn_fec_rs28_host": [0, (_U8, _N * 96), (_U8, _N * 168), (_I8, _N * 28), (_U8, _N), _N, (_I32, _N)],
+    "ddn_audio_s16_host": [(_F32, _N * 160), _N, 1, 0.0, 1, 1, (_I16, _N * 160), (_F32, _N * 32), (_F32, _N)],
+    "ddn_fec_bptc_128x77_host": [(_U8, _N * 128), _N, (_U8, _N * 77), (_U32, _N)],
+    "ddn_fec_bptc_16x2_host": [(_U8, _N * 32), _N, 0, (_U8, _N * 32), (_U32, _N)],
+    "ddn_fec_isch_lookup_host": [(_U64, _N), (_U8, _N * 40), _N, (_I32, _N)],
+    "ddn_fec_golay24_soft_host": [12, (_U8, _N * 12), (_U8, _N * 12), (_I32, _N * 24), _N, (_U8, _N), (_I32, _N)],
+    "ddn_fec_hamming_10_6_3_soft_host": [(_U8, _N * 10), (_I32, _N * 10), _N, (_U8, _N * 10), (_U8, _N)],
+    "ddn_fec_p25_rs_soft_host": [0, (_U8, _N * 12 * 6), (_U8, _N * 12 * 6), (_U8, _N * 12), (_U8, _N * 12), _N, (_U8, _N)],
+    "ddn_fec_p25_12_soft_list_host": [(_I16, _N * 196), _N, 8, (_U8, _N * 8 * 16), (_I32, _N)],
+    "ddn_fec_r34_list_host": [(_U8, _N * 98), (_U8, _N * 98), _N, 32, (_U8, _N * 32 * 24), (_I32, _N)],
+    "ddn_fec_block_code_host": [0, (_U8, _N * 7), _N, 1, (_U8, _N * 4), (_U8, _N)],
+    "ddn_fec_bptc_196x96_host": [(_U8, _N * 196), 0, _N, (_U8, _N * 96), (_U8, _N * 3), (_U32, _N)],
+    "ddn_fec_trellis_decode_host": [(_U8, _N * 22), 22, _N, 8, (_U8, _N * 8), 8],
+    "ddn_fec_rs_12_9_host": [(_U8, _N * 12), _N, (_U8, _N), (_U8, _N), (_U8, _N * 3)],
+    "ddn_audio_agf_host": [(_F32, _N * 160), _N, 1, 0.0, 0, (_F32, _N)],
+    "ddn_fec_p25_mbf34_list_host": [(_I16, _N * 196), _N, 8, (_U8, _N * 8 * 24), (_I32, _N)],
+    "ddn_p25p2_mac_crc_host": [0, (_U8, _N * 156), _N, (_U8, _N), (_U8, _N)],
+    "ddn_p25p2_ess_host": [(_U8, _N * 96), (_I16, _N * 96), (_U8, _N * 168), (_I16, _N * 168), _N, 0, (_U8, _N * 96), (_I32, _N), (_U8, _N)],
+    "ddn_p25p2_groups_host": [(_U8, _N * 1400), (_I16, _N * 1400), _N, 1, (_I32, _N), (_U64, _N), (_U8, _N * 592), 0, (_I32, _N * 4 * 8),
+                              (_U8, _N * 4 * 180), (_U8, _N * 4 * 384), (_U8, _N * 4 * 384), (_U8, _N * 4 * 96)],
+    "ddn_p25p2_sync_cut_host": [(_U8, _N * 64), (_I16, _N * 64 * 2), _N, 64, 64, (_I32, _N), 1, (_I32, _N), (_I32, _N), (_I32, _N),
+                                (_U8, _N * 1400), (_I16, _N * 1400)],
+    "ddn_p25p2_burst_fields_host": [(_U8, _N * 360), (_I16, _N * 360), _N, 0, (_I32, _N), (_I32, _N)],
+    "ddn_p25p2_xcch_host": [0, (_U8, _N * 360), (_I16, _N * 360), _N, 0, (_U8, _N * 156), (_I32, _N), (_U8, _N)],
+}
+# the variants of an object: a null handle is a bad argument
+HOST_CALLS_OF_OBJECTS = ["ddn_front_end_run_host", "ddn_p25_slicer_run_host", "ddn_p25_matched_filter_run_host", "ddn_cqpsk_run_host",
+                         "ddn_p25_rx_run_host", "ddn_gardner_run_host", "ddn_resampler_run_host", "ddn_fsk4_rx_run_host",
+                         "ddn_p25_chain_run_host", "ddn_node_run_host"]
+
+
+def test_every_host_variant_is_in_the_tables(built):
+    assert sorted(list(HOST_CALLS) + HOST_CALLS_OF_OBJECTS) == sorted(k for k in ddn.PROTOTYPES if k.endswith("_host"))
+
+
+@pytest.mark.parametrize("name", sorted(HOST_CALLS))
+def test_host_variant_checks_arguments_before_it_touches_the_device(built, name):
+    """(a) every pointer null: DDN_EINVAL with a message, device or not; (b) valid zeroed buffers: DDN_ENODEV without a device (never
+    a CPU path), DDN_OK with one"""
+    import numpy as np
+    import torch
+    l = ddn.lib()
+    fn = getattr(l, name)
+    spec = HOST_CALLS[name]
+    assert len(spec) == len(ddn.PROTOTYPES[name][1])
+    assert fn(*[None if isinstance(a, tuple) else a for a in spec]) == ddn.DDN_EINVAL
+    assert name.encode() in l.ddn_last_error()           # this call's message, not an earlier one
+    bufs = [np.zeros(a[1], a[0]) if isinstance(a, tuple) else a for a in spec]
+    rc = fn(*[a.ctypes.data if isinstance(a, np.ndarray) else a for a in bufs])
+    assert rc == (ddn.DDN_OK if torch.cuda.is_available() else ddn.DDN_ENODEV), l.ddn_last_error()
+
+
+@pytest.mark.parametrize("name", HOST_CALLS_OF_OBJECTS)
+def test_host_variant_of_an_object_rejects_a_null_handle(built, name):
+    l = ddn.lib()
+    args = [None if t is C.c_void_p else 3 for t in ddn.PROTOTYPES[name][1]]
+    assert getattr(l, name)(*args) == ddn.DDN_EINVAL
