@@ -75,15 +75,26 @@ ddn_fec_r34_batch(const uint8_t* d_dibits98, const uint8_t* d_reliab98, size_t n
     return DDN_OK;
 }
 
+// (the length is also held against the LDS a workgroup may have on this device, before anything is staged or launched: sixteen code
+// words of n_steps steps need 64 n_steps + 48 bytes in the hard form and 96 n_steps + 80 with reliabilities)
 static int
-check_nxdn_conv(const char* who, const uint8_t* sym, const uint8_t* out, int n_steps, int n_bits, int out_stride) {
-    return (sym && out && n_steps > 0 && n_steps <= 1024 && n_bits >= 0 && n_bits <= n_steps && out_stride >= (n_bits + 7) / 8) ? DDN_OK : ddn_bad_argument(who);
+check_nxdn_conv(const char* who, const uint8_t* sym, const uint8_t* rel, const uint8_t* out, int n_steps, int n_bits, int out_stride) {
+    if (!(sym && out && n_steps > 0 && n_steps <= 1024 && n_bits >= 0 && n_bits <= n_steps && out_stride >= (n_bits + 7) / 8)) {
+        return ddn_bad_argument(who);
+    }
+    size_t need = 0, limit = 0;
+    HIP_TRY(ddn_dev_k5_nxdn_lds(n_steps, rel != nullptr, &need, &limit));
+    if (need > limit) {
+        ddn_set_error("%s: %d steps need %zu bytes of LDS per workgroup, the device offers %zu", who, n_steps, need, limit);
+        return DDN_ERANGE;
+    }
+    return DDN_OK;
 }
 
 extern "C" int
 ddn_fec_nxdn_conv_batch(const uint8_t* d_sym, const uint8_t* d_rel, size_t n, int n_steps, int n_bits,
                         uint16_t* d_metrics_io, uint8_t* d_out, int out_stride, void* hip_stream) {
-    DDN_TRY(check_nxdn_conv(__func__, d_sym, d_out, n_steps, n_bits, out_stride));
+    DDN_TRY(check_nxdn_conv(__func__, d_sym, d_rel, d_out, n_steps, n_bits, out_stride));
     HIP_TRY(ddn_dev_k5_nxdn(d_sym, d_rel, (int)n, n_steps, n_bits, d_metrics_io, d_out, out_stride,
                             (hipStream_t)hip_stream));
     return DDN_OK;
@@ -191,7 +202,7 @@ ddn_fec_r34_host(const uint8_t* dibits98, const uint8_t* reliab98, size_t n, uin
 extern "C" int
 ddn_fec_nxdn_conv_host(const uint8_t* sym, const uint8_t* rel, size_t n, int n_steps, int n_bits, uint16_t* metrics_io,
                        uint8_t* out, int out_stride) {
-    DDN_TRY(check_nxdn_conv(__func__, sym, out, n_steps, n_bits, out_stride));
+    DDN_TRY(check_nxdn_conv(__func__, sym, rel, out, n_steps, n_bits, out_stride));
     DdnStaged s;
     const uint8_t* a = s.in(sym, n * 2 * (size_t)n_steps);
     const uint8_t* r = s.in_opt(rel, n * 2 * (size_t)n_steps);

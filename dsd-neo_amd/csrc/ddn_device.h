@@ -298,20 +298,39 @@ hipError_t ddn_dev_imbe_deinterleave(const uint8_t* rec, long n_records, const i
                                      hipStream_t st);
 hipError_t ddn_dev_r34_list(const uint8_t* dibits, const uint8_t* reliab, int n, int max_cand, uint8_t* backs,
                             uint32_t* cand, int32_t* count, hipStream_t st);
+/* The sparse forms below take `wanted` [n] (one byte per item, 0 = nobody reads this item; NULL = every item is wanted).  A wanted
+ * item reads exactly what the dense form gives for it.  What an UNWANTED item reads differs from family to family and is written at
+ * each declaration, as the kernels do it and as the chains rely on it (tests/test_fec_sparse_gpu.py holds every line against
+ * sentinel-filled buffers).  Nothing is written outside items [0, n) in any of them. */
+/* unwanted item: count = 0, its eight candidates left unwritten.  (Wanted item: candidates [count .. 8) are left unwritten too; the
+ * skip is per item - one workgroup per item, min(n, 65536) workgroups that walk the items with that stride.) */
 hipError_t ddn_dev_p25_mbf34_list(const int16_t* llr, int n, int max_cand, const uint8_t* wanted, uint8_t* cand24, int32_t* count,
                                   hipStream_t st);
 hipError_t ddn_dev_p25_half_rate_list(const int16_t* llr, int n, int max_cand, uint32_t* cand, int32_t* count,
                                       hipStream_t st);
 hipError_t ddn_dev_p25_half_rate(const int16_t* llr, int n, uint8_t* out, int32_t* metric, hipStream_t st);
 hipError_t ddn_dev_r34(const uint8_t* dibits, const uint8_t* reliab, int n, uint8_t* out, hipStream_t st);
+/* with a list: groups of 4 items, at most 1024 workgroups (16384 in the _wide form) that walk the groups with that stride.  Unwanted
+ * item in a group with no wanted item: count = 0, candidates left unwritten.  Unwanted item beside a wanted one (same group of 4): decoded
+ * like a wanted item (count and candidates of the dense form).  So count > 0 always comes with valid candidates, which is what
+ * ddn_dev_chain_pdu_take_first reads.  Candidates [count .. 8) of a decoded item are zero.  wanted = NULL: the dense form (groups of 32). */
 hipError_t ddn_dev_p25_half_rate_list_wanted(const int16_t* llr, int n, int max_cand, const uint8_t* wanted, uint32_t* cand, int32_t* count,
                                              hipStream_t st);
 hipError_t ddn_dev_p25_half_rate_list_wanted_wide(const int16_t* llr, int n, int max_cand, const uint8_t* wanted, uint32_t* cand,
                                                   int32_t* count, hipStream_t st);
+/* groups of 16 rows; row i is wanted where wanted[i / wanted_div] != 0 (wanted_div = 2: the two FACCH halves of one slot).  Unwanted row
+ * in a group with no wanted row: its (n_bits + 7) / 8 output bytes are zero.  Unwanted row beside a wanted one: decoded like a wanted row.
+ * Either way the bytes of a row beyond (n_bits + 7) / 8 and an unwanted row's metrics_io are left as they were (the chains pass no
+ * metrics and read unwanted rows nowhere).  n_steps is the caller's to check against ddn_dev_k5_nxdn_lds: a length that does not fit is
+ * answered with hipErrorInvalidValue and not launched. */
+hipError_t ddn_dev_k5_nxdn_lds(int n_steps, bool soft, size_t* need, size_t* limit);
 hipError_t ddn_dev_k5_nxdn_wanted(const uint8_t* sym, const uint8_t* rel, int n, int n_steps, int n_bits, uint16_t* metrics_io,
                                   uint8_t* out, int out_stride, const uint8_t* wanted, int wanted_div, hipStream_t st);
+/* unwanted row (per row, groups of 64 play no part): its result_len output bytes are zero */
 hipError_t ddn_dev_trellis_greedy_wanted(const uint8_t* src, int src_stride, size_t n, int result_len, uint8_t* out, int out_stride,
                                          const uint8_t* wanted, hipStream_t st);
+/* groups of 8 items, one workgroup each.  Unwanted item, whatever its neighbours: count = 0, its 32 candidates left unwritten (and its
+ * part of `backs` untouched).  Candidates [count .. 32) of a wanted item are zero. */
 hipError_t ddn_dev_r34_list_wanted(const uint8_t* dibits, const uint8_t* reliab, int n, int max_cand, const uint8_t* wanted, uint8_t* backs,
                                    uint32_t* cand, int32_t* count, hipStream_t st);
 // the DMR chain's data-burst / embedded-signalling stages (ddn_dmr_data.hip, k_dmr_r34_pick in ddn_trellis.hip)
@@ -326,6 +345,9 @@ hipError_t ddn_dev_dmr_data_prep(const int32_t* dstart, const uint8_t* slot_type
                                  uint8_t* type, uint8_t* bytes12, uint8_t* cw12, hipStream_t st);
 hipError_t ddn_dev_dmr_data_finish(const uint8_t* type, const uint8_t* pdu96, const uint8_t* info, const uint8_t* cw12,
                                    const uint8_t* rs_result, int n, uint8_t* bytes12, uint8_t* crc, uint8_t* r34_wanted, hipStream_t st);
+/* one thread per burst (workgroups of 64).  Unwanted burst: pool_n = 0, conf_crc = 0, unconf18 and conf18 zero, its pool24 entries left
+ * unwritten (hard18 / soft18 / list24 / list_n of that burst are not read).  Pool entries [pool_n .. 34) of a wanted burst are left
+ * unwritten as well. */
 hipError_t ddn_dev_dmr_r34_pick(const uint8_t* td98, const uint8_t* rel98, const uint8_t* wanted, const uint8_t* hard18,
                                 const uint8_t* soft18, const uint8_t* list24, const int32_t* list_n, int n, uint8_t* pool24,
                                 int32_t* pool_n, uint8_t* unconf18, uint8_t* conf18, uint8_t* conf_crc, hipStream_t st);
@@ -337,6 +359,9 @@ hipError_t ddn_dev_k5_nxdn(const uint8_t* sym, const uint8_t* rel, int n, int n_
                            uint8_t* out, int out_stride, hipStream_t st);
 hipError_t ddn_dev_k5_m17(const uint16_t* in, int n, int in_len, int u_len, const DdnPuncture* pu, uint8_t* out,
                           int out_stride, uint32_t* cost, hipStream_t st);
+/* groups of 16 code words.  Unwanted code word in a group with no wanted one: out and cost LEFT UNWRITTEN (whatever the buffers held
+ * stays: the callers in ddn_api_m17.cpp read a row only where the same flag is set).  Unwanted beside a wanted one: decoded like a wanted
+ * code word.  A decoded row's out_stride bytes are all written (zero beyond the decoded bits). */
 hipError_t ddn_dev_k5_m17_wanted(const uint16_t* in, int n, int in_len, int u_len, const DdnPuncture* pu, uint8_t* out, int out_stride,
                                  uint32_t* cost, const uint8_t* wanted, hipStream_t st);
 hipError_t ddn_dev_launch_fused(const DdnFusedArgs* a, const float* taps_host, int group, hipStream_t st);

@@ -35,7 +35,9 @@ float* ddn_fsk4_chain_disc_buffer(struct ddn_fsk4_chain* c);
 void* ddn_fsk4_chain_reads_done_event(struct ddn_fsk4_chain* c);
 /* the mixed chain's overlapped schedule: a second discriminator buffer for the odd steps (ddn_api_chain.cpp) */
 int ddn_p25_chain_double_disc(struct ddn_p25_chain* c);
-/* ddn_fec_viterbi_k5_batch over the code words d_wanted [n] marks, 0 = leave undecoded (ddn_api_fec.cpp) */
+/* ddn_fec_viterbi_k5_batch over the code words d_wanted [n] marks, 0 = leave undecoded (ddn_api_fec.cpp): an unmarked code word's
+ * d_out row and d_cost are left unwritten where none of the 16 code words of its group is marked, and decoded otherwise
+ * (ddn_dev_k5_m17_wanted in ddn_device.h) */
 int ddn_fec_viterbi_k5_batch_wanted(const uint16_t* d_soft, size_t n, int in_len, const uint8_t* punct, int p_len, uint8_t* d_out,
                                     int out_stride, uint32_t* d_cost, const uint8_t* d_wanted, void* hip_stream);
 /* the two kernels of ddn_mbe_synth_batch as separate calls (ddn_api_mbe.cpp) */

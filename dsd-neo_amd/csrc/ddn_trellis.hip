@@ -307,7 +307,9 @@ k_k5_nxdn(const uint8_t* __restrict__ sym, const uint8_t* __restrict__ rel, int 
         }
         m = nm;
     }
-    if (live && metrics_io) {
+    // (a row nobody wants that sits beside a wanted one is decoded with its group, but the metrics it carries are its caller's:
+    // they stay as they were)
+    if (live && metrics_io && (!wanted || wanted[(cw0 + c) / wanted_div] != 0)) {
         metrics_io[(size_t)(cw0 + c) * 16 + j] = (uint16_t)m;
     }
     if (live && j == 0) {
@@ -806,6 +808,44 @@ ddn_dev_r34(const uint8_t* dibits, const uint8_t* reliab, int n, uint8_t* out, h
     return hipGetLastError();
 }
 
+// The dynamic LDS a workgroup of k_k5_nxdn asks for (16 code words: symbols, reliabilities in the soft form, one decision word per
+// step) and what a workgroup may have on the current device.  64 KiB is what a kernel gets without asking; where the device offers
+// more and the length needs it, the kernel is opted in here (once per form and device), so a launch that passes `*need <= *limit`
+// is one the runtime takes.
+extern "C" hipError_t
+ddn_dev_k5_nxdn_lds(int n_steps, bool soft, size_t* need, size_t* limit) {
+    static size_t s_limit[64];
+    static size_t s_opted[64][2];
+    const size_t row = 2 * (size_t)n_steps + 2;
+    *need = 16 * row * (soft ? 2 : 1) + 16 * (size_t)n_steps * 2 + 16;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) {
+        return e;
+    }
+    if (dev < 0 || dev >= 64) {
+        return hipErrorInvalidDevice;
+    }
+    if (!s_limit[dev]) {
+        int v = 0;
+        e = hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+        if (e != hipSuccess) {
+            return e;
+        }
+        s_limit[dev] = (size_t)(v > 0 ? v : 0);
+    }
+    *limit = s_limit[dev];
+    if (*need > 65536 && *need <= *limit && *need > s_opted[dev][soft ? 1 : 0]) {
+        e = hipFuncSetAttribute(soft ? (const void*)k_k5_nxdn<true> : (const void*)k_k5_nxdn<false>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)*need);
+        if (e != hipSuccess) {
+            return e;
+        }
+        s_opted[dev][soft ? 1 : 0] = *need;
+    }
+    return hipSuccess;
+}
+
 extern "C" hipError_t
 ddn_dev_k5_nxdn_wanted(const uint8_t* sym, const uint8_t* rel, int n, int n_steps, int n_bits, uint16_t* metrics_io,
                        uint8_t* out, int out_stride, const uint8_t* wanted, int wanted_div, hipStream_t st) {
@@ -813,8 +853,14 @@ ddn_dev_k5_nxdn_wanted(const uint8_t* sym, const uint8_t* rel, int n, int n_step
         return hipSuccess;
     }
     dim3 grid((unsigned)((n + 15) / 16));
-    const size_t row = 2 * (size_t)n_steps + 2;
-    const size_t shm = 16 * row * (rel ? 2 : 1) + 16 * (size_t)n_steps * 2 + 16;
+    size_t shm = 0, limit = 0;
+    const hipError_t fit = ddn_dev_k5_nxdn_lds(n_steps, rel != nullptr, &shm, &limit);
+    if (fit != hipSuccess) {
+        return fit;
+    }
+    if (shm > limit) { // (never handed to the runtime: ddn_fec_nxdn_conv_* refuse such a length with a message before they get here)
+        return hipErrorInvalidValue;
+    }
     if (rel) {
         hipLaunchKernelGGL((k_k5_nxdn<true>), grid, dim3(256), shm, st, sym, rel, n, n_steps, n_bits, metrics_io, out,
                            out_stride, wanted, wanted_div > 0 ? wanted_div : 1);

@@ -616,7 +616,9 @@ typedef struct ddn_r34_candidate {
 /* P25 Phase 1 confirmed data: the rate 3/4 blocks' LLR list decoder == p25_mbf34_decode_soft_list (include/dsd-neo/protocol/p25/
  * p25p1_mbf34.h:19-29, src/protocol/p25/phase1/p25p1_mbf34.c:129-213): 98 LLR pairs in received order -> up to 8 candidates
  * {18 bytes: DBSN(7) | CRC9 | 16 payload bytes, metric}, cheapest first, ties by arrival, identical payloads once; d_counts [n].
- * d_wanted u8 [n] (optional): only items with a non-zero byte are decoded, the others get count 0. */
+ * d_wanted u8 [n] (optional): only items with a non-zero byte are decoded.  An item with a zero byte gets count 0 and its eight
+ * candidates are left unwritten (they keep what the buffer held); so are candidates [count .. 8) of a decoded item in the device
+ * form (the _host form's buffer starts zero-filled). */
 typedef struct ddn_p25_mbf34_candidate {
     uint8_t bytes[18];
     uint32_t metric;

@@ -117,6 +117,17 @@ orc_p25_12_soft_llr(const int16_t* llr196, uint8_t out12[12]) {
     return (int)(best >> 8);
 }
 
+/* What the last call of a de-duplicating list decoder (orc_p25_12_soft_llr_list, orc_p25_mbf34_list) met at its merge: out[0] = final
+ * survivors traced (before de-duplication), out[1] = those dropped because their bytes were already in the list.  TEST INFRASTRUCTURE:
+ * the edge tests prove with it that their inputs exercise the duplicate rule (not re-entrant, like the decoders). */
+static int g_list_paths, g_list_dups;
+
+void
+orc_list_last_stats(int out[2]) {
+    out[0] = g_list_paths;
+    out[1] = g_list_dups;
+}
+
 /* P25 1/2-rate list decoder, src/protocol/p25/p25_12.c:31-202: 8 survivors per state.  A state's survivor list is the
  * 8 smallest of the 32 extensions under the order (metric, predecessor state, predecessor rank) — which is what the
  * reference's "insert before the first strictly larger metric" gives when extensions arrive predecessor by
@@ -190,11 +201,13 @@ orc_p25_12_soft_llr_list(const int16_t* llr196, uint8_t* out_bytes /* [max][12] 
         memcpy(prev, cur, sizeof(prev));
     }
     int count = 0;
+    g_list_paths = g_list_dups = 0;
     for (int st = 0; st < 4; st++) {
         for (int rk = 0; rk < K; rk++) {
             if (prev[st][rk] == 0xFFFFFFFFu) {
                 continue;
             }
+            g_list_paths++;
             uint8_t path[49], bytes[12];
             int s = st, r = rk;
             for (int t = 48; t >= 0; t--) {
@@ -214,6 +227,7 @@ orc_p25_12_soft_llr_list(const int16_t* llr196, uint8_t* out_bytes /* [max][12] 
                 }
             }
             if (dup) {
+                g_list_dups++;
                 continue;
             }
             const uint32_t m = prev[st][rk];
@@ -635,11 +649,13 @@ orc_p25_mbf34_list(const int16_t* llr196, int max, uint8_t* out_bytes, uint32_t*
         memcpy(a, b, sizeof(a));
     }
     int n = 0;
+    g_list_paths = g_list_dups = 0;
     for (int s = 0; s < 8; s++) {
         for (int r = 0; r < K; r++) {
             if (!a[s][r].on) {
                 continue;
             }
+            g_list_paths++;
             uint8_t by[18];
             mbf_pack(a[s][r].st, by);
             int dup = 0;
@@ -647,6 +663,7 @@ orc_p25_mbf34_list(const int16_t* llr196, int max, uint8_t* out_bytes, uint32_t*
                 dup |= memcmp(out_bytes + 18 * i, by, 18) == 0;
             }
             if (dup) {
+                g_list_dups++;
                 continue;
             }
             int at = n;

@@ -35,14 +35,50 @@ def candidate_metric(td98, rel98, b18):
     dei, rdei = np.zeros(98, np.int64), np.zeros(98, np.int64)
     dei[il] = np.asarray(td98, np.int64) & 3
     rdei[il] = np.asarray(rel98, np.int64)
-    bits = np.unpackbits(np.asarray(b18, np.uint8))
-    states = [_int(bits[3 * k:3 * k + 3]) for k in range(48)] + [0]
-    metric, prev = 0, 0
-    for t in range(49):
-        x = int(p2n[fsm[prev * 8 + states[t]] & 15]) ^ int((dei[2 * t] << 2) | dei[2 * t + 1])
-        metric += (((x >> 3) & 1) + ((x >> 2) & 1)) * int(rdei[2 * t]) + (((x >> 1) & 1) + (x & 1)) * int(rdei[2 * t + 1])
-        prev = states[t]
-    return metric
+    bits = np.unpackbits(np.asarray(b18, np.uint8)).astype(np.int64)
+    states = np.concatenate([bits[0:144:3] * 4 + bits[1:144:3] * 2 + bits[2:144:3], [0]])
+    prev = np.concatenate([[0], states[:-1]])
+    x = np.asarray(p2n, np.int64)[np.asarray(fsm, np.int64)[prev * 8 + states] & 15] ^ ((dei[0::2] << 2) | dei[1::2])
+    return int(((((x >> 3) & 1) + ((x >> 2) & 1)) * rdei[0::2] + (((x >> 1) & 1) + (x & 1)) * rdei[1::2]).sum())
+
+
+def pool_of(td98, rel98, sources):
+    """dmr_dburst_pick_trellis_payload() (src/protocol/dmr/dmr_dburst.c:397-536), its candidate pool: the 18-byte payloads of `sources`
+    (hard decode, soft decode, then the list decoder's candidates) in that order, identical payloads once, at most 34; each with its
+    dmr_r34_candidate_metric(), whether its CRC9 checks and its DBSN -> (pool [(bytes18, metric, crc_ok, dbsn)], how many entries the
+    first two sources left)"""
+    pool = []
+    n_hs = 0
+    for k, b in enumerate(sources):
+        b = np.asarray(b, np.uint8)
+        if not any(np.array_equal(b, q[0]) for q in pool) and len(pool) < 34:
+            bits = np.unpackbits(b)
+            c9 = p25gen.crc9(list(bits[16:144]) + list(bits[:7]))
+            pool.append((b.copy(), candidate_metric(td98, rel98, b), int(c9 == (_int(bits[7:16]) ^ 0x1FF)), int(b[0]) >> 1))
+        if k == 1:
+            n_hs = len(pool)
+    return pool, n_hs
+
+
+def _lowest(pool, idx):
+    best = -1
+    for j in idx:
+        if best < 0 or pool[j][1] < pool[best][1]:
+            best = j
+    return best
+
+
+def pick_unconfirmed(pool, n_hs):
+    """the pick while state->data_conf_data = 0 (dmr_dburst.c:397-536): the cheaper of the hard and the soft decode, the first on a tie;
+    the list is not consulted -> pool index (-1: empty pool)"""
+    return _lowest(pool, range(n_hs))
+
+
+def pick_confirmed(pool):
+    """the pick for confirmed data before the DBSN expectation is applied (dmr_dburst.c:397-536): the cheapest candidate whose CRC9
+    checks, else the cheapest; the first on a tie -> (pool index, whether a candidate with a good CRC9 exists)"""
+    crc = _lowest(pool, [j for j in range(len(pool)) if pool[j][2]])
+    return (crc if crc >= 0 else _lowest(pool, range(len(pool)))), int(crc >= 0)
 
 
 def r34_pool(td98, rel98):
@@ -56,26 +92,9 @@ def r34_pool(td98, rel98):
     o.orc_r34_decode_list.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lm, lb = np.zeros(32, np.int32), np.zeros((32, 18), np.uint8)
     nl = o.orc_r34_decode_list(td.ctypes.data, rel.ctypes.data, 32, lm.ctypes.data, lb.ctypes.data)
-    pool = []
-    n_hs = 0
-    for k, b in enumerate([hard, soft] + [lb[j] for j in range(nl)]):
-        if not any(np.array_equal(b, q[0]) for q in pool) and len(pool) < 34:
-            bits = np.unpackbits(b)
-            c9 = p25gen.crc9(list(bits[16:144]) + list(bits[:7]))
-            pool.append((b.copy(), candidate_metric(td, rel, b), int(c9 == (_int(bits[7:16]) ^ 0x1FF)), int(b[0]) >> 1))
-        if k == 1:
-            n_hs = len(pool)
-
-    def lowest(idx):
-        best = -1
-        for j in idx:
-            if best < 0 or pool[j][1] < pool[best][1]:
-                best = j
-        return best
-    u = lowest(range(n_hs))
-    crc = lowest([j for j in range(len(pool)) if pool[j][2]])
-    c = crc if crc >= 0 else lowest(range(len(pool)))
-    return pool, pool[u][0], pool[c][0], int(crc >= 0)
+    pool, n_hs = pool_of(td, rel, [hard, soft] + [lb[j] for j in range(nl)])
+    c, crc = pick_confirmed(pool)
+    return pool, pool[pick_unconfirmed(pool, n_hs)][0], pool[c][0], crc
 
 
 def data_burst(dib144, rel144):

@@ -108,7 +108,7 @@ def gen_nxdn(rng, n, n_steps, p_err=0.04, p_erase=0.05, random_frac=0.2):
 
 def gen_m17(rng, n, in_len, sigma=9000.0, random_frac=0.2):
     """-> soft [n, in_len] uint16 (0 = strong 0, 0xFFFF = strong 1)."""
-    L = in_len // 2
+    L = (in_len + 1) // 2          # (an odd in_len ends on the first soft bit of a pair)
     data = rng.integers(0, 2, (n, L)).astype(np.int64)
     data[:, -4:] = 0
     enc = conv_k5_encode(data).astype(np.float64)[:, :in_len]

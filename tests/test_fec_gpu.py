@@ -207,9 +207,14 @@ def test_p25_half_rate_list(built):
             assert np.array_equal(cand[i, :no, 12:].copy().view(np.uint32)[:, 0], om[:no]), (i, mx)
             assert not cand[i, no:].any()
     # drop-in name, one codeword
-    one = (C.c_uint8 * (16 * 8))()
-    k = ddn.lib().p25_12_soft_llr_list(None, llr[9].ctypes.data, C.addressof(one), 8)
-    assert k == cnt[9] or True
+    for mx in (8, 3):
+        one = np.full((8, 16), 0xA5, np.uint8)
+        k = ddn.lib().p25_12_soft_llr_list(None, llr[9].ctypes.data, one.ctypes.data, mx)
+        ob = np.zeros((8, 12), np.uint8)
+        om = np.zeros(8, np.uint32)
+        assert k == o.orc_p25_12_soft_llr_list(llr[9].ctypes.data, ob.ctypes.data, om.ctypes.data, mx) == mx
+        assert np.array_equal(one[:k, :12], ob[:k]) and np.array_equal(one[:k, 12:].copy().view(np.uint32)[:, 0], om[:k])
+        assert (one[k:] == 0xA5).all()                    # the drop-in writes its count of candidates, as the reference does
 
 
 @pytest.mark.parametrize("weighted", [0, 1])
