@@ -124,6 +124,7 @@ PROTOTYPES = {
     "ddn_cq_rx_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                C.c_void_p]),
     "ddn_cq_rx_get_state": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "ddn_cq_rx_set_debug_flags": (C.c_int, [C.c_void_p, C.c_int]),
     "ddn_p25_rx_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "ddn_p25_rx_destroy": (None, [C.c_void_p]),
     "ddn_p25_rx_reset": (C.c_int, [C.c_void_p]),
@@ -1286,11 +1287,13 @@ class CqRx:
     """ddn_cq_rx batch object with device buffers of its own (host-buffer convenience wrapper used by the tests):
     run(symbols f32 [B][n], counts) -> (rec u8 [B][n][10], flags u8 [B][n], counts i32 [B], events [B] lists of (pos, kind, a, b, data4))"""
 
-    def __init__(self, n_channels, protocol=CQ_P25P1, lock_symbols=0, snr_db=0.0, max_events=1024):
+    def __init__(self, n_channels, protocol=CQ_P25P1, lock_symbols=0, snr_db=0.0, max_events=1024, debug_flags=0):
         self.B, self.E = n_channels, max_events
         cfg = CqRxConfig(n_channels, protocol, lock_symbols, 0, snr_db)
         self.h = C.c_void_p()
         _check(lib().ddn_cq_rx_create(C.byref(cfg), C.byref(self.h)), "ddn_cq_rx_create")
+        if debug_flags:
+            _check(lib().ddn_cq_rx_set_debug_flags(self.h, debug_flags), "ddn_cq_rx_set_debug_flags")
         self.d_ev, self.d_nev, self.d_evd = (C.c_void_p() for _ in range(3))
         l = lib()
         _check(l.ddn_device_alloc(n_channels * max_events * 16, C.byref(self.d_ev)), "alloc")

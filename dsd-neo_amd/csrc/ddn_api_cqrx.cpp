@@ -118,6 +118,15 @@ ddn_cq_rx_set_events(ddn_cq_rx* b, int32_t* d_events, int32_t* d_n_events, int32
 }
 
 extern "C" int
+ddn_cq_rx_set_debug_flags(ddn_cq_rx* b, int flags) {
+    if (!b) {
+        return DDN_EINVAL;
+    }
+    b->dc.dbg = flags;
+    return DDN_OK;
+}
+
+extern "C" int
 ddn_cq_rx_run(ddn_cq_rx* b, const float* d_symbols, const int32_t* d_counts_in, size_t n, size_t sym_stride, uint8_t* d_records10,
               uint8_t* d_flags, int32_t* d_counts, size_t max_symbols, void* hip_stream) {
     if (!b || !d_symbols || !d_records10 || !d_flags || !d_counts || n > 0x7FFFFFFF || sym_stride < n) {

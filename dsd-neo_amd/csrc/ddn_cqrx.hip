@@ -195,6 +195,12 @@ cq_digitize(float sym, float center, int map_idx, int negative, const float leve
     rel8 = clamp255(a1 < a0 ? a1 : a0);
 }
 
+// the half-rate decoder's short cut as a call: inlined, its registers are allocated on top of the per-symbol path's (capped below)
+__device__ __noinline__ bool
+cq_hard_path(const ddn_p25h::Scratch& sc, int lane, uint32_t* by) {
+    return ddn_p25h::half_rate_hard_path_wave(sc, lane, by);
+}
+
 // (round 6) three wavefronts per SIMD: left to itself the kernel compiled to 256 + registers (the handlers' decoders, inlined) - ONE
 // wavefront per SIMD, four channels per CU, 4096 channels in four rounds (29 ms per 4096 x 4800 symbols).  The per-symbol path needs a
 // fraction of that.  Capped at 168 registers twelve channels are resident per CU (the chain objects at 4096 channels: P25 CQPSK 72.6
@@ -330,7 +336,11 @@ k_cq_rx(const float* __restrict__ symbols, const int32_t* __restrict__ counts_in
     // tsbk_decode_repetition_bytes(): list-8, the first CRC16-clean candidate, else the best one
     auto half_rate_select = [&](uint32_t by[3], int& crc_ok) -> int {
         wave_sync();
-        ddn_p25h::half_rate_best_wave(L.sc, lane, by);
+        // a clean block's best path is its hard dibits' walk through the trellis (ddn_p25h_dev.h); cfg.dbg bit 1 switches the short
+        // cut off (A/B for the tests)
+        if ((cfg.dbg & 1) || !cq_hard_path(L.sc, lane, by)) {
+            ddn_p25h::half_rate_best_wave(L.sc, lane, by);
+        }
         crc_ok = ddn_p25h::crc16_ok_wave(L.sc, by, lane);
         int sel = 0;
         if (!crc_ok) {

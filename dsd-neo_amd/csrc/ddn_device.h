@@ -409,6 +409,7 @@ typedef struct DdnCqConfig {
     int snr_scale;     /* the CQPSK SNR weight as the numerator over 256 (204 + (w256 >> 2)), -1 = no weight (SNR not available) */
     int nid_threshold; /* p25p1_get_erasure_threshold() */
     int max_events;
+    int dbg;           /* A/B experiments (ddn_cq_rx_set_debug_flags): 1 = no hard-path short cut ahead of the half-rate decoder */
     uint64_t target[2][4]; /* [polarity][identity, X2400, N1200, P1200]: the sync word as raw dibits, oldest in the high bits */
 } DdnCqConfig;
 typedef struct DdnCqState { /* one channel, carried from call to call */

@@ -11,10 +11,11 @@
 //                                                                    p25p1_mdpu.c:177-198,270-307
 // One decision at a time, the whole wavefront on it: the symbols of the phase are sliced (dibit + LLRs, ddn_slicer_dev.h) one
 // per lane out of the loop's in-frame history ring; the NID goes through the full ladder (ddn_nid_dev.h: hard decode, NAC retry,
-// Chase search one candidate per lane); a trellis block takes a short cut that is exact - when every LLR is non-zero, the hard
-// dibits walk the trellis from state 0 and the bytes pass the CRC16, the list decoder's best candidate IS that code word
-// (its metric is 0 and every other path's is positive) and the CRC scan stops at it - and otherwise the list-8 decoder proper,
-// four lanes (one per state) as ddn_trellis.hip's k_p25_half_rate_list.
+// Chase search one candidate per lane); a trellis block takes a short cut that is exact (half_rate_hard_path_wave) - when every
+// LLR is non-zero and the hard dibits walk the trellis from state 0, that walk IS the best path and the list decoder's first
+// candidate (its metric is 0 and every other path's is positive), so the 49-step add-compare-select chain is not run; when its
+// bytes pass the CRC16 the CRC scan stops at it.  Otherwise the best path proper (half_rate_best_wave), and when that fails its
+// CRC the list-8 decoder (half_rate_list_wave: one lane per (state, rank), as ddn_trellis.hip's k_p25_half_rate_list).
 #ifndef DDN_P25H_DEV_H
 #define DDN_P25H_DEV_H
 #include <hip/hip_runtime.h>
@@ -65,11 +66,31 @@ deinterleave98(int i) { // as ddn_trellis.hip: 49 dibit pairs dealt to 4 lanes r
     return 2 * (lane + 4 * k) + (i & 1);
 }
 
-__device__ __forceinline__ int
-half_rate_nibble(int idx) { // trellis output for (state << 2) | next state, src/protocol/p25/p25_12.c:19
-    // {2, 12, 1, 15, 14, 0, 13, 3, 9, 7, 10, 4, 5, 11, 6, 8} packed 4 bits each
-    return (int)((0x86B5'4A79'3D0E'F1C2ull >> (4 * idx)) & 15u);
+// trellis output for (state << 2) | next state, src/protocol/p25/p25_12.c:19:
+// {2, 12, 1, 15, 14, 0, 13, 3, 9, 7, 10, 4, 5, 11, 6, 8} packed 4 bits each
+constexpr uint64_t HALF_RATE_NIBBLES = 0x86B5'4A79'3D0E'F1C2ull;
+__host__ __device__ constexpr int
+half_rate_nibble(int idx) {
+    return (int)((HALF_RATE_NIBBLES >> (4 * idx)) & 15u);
 }
+// the table read the other way: (state << 2) | next state of the one branch that emits a nibble, packed 4 bits each
+__host__ __device__ constexpr uint64_t
+half_rate_branches_by_nibble() {
+    uint64_t inv = 0;
+    for (int idx = 0; idx < 16; idx++) {
+        inv |= (uint64_t)idx << (4 * half_rate_nibble(idx));
+    }
+    return inv;
+}
+__host__ __device__ constexpr bool
+half_rate_nibbles_distinct() {
+    unsigned seen = 0;
+    for (int idx = 0; idx < 16; idx++) {
+        seen |= 1u << half_rate_nibble(idx);
+    }
+    return seen == 0xFFFFu;
+}
+static_assert(half_rate_nibbles_distinct(), "half_rate_hard_path_wave: one branch per nibble, or the look-up is not a function");
 
 __device__ __forceinline__ int
 crc16_ok(const uint32_t w[3]) { // p25_crc.c:18-36 over bytes 0..9 of the 12 (big-endian in the words' byte order below)
@@ -401,6 +422,45 @@ half_rate_best_wave(Scratch& sc, int lane, uint32_t by[3]) {
     by[0] = sc.byw[0];
     by[1] = sc.byw[1];
     by[2] = sc.byw[2];
+}
+
+// The exact short cut ahead of half_rate_best_wave(), LLR pairs in sc.d.  The hard bits (a branch bit of 1 costs max(0, -llr), so a
+// positive LLR says 1 - the sign the slicer gives the dibit, ddn_slicer_dev.h) of step t are one nibble, and one branch
+// (predecessor state, input dibit) emits it: lane t looks it up.  The 49 branches are a path of the trellis iff step 0 leaves state 0
+// and every step leaves the state the step before entered (one lane shift, one compare, one ballot).  Such a path costs 0; with
+// every LLR non-zero any other path differs from it in a bit that costs something, so it is the unique minimum: what
+// half_rate_best_wave() returns whatever its tie rules, and the list decoder's first candidate.  A zero LLR costs nothing either
+// way and lets another path tie, so a block that carries one is left to the decoder proper.  True: by[] holds the 12 bytes in
+// every lane, in half_rate_best_wave()'s layout.  False: by[] is untouched.
+__device__ __forceinline__ uint32_t
+row_or(uint32_t v) { // OR over each row of 16 lanes, in every lane of the row
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);  // quad_perm [1,0,3,2]
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);  // quad_perm [2,3,0,1]
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true); // row_half_mirror
+    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true); // row_mirror
+    return v;
+}
+__device__ __forceinline__ bool
+half_rate_hard_path_wave(const Scratch& sc, int lane, uint32_t by[3]) {
+    constexpr uint64_t BR = half_rate_branches_by_nibble();
+    const int t = lane < 49 ? lane : 48;
+    const int32_t p0 = sc.d[2 * t], p1 = sc.d[2 * t + 1];
+    const int l0 = (int16_t)(p0 & 0xFFFF), l1 = (int16_t)(p0 >> 16), l2 = (int16_t)(p1 & 0xFFFF), l3 = (int16_t)(p1 >> 16);
+    const bool nonzero = l0 != 0 && l1 != 0 && l2 != 0 && l3 != 0;
+    const int nib = (l0 > 0 ? 8 : 0) | (l1 > 0 ? 4 : 0) | (l2 > 0 ? 2 : 0) | (l3 > 0 ? 1 : 0);
+    const int br = (int)((BR >> (4 * nib)) & 15u);
+    const int ps = br >> 2, ns = br & 3;
+    int came = __shfl_up(ns, 1); // the state the step before entered
+    came = lane == 0 ? 0 : came;
+    if (__ballot(lane < 49 && !(nonzero && ps == came)) != 0) {
+        return false;
+    }
+    // the state after step t = the decoded dibit t (step 48 is the flush)
+    const uint32_t v = row_or(lane < 48 ? (uint32_t)ns << (8 * ((lane >> 2) & 3) + 6 - 2 * (lane & 3)) : 0u);
+    by[0] = (uint32_t)__builtin_amdgcn_readlane((int)v, 0);
+    by[1] = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
+    by[2] = (uint32_t)__builtin_amdgcn_readlane((int)v, 32);
+    return true;
 }
 
 // symbols p25_mpdu_read_repetition() consumes for one repetition starting with the counter at sk0 (98 data dibits, <= 101 reads)

@@ -943,6 +943,19 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
             phase = PH_NID;
         }
         int ext = 0, more = 0;
+        // cfg.dbg bit 2147483648 (A/B for the tests): every trellis block through half_rate_best_wave(), every verdict after its decode
+        const bool quick = ((unsigned)cfg.dbg & 2147483648u) == 0;
+        auto answer = [&](int ext_now, int more_now) { // the verdict to the waiting lane (once per request)
+            if (lane == c) {
+                H.rsp_ext[c] = ext_now;
+                H.rsp_more[c] = more_now;
+#if DDN_RX_CYCLES
+                H.rsp_t[c] = (int)clock64();
+#endif
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+                __hip_atomic_store(&H.rsp_seq[c], seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        };
         int ev_kind = 0, ev_a = 0, ev_b = 0;
         int32_t pay0 = 0, pay1 = 0, pay2 = 0, pay3 = 0; // what the decision decoded (cfg.event_data)
         auto slice_at = [&](int i, int& d, int& relb, int& l0, int& l1) {
@@ -1057,11 +1070,22 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
             const int sk_after = block_counter_after(sk0, nsym, n_data);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            // The third block of a TSDU ends the phase whatever it decodes (last || block >= 3 below): its verdict goes out now and
+            // the decode only feeds the event.  The phase's symbols were all copied out of the lane's history ring by the slice above
+            // (sc.d; the release fence of answer() has those reads done), and nothing below reads the ring or the request words
+            // again - the lane may overwrite both as soon as it goes on.  Its next request is picked up after this one's event is
+            // written (one decision at a time), so the channel's events keep their order.
+            if (quick && phase == PH_TSBK && block >= 2) {
+                answer(0, 0);
+            }
             // tsbk_decode_repetition_bytes(): list-8 decode, the first CRC16-clean candidate, else the best one.  The list's
-            // first candidate is the plain best path (ddn_p25h_dev.h), so the list proper is only run when that fails its CRC.
+            // first candidate is the plain best path (ddn_p25h_dev.h), so the list proper is only run when that fails its CRC;
+            // and the best path of a clean block is its hard dibits' walk through the trellis, found without the decoder.
             dbg_stamp(0);
             uint32_t by[3];
-            half_rate_best_wave(sc, lane, by);
+            if (!(quick && half_rate_hard_path_wave(sc, lane, by))) {
+                half_rate_best_wave(sc, lane, by);
+            }
             dbg_stamp(1);
             int crc_ok = crc16_ok_wave(sc, by, lane), sel = 0;
             dbg_stamp(2);
@@ -1132,18 +1156,14 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
             hs.nac = nac;
             hs.p2_cc = p2cc;
             h_served = seq;
-            H.rsp_ext[c] = ext;
-            H.rsp_more[c] = more;
-#if DDN_RX_CYCLES
-            H.rsp_t[c] = (int)clock64();
-#endif
+        }
+        if (!(quick && ev_kind == EV_TSBK && ev_a >= 2)) { // (a TSDU's third block: answered above, ahead of its decode)
+            answer(ext, more);
         }
 #if DDN_RX_CYCLES
         dbg_free = (int)clock64();
 #endif
         if (lane == c) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-            __hip_atomic_store(&H.rsp_seq[c], seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             if (ev_kind) {
                 if (nev < cfg.max_events && gch < n_channels) {
                     int32_t* e = events + ((size_t)gch * cfg.max_events + nev) * 4;
@@ -1278,6 +1298,8 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
             const unsigned long long pend = __ballot(lane < CPW && rq != h_served);
             if (pend != 0) {
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                // (lowest channel first.  Serving a pending NID - 2 k cycles - ahead of a pending block was tried once the block's
+                // decision was short: the step did not move, profiles/r11_rxw_cycle_tables.txt)
                 const int c = __ffsll((long long)pend) - 1;
                 dbg_pend = __popcll(pend);
 #if DDN_RX_CYCLES

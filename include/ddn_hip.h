@@ -221,7 +221,8 @@ int ddn_p25_rx_set_channels_per_wave(ddn_p25_rx* b, int channels_per_wave);
 int ddn_p25_rx_set_filter_in_loop(ddn_p25_rx* b, int on);
 /* A/B selectors of the loop kernel's schedule (which of two equivalent code paths a launch takes; the results never depend on them):
  * 4096 = the bulk hunting passes one owner lane at a time, 2097152 = lean runs of one trip, 16777216 = four recurrence waves of two
- * lanes ... (ddn_rx.hip documents each bit where it is read).  For the parity tests and timing tools; 0 = the product's choice. */
+ * lanes, 2147483648 (the sign bit) = every trellis block through the half-rate decoder and every handler verdict after its decode
+ * ... (ddn_rx.hip documents each bit where it is read).  For the parity tests and timing tools; 0 = the product's choice. */
 int ddn_p25_rx_set_debug_flags(ddn_p25_rx* b, int flags);
 size_t ddn_p25_rx_max_symbols(const ddn_p25_rx* b, size_t n);
 int ddn_p25_rx_run(ddn_p25_rx* b, const float* d_disc, size_t n, uint8_t* d_records10, uint8_t* d_flags,
@@ -575,6 +576,9 @@ int ddn_cq_rx_run(ddn_cq_rx* b, const float* d_symbols, const int32_t* d_counts_
                   uint8_t* d_flags, int32_t* d_counts, size_t max_symbols, void* hip_stream);
 /* {centre, max, min, map index, last sync (0 none, 1 +, 2 -), in frame, hunted symbols, extrema window index} of one channel */
 int ddn_cq_rx_get_state(ddn_cq_rx* b, int channel, float out8[8]);
+/* A/B selector as ddn_p25_rx_set_debug_flags (the results never depend on it): 1 = every trellis block through the half-rate
+ * decoder, without the hard-path short cut ahead of it.  For the parity tests; 0 = the product's choice. */
+int ddn_cq_rx_set_debug_flags(ddn_cq_rx* b, int flags);
 
 /* ---- batched trellis / Viterbi decoders (bit-exact integer) ------------------------------------------
  * d_* = device pointers, asynchronous on hip_stream; *_host = host pointers, synchronous.
