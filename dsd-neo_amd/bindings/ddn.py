@@ -1234,9 +1234,9 @@ class P25P2ChainResults(C.Structure):  # == ddn_p25p2_chain_results
 
 class P25P2ChainC:
     """ddn_p25p2_chain: I/Q of B Phase 2 channels -> MAC PDUs + PCM of both logical channels, one C call per batch of samples.
-    `handle`: a non-owning view of a chain object that exists already (a node part's), as Fsk4ChainC has it"""
+    `handle`: a non-owning view of a chain object that exists already (a node part's), as Fsk4ChainC has it; sample_rate_hz 0 = 48000"""
 
-    def __init__(self, seeds44, samples_per_call, block_len=8192, input_format=0, vocoder=1, max_groups=0, handle=None):
+    def __init__(self, seeds44, samples_per_call, block_len=8192, input_format=0, vocoder=1, max_groups=0, handle=None, sample_rate_hz=0):
         import numpy as np
         self.np = np
         self.own = handle is None
@@ -1244,7 +1244,7 @@ class P25P2ChainC:
         if handle is not None:
             self.h = C.c_void_p(handle)
             return
-        cfg = P25P2ChainConfig(self.B, samples_per_call, block_len, input_format, 0, vocoder, max_groups, 0.0)
+        cfg = P25P2ChainConfig(self.B, samples_per_call, block_len, input_format, sample_rate_hz, vocoder, max_groups, 0.0)
         seeds = np.ascontiguousarray(seeds44, np.uint64)
         self.h = C.c_void_p()
         _check(lib().ddn_p25p2_chain_create(C.byref(cfg), seeds.ctypes.data, C.byref(self.h)), "ddn_p25p2_chain_create")

@@ -13,6 +13,7 @@ import ddn
 import orc
 import p2capture
 import p2seq
+from chain_p25p2_stream import oracle_groups
 from conftest import golden
 from test_oracle_p25p2_capture import SACCH_OCTETS
 
@@ -27,28 +28,12 @@ def _upload(a):
     return p
 
 
-def oracle_groups(iq, n_call):
-    """-> (symbols, rec4, flags, sync positions, bits [G][1400], llr [G][1400]) of the whole stream, front end block structure per call"""
-    x = ((iq.astype(np.float32) - 127.5) * np.float32(1.0 / 127.5)).astype(np.float32)
-    fe = orc.OracleCqpskFe(rate=48000, sym_rate=6000)
-    sym = np.concatenate([fe.run(x[k:k + n_call], 8192) for k in range(0, len(x), n_call)])
-    rec, fl = orc.OracleCqRx(orc.CQ_P25P2).run(sym)
-    pos = [int(p) for p in np.flatnonzero(fl & 2) if p + 700 < len(sym)]
-    bits = np.zeros((len(pos), 1400), np.uint8)
-    llr = np.zeros((len(pos), 1400), np.int16)
-    for k, p in enumerate(pos):
-        d = rec[p + 1:p + 701]
-        bits[k, 0::2], bits[k, 1::2] = (d[:, 0] >> 1) & 1, d[:, 0] & 1
-        llr[k, 0::2], llr[k, 1::2] = d[:, 2], d[:, 3]
-    return sym, rec, fl, pos, bits, llr
-
-
 @pytest.mark.parametrize("n_call", [48000, 32000])
 def test_capture_from_iq_to_sacch_pdus(built, n_call):
     iq = np.ascontiguousarray(golden("iq_p25p2_cc.npz")["iq"])
     n_total = (len(iq) // n_call) * n_call
     iq = iq[:n_total]
-    sym, rec, fl, pos, wb, wl = oracle_groups(iq, n_call)
+    sym, rec, fl, pos, wb, wl, _ = oracle_groups(iq, n_call)
     assert len(pos) >= 10
     want = p2seq.run_groups(wb, wl, p2capture.WACN, p2capture.SYSID, p2capture.NAC, p2seq.new_state())
     ch = ddn.P25P2ChainC([SEED, SEED, 0], n_call, vocoder=0)

@@ -9,39 +9,12 @@ import pytest
 import ddn
 import p2capture
 import p2seq
+from chain_p25p2_stream import compare
 from test_oracle_p25p2_capture import SACCH_OCTETS
 from test_oracle_p25p2_seq import capture_groups
 
 pytestmark = pytest.mark.gpu
 FZ = 7919 * int(os.environ.get("DDN_FUZZ_BASE", "0"))
-
-
-def compare(got, want_rows, c):
-    """got = P25P2Groups.run() arrays; want_rows = run_groups() dicts of channel c (rows in order)"""
-    info, pay, fr, rel, ess = got
-    G = info.shape[1]
-    n = 0
-    for k, w in enumerate(want_rows):
-        g, ts = divmod(k, 4)
-        i = info[c, g, ts]
-        tag = (c, g, ts, w["action"])
-        assert (i[0], i[1], i[2], i[3], i[4]) == (w["duid"], w["isch"], w["offset"], w["slot"], w["action"]), (tag, i.tolist())
-        a = w["action"]
-        if a in (p2seq.A_4V, p2seq.A_2V):
-            assert i[6] == w["fourv"], tag
-            assert np.array_equal(fr[c, g, ts], w["fr"]) and np.array_equal(rel[c, g, ts], w["rel"]), tag
-            if a == p2seq.A_2V:
-                assert i[5] == w["ec"] and bool(i[7] & 8) == bool(w["ess_ok"]) and np.array_equal(ess[c, g, ts], w["ess"]), (tag, i.tolist(), w["ec"])
-        elif a in (p2seq.A_SACCH_S, p2seq.A_SACCH_C, p2seq.A_FACCH_C, p2seq.A_FACCH_S, p2seq.A_LCCH_C, p2seq.A_LCCH_S):
-            assert i[5] == w["ec"] and (i[7] & 1) == w["used"] and bool(i[7] & 2) == bool(w["crc12"]), (tag, i.tolist(), w["ec"], w["used"])
-            if a not in (p2seq.A_FACCH_C, p2seq.A_FACCH_S):
-                assert bool(i[7] & 4) == bool(w["crc16"]), tag
-            assert np.array_equal(pay[c, g, ts], w["payload"]), tag
-        else:
-            assert i[5] == 0 and i[7] == 0 and not pay[c, g, ts].any() and not fr[c, g, ts].any(), tag
-        n += 1
-    assert n == G * 4
-    return n
 
 
 def test_the_reference_capture_through_the_sequencing_stage(built):
