@@ -873,7 +873,7 @@ chain_decode(ddn_p25_chain* c, int cur, int flush, hipStream_t st, hipEvent_t ev
     // Last on this stream, the kernels that take a large share of a CU's LDS (k_p25_lsd 49 KB, k_p25_half_rate_list 80 KB per
     // workgroup): in the pipelined forms the next call's front end (153 KB per CU) runs beside this decode, and a workgroup that needs
     // more LDS than the front end leaves (10 KB) waits for one of its workgroups to end - i.e. ~2 ms, with everything queued behind
-    // it.  Everything above fits beside the front end (k_rs63 7.6 KB, k_golay24 8 KB).
+    // it.  Everything above fits beside the front end (k_rs63 6.8 KB, k_golay24 8 KB).
     ddn_sel_set(c->d_lists + (size_t)DDN_LIST_LSD * S, c->d_list_n + DDN_LIST_LSD);
     DDN_TRY(ddn_p25p1_framer_gather_lsd(c->fr, rec, c->d_cnt_full[cur], stride, c->d_lsd, c->d_lsd_llr, c->d_vldu, st));
     DDN_TRY(ddn_fec_p25_lsd_batch(c->d_lsd, c->d_lsd_llr, S * 2, c->d_lsd_ok, st));

@@ -29,10 +29,7 @@ k_nid_decode(const uint8_t* __restrict__ bits63, const uint8_t* __restrict__ rel
     __shared__ uint8_t ex[128];
     __shared__ uint8_t lg[64];
     __shared__ uint8_t work[(23 + 24 + 24 + 24) * 64];
-    if (threadIdx.x == 0) {
-        gf_fill(ex, lg);
-    }
-    __syncthreads();
+    gf_fill_wg(ex, lg);
     const Gf gf = {ex, lg};
     const Work wk = {work + threadIdx.x, work + 23 * 64 + threadIdx.x, work + 47 * 64 + threadIdx.x,
                      work + 71 * 64 + threadIdx.x};
@@ -159,15 +156,9 @@ k_nid_chase(const uint8_t* __restrict__ bits63, const uint8_t* __restrict__ rel6
     }
     const int lane = threadIdx.x;
     if (lane == 0) {
-        gf_fill(ex, lg);
-        int k = 0;
-        for (int m = 0; m < 256; m++) { // masks with at most three flips, increasing: 93 of them (42 below 64, 64 below 128)
-            if (__popc((unsigned)m) <= 3) {
-                masks[k++] = (uint8_t)m;
-            }
-        }
+        chase_masks_fill(masks);
     }
-    __syncthreads();
+    gf_fill_wg(ex, lg);
     const Gf gf = {ex, lg};
     const Work wk = {work + lane, work + 23 * 64 + lane, work + 47 * 64 + lane, work + 71 * 64 + lane};
     const int c = chase_list[blockIdx.x];
@@ -269,14 +260,13 @@ k_nid_wave(const uint8_t* __restrict__ bits63, const uint8_t* __restrict__ rel63
     __shared__ uint8_t relb[64];
     const int lane = threadIdx.x;
     if (lane == 0) {
-        gf_fill(ex, lg);
         chase_masks_fill(masks);
     }
     const int c = blockIdx.x;
     const uint8_t* bp = bits63 + (size_t)c * 63;
     const uint64_t w = __ballot(lane < 63 && bp[lane < 63 ? lane : 0] != 0);
     relb[lane] = (rel63 && lane < 63) ? rel63[(size_t)c * 63 + lane] : 0;
-    __syncthreads();
+    gf_fill_wg(ex, lg);
     const Gf gf = {ex, lg};
     const Work wk = {work + lane, work + 23 * 64 + lane, work + 47 * 64 + lane, work + 71 * 64 + lane};
     const int par = parity ? (parity[c] ? 1 : 0) : 0;

@@ -237,7 +237,7 @@ k_cq_rx(const float* __restrict__ symbols, const int32_t* __restrict__ counts_in
     }
     ddn_p25h::crc_cols_fill(L.sc.crc_cols, lane);
     if (lane == 0) {
-        ddn_nid::gf_fill(L.sc.ex, L.sc.lg);
+        ddn_gf64::gf_fill(L.sc.ex, L.sc.lg);
         ddn_nid::chase_masks_fill(L.sc.masks);
     }
     float s_max = gs->max, s_min = gs->min, lmin = gs->lmin, lmax = gs->lmax;

@@ -265,6 +265,11 @@ hipError_t ddn_dev_p25p2_xcch(int kind, const uint8_t* bits360, const int16_t* l
                               hipStream_t st);
 hipError_t ddn_dev_rs28(int kind, uint8_t* payload_bits, const uint8_t* parity_bits, const int8_t* erasures,
                         const uint8_t* n_erasures, int n, int32_t* status, hipStream_t st);
+// ddn_rs.hip, for the Phase 2 stages (ddn_p25p2_burst.hip): the decode with the first n_fixed erasures of each section's list, then,
+// for the sections that failed, the retries with 1 .. max_add more; ess_rule: a plain decode that located 15 symbols or more is not taken
+// (between two files of the library only: not exported)
+__attribute__((visibility("hidden"))) hipError_t ddn_rs28_ranked(int kind, uint8_t* payload_bits, const uint8_t* parity_bits, const int8_t* erasures28, const uint8_t* n_total,
+                           int n, int32_t* status, uint8_t* used_dynamic, int n_fixed, int max_add, int ess_rule, hipStream_t st);
 hipError_t ddn_dev_rs63_soft(uint8_t* data6, const uint8_t* parity6, const uint8_t* data_rel, const uint8_t* parity_rel,
                              int n_par, int n_data, int t, int threshold, int n, uint8_t* status, hipStream_t st);
 hipError_t ddn_dev_rs63(uint8_t* data6, const uint8_t* parity6, int n_par, int n_data, int t, int n, uint8_t* status,

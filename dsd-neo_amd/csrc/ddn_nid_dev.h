@@ -7,31 +7,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ddn_gf64_dev.h"
+
 namespace ddn_nid {
 
-struct Gf {
-    const uint8_t* ex; // [128]
-    const uint8_t* lg; // [64]
-    __device__ __forceinline__ int mul(int a, int b) const { return (a && b) ? ex[lg[a] + lg[b]] : 0; }
-    __device__ __forceinline__ int div(int a, int b) const { return a ? ex[lg[a] + 63 - lg[b]] : 0; }
-};
-
-__device__ inline void
-gf_fill(uint8_t* ex, uint8_t* lg) { // one thread
-    int x = 1;
-    for (int i = 0; i < 63; i++) {
-        ex[i] = (uint8_t)x;
-        ex[i + 63] = (uint8_t)x;
-        lg[x] = (uint8_t)i;
-        x <<= 1;
-        if (x & 64) {
-            x ^= 0x43; // x^6 = x + 1
-        }
-    }
-    ex[126] = ex[0];
-    ex[127] = ex[1];
-    lg[0] = 0;
-}
+using ddn_gf64::Gf;
+using ddn_gf64::gf_fill;
+using ddn_gf64::gf_fill_wg;
 
 // Per-lane working arrays live in LDS, element k of this lane at base[k * 64] (no scratch memory, no bank
 // conflicts beyond byte-in-word sharing).  Exponent arithmetic mod 63 uses running sums with a conditional

@@ -904,7 +904,7 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                 H.fready[w] = 0;
                 H.staged[w] = 1;
             }
-            ddn_nid::gf_fill(H.sc.ex, H.sc.lg);
+            ddn_gf64::gf_fill(H.sc.ex, H.sc.lg);
             ddn_nid::chase_masks_fill(H.sc.masks);
         }
     }

@@ -1,7 +1,8 @@
 """GPU: the size limits and small-batch edges of the FEC decoders' dense public forms against the oracle, bit-exact: the NXDN
 convolution's n_steps limit (decided on the host against the LDS a workgroup may have - the test reads the same figure from the device
 properties and never tries a launch the entry has not checked), its n_bits / out_stride / batch edges, the K = 5 libM17 decoder's
-puncture and length edges and refusals, the trellis and block-code kernels at their workgroup edges, and n = 0 everywhere."""
+puncture and length edges and refusals, the trellis and block-code kernels at their workgroup edges, the Reed-Solomon / Golay / soft Hamming
+kernels and the Phase 2 burst stages at theirs, and n = 0 everywhere."""
 import ctypes as C
 
 import numpy as np
@@ -12,6 +13,7 @@ import ddn
 import fec3
 import fec_edge as fe
 import fecgen
+import rs28
 
 pytestmark = pytest.mark.gpu
 
@@ -209,6 +211,206 @@ def test_block_codes_at_their_group_edges(built):
         assert np.array_equal(syn, wsyn[:n]), n
 
 
+RS_ID = {"24_12_13": 0, "24_16_9": 1, "36_20_17": 2}
+
+
+def _classes(rc_ok, changed):
+    """how many clean, corrected and failed words a batch holds"""
+    return int((rc_ok & ~changed).sum()), int((rc_ok & changed).sum()), int((~rc_ok).sum())
+
+
+def test_rs_and_golay_hosts_at_their_group_edges(built):
+    """the 64-thread kernels (k_rs63, k_rs63_soft, k_rs28_decode, k_golay24) at n 1 / 63 / 64 / 65, clean, correctable and
+    uncorrectable words in every batch of 63 and more; word 0 of the soft RS batch is one that only an erasure retry decodes -
+    the existing tests start at n = 1500"""
+    from test_oracle_rs import gen_rs_soft, oracle_golay, oracle_rs, oracle_rs_soft_rel
+    from test_rs28_gpu import _batch
+    l = ddn.lib()
+    N = 65
+    for code, cid in RS_ID.items():
+        rng = np.random.default_rng(fe.FZ + 100 + cid)
+        d, p = fecgen.gen_p25_rs(rng, code, N, max_extra=4)
+        d[1::9] = rng.integers(0, 2, d[1::9].shape)
+        p[1::9] = rng.integers(0, 2, p[1::9].shape)
+        d[2], p[2] = 0, 0
+        wd, wrc = oracle_rs(code, d, p)
+        assert min(_classes(wrc[:63] == 0, (wd[:63] != d[:63]).any(axis=(1, 2)))) > 0
+        for n in (1, 63, 64, N):
+            got, st = d[:n].copy(), fe.sentinel((n,))
+            assert l.ddn_fec_p25_rs_host(cid, got.ctypes.data, p.ctypes.data, n, st.ctypes.data) == 0
+            assert np.array_equal(st, wrc[:n]) and np.array_equal(got, wd[:n]), (code, n)
+        d, p, drel, prel = gen_rs_soft(rng, code, 400)
+        hard_rc = oracle_rs(code, d, p)[1]
+        wd, wrc = oracle_rs_soft_rel(code, d, p, drel, prel)
+        first = int(np.flatnonzero((hard_rc != 0) & (wrc == 0))[0])      # hard decode fails, a ranked-erasure retry decodes
+        order = [first] + [i for i in range(N) if i != first]
+        d, p, drel, prel, wd, wrc, hard_rc = (np.ascontiguousarray(a[order]) for a in (d, p, drel, prel, wd, wrc, hard_rc))
+        assert hard_rc[0] != 0 and wrc[0] == 0
+        assert min(_classes(wrc[:63] == 0, (wd[:63] != d[:63]).any(axis=(1, 2)))) > 0
+        for n in (1, 63, 64, N):
+            got, st = d[:n].copy(), fe.sentinel((n,))
+            assert l.ddn_fec_p25_rs_soft_host(cid, got.ctypes.data, p.ctypes.data, drel.ctypes.data, prel.ctypes.data, n,
+                                              st.ctypes.data) == 0
+            assert np.array_equal(st, wrc[:n]) and np.array_equal(got, wd[:n]), (code, n)
+    for kind in (0, 1, 2):
+        pl, pa, er, ne, _ = _batch(np.random.default_rng(fe.FZ + 110 + kind), kind, N)
+        want = [rs28.oracle_rs28(kind, pl[i].astype(np.int32), pa[i].astype(np.int32), er[i, :ne[i]].astype(np.int32)) for i in range(N)]
+        wpl, wrc = np.stack([w[0] for w in want]).astype(np.uint8), np.array([w[1] for w in want], np.int32)
+        assert min(_classes(wrc[:63] >= 0, (wpl[:63] != pl[:63]).any(axis=1))) > 0
+        for n in (1, 63, 64, N):
+            got, st = pl[:n].copy(), fe.sentinel((n,), np.int32)
+            assert l.ddn_fec_rs28_host(kind, got.ctypes.data, pa.ctypes.data, er.ctypes.data, ne.ctypes.data, n, st.ctypes.data) == 0
+            assert np.array_equal(st, wrc[:n]) and np.array_equal(got, wpl[:n]), (kind, n)
+    for length in (6, 12):
+        rng = np.random.default_rng(fe.FZ + 120 + length)
+        d, p = fecgen.gen_golay24(rng, N, length)
+        d[1::9], p[1::9] = rng.integers(0, 2, d[1::9].shape), rng.integers(0, 2, p[1::9].shape)
+        d[2], p[2] = 0, 0
+        d[3, 1] = 2                                                        # an invalid bit value: rc 1, untouched
+        wd, wrc, wfx = oracle_golay(d, p)
+        assert min(_classes(wrc[:63] == 0, wfx[:63] > 0)) > 0
+        for n in (1, 63, 64, N):
+            got, st, fx = d[:n].copy(), fe.sentinel((n,)), fe.sentinel((n,), np.int32)
+            assert l.ddn_fec_golay24_host(length, got.ctypes.data, p.ctypes.data, n, st.ctypes.data, fx.ctypes.data) == 0
+            assert np.array_equal(st, wrc[:n]) and np.array_equal(fx, wfx[:n]) and np.array_equal(got, wd[:n]), (length, n)
+
+
+def test_soft_golay_and_hamming_hosts_at_their_group_edges(built):
+    """k_golay24_soft and k_hamming_10_6_3_soft (256 threads) at n 1 / 255 / 256 / 257: 0 .. 6 flipped bits per word, so clean,
+    corrected and rejected words in every batch"""
+    from test_oracle_rs import gen_soft_reliab, oracle_golay_soft, oracle_hamming_soft
+    l = ddn.lib()
+    N = 257
+    for length in (6, 12):
+        rng = np.random.default_rng(fe.FZ + 130 + length)
+        d, p, flips = np.zeros((N, length), np.uint8), np.zeros((N, 12), np.uint8), np.zeros((N, length + 12), bool)
+        for i in range(N):
+            d12 = np.zeros(12, np.uint8)
+            d12[12 - length:] = rng.integers(0, 2, length)
+            w = np.concatenate([d12[12 - length:], fecgen.golay24_encode(d12)])
+            pos = rng.choice(length + 12, i % 7, replace=False)
+            w[pos] ^= 1
+            flips[i, pos] = True
+            d[i], p[i] = w[:length], w[length:]
+        rel = gen_soft_reliab(rng, flips.shape, flips)
+        d[20, 0] = 3
+        want, wrc, wfx = oracle_golay_soft(d, p, rel)
+        assert min(_classes(wrc[:255] == 0, wfx[:255] > 0)) > 0
+        for n in (1, 255, 256, N):
+            got, st, fx = d[:n].copy(), fe.sentinel((n,)), fe.sentinel((n,), np.int32)
+            assert l.ddn_fec_golay24_soft_host(length, got.ctypes.data, p.ctypes.data, rel.ctypes.data, n, st.ctypes.data, fx.ctypes.data) == 0
+            assert np.array_equal(st, wrc[:n]) and np.array_equal(fx, wfx[:n]) and np.array_equal(got, want[:n]), (length, n)
+    rng = np.random.default_rng(fe.FZ + 140)
+    d = rng.integers(0, 2, (N, 6)).astype(np.uint8)
+    p = np.stack([d[:, 0] ^ d[:, 1] ^ d[:, 2] ^ d[:, 5], d[:, 0] ^ d[:, 1] ^ d[:, 3] ^ d[:, 5],
+                  d[:, 0] ^ d[:, 2] ^ d[:, 3] ^ d[:, 4], d[:, 1] ^ d[:, 2] ^ d[:, 3] ^ d[:, 4]], axis=1)
+    bits = np.ascontiguousarray(np.concatenate([d, p], axis=1).astype(np.uint8))
+    flips = rng.random(bits.shape) < np.array([0.0, 0.08, 0.3])[np.arange(N) % 3][:, None]
+    bits ^= flips.astype(np.uint8)
+    rel = gen_soft_reliab(rng, bits.shape, flips)
+    bits[10, 3] = 2
+    want, wrc = oracle_hamming_soft(bits, rel)
+    assert set(wrc[:255].tolist()) == {0, 1, 2}                            # valid, corrected, uncorrectable
+    for n in (1, 255, 256, N):
+        out, st = fe.sentinel((n, 10)), fe.sentinel((n,))
+        assert l.ddn_fec_hamming_10_6_3_soft_host(bits.ctypes.data, rel.ctypes.data, n, out.ctypes.data, st.ctypes.data) == 0
+        assert np.array_equal(st, wrc[:n]) and np.array_equal(out, want[:n]), n
+
+
+def _hex_reliab(llr):
+    """reliability of each 6-bit symbol: the least min(|LLR|, 255) of its bits"""
+    return np.minimum(np.abs(np.asarray(llr, np.int32)), 255).reshape(-1, 6).min(axis=1)
+
+
+def _front(items, went_to_retries, n_keep=65):
+    """the batch with a section that only a retry decodes in front, then one that fails every retry and one whose ranked list ends
+    before max_add; items: (inputs, oracle answer, used_dynamic, failed, list shorter than max_add)"""
+    a = next(k for k, it in enumerate(items) if it[2] == 1)
+    b = next(k for k, it in enumerate(items) if it[3])
+    c = next(k for k, it in enumerate(items) if k not in (a, b) and went_to_retries(it) and it[4])
+    out = [items[a], items[b], items[c]] + [it for k, it in enumerate(items) if k not in (a, b, c)]
+    return out[:n_keep]
+
+
+@pytest.mark.parametrize("kind", [0, 1])
+def test_xcch_stage_where_the_probe_grid_is_ragged(built, kind):
+    """ddn_p25p2_xcch at n 1 / 63 / 65: n * max_add (10 FACCH, 16 SACCH) is no multiple of the probe pass's 64 threads.  Burst 0 fails
+    its plain decode and decodes on a retry; every batch of 63 and more also holds a burst that fails every retry and one that goes
+    to the retries with a ranked list shorter than max_add (the probe threads past its end)."""
+    from test_oracle_p25p2_xcch import N_PL, oracle_xcch
+    rng = np.random.default_rng(fe.FZ + 150 + kind)
+    min_add, max_add = ((5, 10), (8, 16))[kind]
+    items = []
+    for i in range(300):
+        n_err = int(rng.integers(0, 15))
+        b, llr, _ = rs28.make_xcch_burst(rng, kind, n_err, int(rng.integers(0, n_err + 1)), int(rng.integers(0, 8)))
+        ec, pl, used = oracle_xcch(kind, b, llr)
+        rel = np.concatenate([_hex_reliab(llr[rs28.XCCH_PAYLOAD_POS[kind]]), _hex_reliab(llr[rs28.XCCH_PARITY_POS[kind]])])
+        add = min(max(int((rel < 64).sum()), min_add), max_add)
+        items.append(((b, llr), (ec, pl), used, ec < 0, add < max_add))
+    items = _front(items, lambda it: it[2] == 1 or it[3])
+    assert items[0][2] == 1 and items[0][1][0] >= 0
+    assert any(it[3] for it in items[:63]) and any((it[2] == 1 or it[3]) and it[4] for it in items[:63])
+    bits, llr = np.stack([it[0][0] for it in items]).astype(np.uint8), np.stack([it[0][1] for it in items]).astype(np.int16)
+    for n in (1, 63, 65):
+        pl, ec, used = fe.sentinel((n, N_PL[kind])), fe.sentinel((n,), np.int32), fe.sentinel((n,))
+        assert ddn.lib().ddn_p25p2_xcch_host(kind, bits.ctypes.data, llr.ctypes.data, n, 64, pl.ctypes.data, ec.ctypes.data, used.ctypes.data) == 0
+        for i in range(n):
+            (wec, wpl), wused = items[i][1], items[i][2]
+            assert ec[i] == wec and used[i] == wused and np.array_equal(pl[i], wpl), (kind, n, i, ec[i], wec, used[i], wused)
+
+
+def test_ess_stage_where_the_probe_grid_is_ragged(built):
+    """ddn_p25p2_ess at n 1 / 63 / 65 (28 attempts per section), the same three kinds of section in front as for the bursts"""
+    from test_oracle_p25p2_xcch import oracle_ess
+    rng = np.random.default_rng(fe.FZ + 160)
+    items = []
+    for i in range(300):
+        n_err = int(rng.integers(0, 26))
+        a, b, c, d, _ = rs28.make_ess_case(rng, n_err, int(rng.integers(0, n_err + 1)), int(rng.integers(0, 8)))
+        acc, wec, wout = oracle_ess(a, b, c, d)
+        plain = rs28.oracle_rs28(0, a.astype(np.int32), c.astype(np.int32), np.zeros(0, np.int32))[1]
+        retried = not 0 <= plain < 15                                      # the plain decode failed or located 15 symbols or more
+        cnt = min(max(int((np.concatenate([_hex_reliab(b), _hex_reliab(d)]) < 64).sum()), 14), 28)
+        items.append(((a, b, c, d), (acc, wec, wout), int(bool(acc) and retried), not acc, cnt < 28))
+    items = _front(items, lambda it: it[2] == 1 or it[3])
+    assert items[0][2] == 1
+    assert any(it[3] for it in items[:63]) and any((it[2] == 1 or it[3]) and it[4] for it in items[:63])
+    pl, pll, pa, pal = (np.ascontiguousarray(np.stack([it[0][k] for it in items])) for k in range(4))
+    for n in (1, 63, 65):
+        out, ec, used = fe.sentinel((n, 96)), fe.sentinel((n,), np.int32), fe.sentinel((n,))
+        assert ddn.lib().ddn_p25p2_ess_host(pl.ctypes.data, pll.ctypes.data, pa.ctypes.data, pal.ctypes.data, n, 64, out.ctypes.data,
+                                            ec.ctypes.data, used.ctypes.data) == 0
+        for i in range(n):
+            acc, wec, wout = items[i][1]
+            assert (ec[i] >= 0) == bool(acc) and ec[i] == wec and np.array_equal(out[i], wout), (n, i, ec[i], acc, wec)
+            assert used[i] == items[i][2], (n, i)
+
+
+@pytest.mark.parametrize("code", list(RS_ID))
+def test_rs_failed_word_with_a_non_binary_byte(built, code):
+    """an uncorrectable word with a data byte of 5: the hard entry rewrites the data bits from the uncorrected symbols (the 5 reads
+    back as 1), the soft-reliability entry leaves the data as it came - both as the oracle does"""
+    from test_oracle_rs import oracle_rs, oracle_rs_soft_rel
+    rng = np.random.default_rng(fe.FZ + 170 + RS_ID[code])
+    d, p = fecgen.gen_p25_rs(rng, code, 40)
+    d[:], p[:] = rng.integers(0, 2, d.shape), rng.integers(0, 2, p.shape)
+    d[:, 1, 2] = 5
+    drel, prel = np.full(d.shape[:2], 200, np.uint8), np.full(p.shape[:2], 200, np.uint8)
+    k = int(np.flatnonzero((oracle_rs(code, d, p)[1] == 1) & (oracle_rs_soft_rel(code, d, p, drel, prel)[1] == 1))[0])
+    d, p, drel, prel = (np.ascontiguousarray(a[k:k + 1]) for a in (d, p, drel, prel))      # a random word that both decoders give up on
+    wd, wrc = oracle_rs(code, d, p)
+    ws, wsrc = oracle_rs_soft_rel(code, d, p, drel, prel)
+    assert wrc[0] == 1 and wsrc[0] == 1 and wd[0, 1, 2] == 1 and ws[0, 1, 2] == 5
+    got, st = d.copy(), fe.sentinel((1,))
+    assert ddn.lib().ddn_fec_p25_rs_host(RS_ID[code], got.ctypes.data, p.ctypes.data, 1, st.ctypes.data) == 0
+    assert st[0] == 1 and np.array_equal(got, wd)
+    got, st = d.copy(), fe.sentinel((1,))
+    assert ddn.lib().ddn_fec_p25_rs_soft_host(RS_ID[code], got.ctypes.data, p.ctypes.data, drel.ctypes.data, prel.ctypes.data, 1,
+                                              st.ctypes.data) == 0
+    assert st[0] == 1 and np.array_equal(got, ws)
+
+
 def test_n_zero_is_ok_and_writes_nothing(built):
     l = ddn.lib()
     a = fe.sentinel((4096,))          # one buffer stands for every argument: with n = 0 nothing may be read or written
@@ -227,6 +429,12 @@ def test_n_zero_is_ok_and_writes_nothing(built):
         lambda: l.ddn_fec_bptc_128x77_host(p, 0, p, p),
         lambda: l.ddn_fec_bptc_16x2_host(p, 0, 1, p, p),
         lambda: l.ddn_fec_rs_12_9_host(p, 0, p, p, p),
+        lambda: l.ddn_fec_p25_rs_host(2, p, p, 0, p),
+        lambda: l.ddn_fec_p25_rs_soft_host(2, p, p, p, p, 0, p),
+        lambda: l.ddn_fec_rs28_host(0, p, p, p, p, 0, p),
+        lambda: l.ddn_fec_golay24_host(12, p, p, 0, p, p),
+        lambda: l.ddn_fec_golay24_soft_host(12, p, p, p, 0, p, p),
+        lambda: l.ddn_fec_hamming_10_6_3_soft_host(p, p, 0, p, p),
     ]
     for k, call in enumerate(calls):
         assert call() == ddn.DDN_OK, (k, l.ddn_last_error())

@@ -247,6 +247,28 @@ def main():
             rs28.oracle_rs28(1, c[0], c[1], c[2])
     report("p25p2_rs28_facch", nrs, ms, 45 * 6 + 28 + 4, cpu(cpu_rs28, 512), "sections")
 
+    # P25 Phase 1 RS(36,20,17): hard decision (0 .. t + 3 symbol errors) and the soft-reliability ladder (hard attempt, then ranked erasures)
+    from test_oracle_rs import gen_rs_soft, oracle_rs, oracle_rs_soft_rel
+    n36, rng36 = 65536, np.random.default_rng(36)       # (a generator of its own: the rows below keep their inputs)
+    h_d, h_p = fecgen.gen_p25_rs(rng36, "36_20_17", 512)
+    s_d, s_p, s_dr, s_pr = gen_rs_soft(rng36, "36_20_17", 512)
+    up = lambda a: torch.from_numpy(np.tile(a, (n36 // 512, 1, 1) if a.ndim == 3 else (n36 // 512, 1))).cuda()
+    d_hd0, d_hp, d_sd0, d_sp, d_sdr, d_spr = up(h_d), up(h_p), up(s_d), up(s_p), up(s_dr), up(s_pr)
+    d_hd, d_sd, d_rc = d_hd0.clone(), d_sd0.clone(), torch.zeros(n36, dtype=torch.uint8, device="cuda")
+
+    def run_rs36():
+        d_hd.copy_(d_hd0)
+        l.ddn_fec_p25_rs_batch(2, d_hd.data_ptr(), d_hp.data_ptr(), n36, d_rc.data_ptr(), st)
+    ms = timeit(run_rs36)
+    report("p25p1_rs_36_20_17", n36, ms, 36 * 6 + 20 * 6 + 1, cpu(lambda: oracle_rs("36_20_17", h_d, h_p), 512), "codewords")
+
+    def run_rs36_soft():
+        d_sd.copy_(d_sd0)
+        l.ddn_fec_p25_rs_soft_batch(2, d_sd.data_ptr(), d_sp.data_ptr(), d_sdr.data_ptr(), d_spr.data_ptr(), n36, d_rc.data_ptr(), st)
+    ms = timeit(run_rs36_soft)
+    report("p25p1_rs_36_20_17_soft", n36, ms, 36 * 7 + 20 * 6 + 1, cpu(lambda: oracle_rs_soft_rel("36_20_17", s_d, s_p, s_dr, s_pr), 512),
+           "codewords")
+
     # short-integer voice path (processAudio -> hpf_dL) and the I-ISCH lookup
     from test_oracle_audio import oracle_s16, s16_state, voice_like
     S, F = 4096, 50
