@@ -578,6 +578,34 @@ class M17DataChainResults(C.Structure):  # == ddn_m17_data_chain_results
                                   "d_packet_app_len", "d_packet_crc_ok", "d_packet_slot")]
 
 
+class DmrPduInput(C.Structure):  # == ddn_dmr_pdu_input
+    _fields_ = [("n_channels", C.c_int), ("max_bursts", C.c_int), ("max_marks", C.c_int)] + [
+        (k, C.c_void_p) for k in ("d_n_bursts", "d_slot", "d_type", "d_bytes12", "d_info196", "d_errs", "d_crc", "d_unconfirmed18", "d_pool",
+                                  "d_pool_n", "d_n_resets", "d_reset_before", "d_n_losses", "d_loss_before")]
+
+
+class DmrPduOutput(C.Structure):  # == ddn_dmr_pdu_output
+    _fields_ = [("max_pdus", C.c_int)] + [
+        (k, C.c_void_p) for k in ("d_burst_conf", "d_burst_counter", "d_burst_crc", "d_burst_dbsn", "d_burst_pick", "d_burst_status", "d_n_pdus",
+                                  "d_pdu_kind", "d_pdu_slot", "d_pdu_burst", "d_pdu_len", "d_pdu_bytes", "d_pdu_crc4", "d_pdu_block_crc",
+                                  "d_pdu_header9")]
+
+
+class DmrPduChainResults(C.Structure):  # == ddn_dmr_pdu_chain_results
+    _fields_ = [("dmr_data_bursts", C.c_int), ("max_marks", C.c_int), ("d_n_resets", C.c_void_p), ("d_reset_before", C.c_void_p),
+                ("d_n_losses", C.c_void_p), ("d_loss_before", C.c_void_p), ("out", DmrPduOutput)]
+
+
+PROTOTYPES.update({
+    "ddn_dmr_pdu_state_bytes": (C.c_size_t, []),
+    "ddn_dmr_pdu_walk_batch": (C.c_int, [C.c_void_p] * 4),
+    "ddn_dmr_pdu_marks_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int] + [C.c_void_p] * 3
+                                + [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]),
+    "ddn_fsk4_chain_set_dmr_pdu_slots": (C.c_int, [C.c_void_p, C.c_int]),
+    "ddn_fsk4_chain_get_dmr_pdu_results": (C.c_int, [C.c_void_p, C.c_void_p]),
+})
+
+
 def dpmr_air_interface_id(v):
     """ddn_dpmr_air_interface_id: the seven characters the reference prints for a raw 24-bit dPMR ID"""
     out = C.create_string_buffer(8)
@@ -718,6 +746,16 @@ class Fsk4ChainC:
     def set_m17_packet_slots(self, max_packets):
         """ddn_fsk4_chain_set_m17_packet_slots: completed packets stored per channel and call (1 .. 33, default 4), before the first run"""
         _check(lib().ddn_fsk4_chain_set_m17_packet_slots(self.h, max_packets), "ddn_fsk4_chain_set_m17_packet_slots")
+
+    def dmr_pdu_results(self):
+        """ddn_fsk4_chain_get_dmr_pdu_results (DMR chains after set_dmr_pdu_slots): the data PDUs of the last call"""
+        r = DmrPduChainResults()
+        _check(lib().ddn_fsk4_chain_get_dmr_pdu_results(self.h, C.byref(r)), "ddn_fsk4_chain_get_dmr_pdu_results")
+        return r
+
+    def set_dmr_pdu_slots(self, max_pdus):
+        """ddn_fsk4_chain_set_dmr_pdu_slots: assemble data PDUs on the device, 1 .. 8 stored per channel and call; before the first run"""
+        _check(lib().ddn_fsk4_chain_set_dmr_pdu_slots(self.h, max_pdus), "ddn_fsk4_chain_set_dmr_pdu_slots")
 
     @property
     def rx(self):

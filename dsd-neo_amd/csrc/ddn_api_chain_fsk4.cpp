@@ -266,6 +266,37 @@ dmr_alloc(ddn_fsk4_chain* c) {
     return voice_tail_alloc(c, V * 3, 2 * c->B);
 }
 
+// data PDUs (ddn_fsk4_chain_set_dmr_pdu_slots): where the events and the call's new flags put dmr_reset_blocks() and carrier loss
+// among the bursts, then the walk over the data-burst stage's arrays; the state block starts all zeros (= a stream's start)
+static void
+dmr_pdu_output(const ddn_fsk4_chain* c, ddn_dmr_pdu_output* o) {
+    const auto& p = c->dmr.pw;
+    *o = ddn_dmr_pdu_output{p.P,   p.b_conf, p.b_counter, p.b_crc, p.b_dbsn, p.b_pick, p.b_status, p.n_pdus,
+                            p.kind, p.slot,   p.burst,     p.len,   p.bytes,  p.crc4,   p.bcrc,     p.hdr};
+}
+
+static int
+dmr_pdu_walk(ddn_fsk4_chain* c, int cur, hipStream_t st) {
+    auto& p = c->dmr.pw;
+    const size_t B = (size_t)c->B, D = c->dmr.D;
+    if (!p.state) { // (the PDU slots: their number may change until the first run)
+        const size_t BP = B * (size_t)p.P, BM = B * (size_t)p.M;
+        DDN_TRY(alloc_rc(BUF(dmr.pw.state, B * ddn_dmr_pdu_state_bytes()) && BUF(dmr.pw.rb, BM) && BUF(dmr.pw.nr, B) && BUF(dmr.pw.lb, BM)
+                           && BUF(dmr.pw.nl, B) && BUF(dmr.pw.b_conf, D) && BUF(dmr.pw.b_counter, D) && BUF(dmr.pw.b_crc, D)
+                           && BUF(dmr.pw.b_dbsn, D) && BUF(dmr.pw.b_pick, D) && BUF(dmr.pw.b_status, D) && BUF(dmr.pw.n_pdus, B)
+                           && BUF(dmr.pw.kind, BP) && BUF(dmr.pw.slot, BP) && BUF(dmr.pw.burst, BP) && BUF(dmr.pw.len, BP)
+                           && BUF(dmr.pw.bytes, BP * 3072) && BUF(dmr.pw.crc4, BP * 4) && BUF(dmr.pw.bcrc, BP * 128) && BUF(dmr.pw.hdr, BP * 9)));
+    }
+    DDN_TRY(ddn_dmr_pdu_marks_batch(c->dmr.ev, c->dmr.nev, (size_t)c->dmr.E, c->d_fl[cur], c->stride, c->T, c->d_new[cur], c->dmr.data.start,
+                                    c->dmr.data.n, c->B, c->dmr.db, p.state, p.rb, p.nr, p.lb, p.nl, p.M, st));
+    ddn_dmr_pdu_input in{c->B,           c->dmr.db,        p.M,           c->dmr.data.n, c->dmr.data.slot, c->dmr.data.type, c->dmr.data.bytes,
+                         c->dmr.data.info, c->dmr.data.errs, c->dmr.data.crc, c->dmr.data.unconf, c->dmr.data.pool, c->dmr.data.pooln,
+                         p.nr,           p.rb,             p.nl,          p.lb};
+    ddn_dmr_pdu_output out;
+    dmr_pdu_output(c, &out);
+    return ddn_dmr_pdu_walk_batch(&in, p.state, &out, st);
+}
+
 static int
 dmr_decode(ddn_fsk4_chain* c, int cur, int flush, hipStream_t st) {
     const size_t S = c->S;
@@ -303,6 +334,9 @@ dmr_decode(ddn_fsk4_chain* c, int cur, int flush, hipStream_t st) {
                                         c->dmr.emb.n, st));
         DDN_TRY(ddn_fec_bptc_128x77_batch(c->dmr.emb.in, L, c->dmr.emb.out, c->dmr.emb.errs, st));
         HIP_TRY(ddn_dev_dmr_emb_finish(c->dmr.emb.out, c->dmr.emb.pos, (int)L, c->dmr.emb.ok, st));
+        if (c->dmr.pw.P) {
+            DDN_TRY(dmr_pdu_walk(c, cur, st));
+        }
     }
     if (!c->mbe) {
         HIP_TRY(hipEventRecord(c->ev_reads, st));
@@ -798,6 +832,34 @@ ddn_fsk4_chain_get_m17_data_results(ddn_fsk4_chain* c, ddn_m17_data_chain_result
     r->d_packet_app_len = c->m17.packet_len;
     r->d_packet_crc_ok = c->m17.packet_ok;
     r->d_packet_slot = c->m17.packet_slot;
+    return DDN_OK;
+}
+
+extern "C" int
+ddn_fsk4_chain_set_dmr_pdu_slots(ddn_fsk4_chain* c, int max_pdus) {
+    if (!c || c->cfg.protocol != DDN_FSK4_DMR || !c->cfg.handlers || c->step != 0 || max_pdus < 1 || max_pdus > 8) {
+        ddn_set_error("ddn_fsk4_chain_set_dmr_pdu_slots: a DMR chain with handlers = 1 before its first run, 1 .. 8 PDU slots");
+        return DDN_EINVAL;
+    }
+    c->dmr.pw.P = max_pdus;
+    c->dmr.pw.M = c->dmr.E; // (a mark needs an event or 1800 symbols)
+    return DDN_OK;
+}
+
+extern "C" int
+ddn_fsk4_chain_get_dmr_pdu_results(ddn_fsk4_chain* c, ddn_dmr_pdu_chain_results* r) {
+    if (!c || !r || c->cfg.protocol != DDN_FSK4_DMR || !c->dmr.pw.P) {
+        ddn_set_error("ddn_fsk4_chain_get_dmr_pdu_results: a DMR chain with ddn_fsk4_chain_set_dmr_pdu_slots called");
+        return DDN_EINVAL;
+    }
+    memset(r, 0, sizeof(*r));
+    r->dmr_data_bursts = c->dmr.db;
+    r->max_marks = c->dmr.pw.M;
+    r->d_n_resets = c->dmr.pw.nr;
+    r->d_reset_before = c->dmr.pw.rb;
+    r->d_n_losses = c->dmr.pw.nl;
+    r->d_loss_before = c->dmr.pw.lb;
+    dmr_pdu_output(c, &r->out);
     return DDN_OK;
 }
 

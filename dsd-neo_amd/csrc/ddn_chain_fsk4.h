@@ -64,6 +64,14 @@ struct ddn_fsk4_chain {
             uint32_t* errs;
             uint8_t *sig, *in, *out, *ok;
         } emb;
+        // data PDUs (ddn_dmr_pdu.hip), off until ddn_fsk4_chain_set_dmr_pdu_slots: P = 0, nothing allocated, nothing launched.  The
+        // state carried per channel, the marks of a call (M per channel), the walk's outputs per burst and - P slots per channel, made
+        // at the first run - per completed PDU
+        struct {
+            int P, M;
+            uint8_t *state, *b_conf, *b_crc, *b_dbsn, *b_status, *kind, *slot, *bytes, *crc4, *bcrc;
+            int32_t *b_counter, *b_pick, *n_pdus, *burst, *len, *hdr, *rb, *nr, *lb, *nl;
+        } pw;
     } dmr;
     struct { // NXDN48 / NXDN96; vf: voice frames per channel and call
         int vf;

@@ -360,6 +360,20 @@ hipError_t ddn_dev_dmr_emb_collect(const int32_t* events, const int32_t* n_event
                                    size_t max_sym, int n_channels, int max_lc, uint8_t* sig, uint8_t* in128, int32_t* lc_pos,
                                    int32_t* lc_n, hipStream_t st);
 hipError_t ddn_dev_dmr_emb_finish(const uint8_t* out77, const int32_t* lc_pos, int n, uint8_t* ok, hipStream_t st);
+// the DMR protocol layer behind the data bursts: resets / carrier loss between them, the walk to completed PDUs (ddn_dmr_pdu.hip)
+size_t ddn_dev_dmr_pdu_state_bytes(void);
+hipError_t ddn_dev_dmr_pdu_marks(const int32_t* events, const int32_t* n_events, int max_events, const uint8_t* flags, size_t stride,
+                                 int carry, const int32_t* n_new, const int32_t* dstart, const int32_t* dn, int n_channels, int max_bursts,
+                                 void* state, int32_t* reset_before, int32_t* n_resets, int32_t* loss_before, int32_t* n_losses,
+                                 int max_marks, hipStream_t st);
+hipError_t ddn_dev_dmr_pdu_walk(const int32_t* n_bursts, int n_channels, int max_bursts, const uint8_t* bslot, const uint8_t* btype,
+                                const uint8_t* bytes12, const uint8_t* info196, const uint32_t* errs, const uint8_t* crcflags,
+                                const uint8_t* unconf18, const void* pool, const int32_t* pool_n, const int32_t* n_resets,
+                                const int32_t* reset_before, const int32_t* n_losses, const int32_t* loss_before, int max_marks, void* state,
+                                uint8_t* o_conf, int32_t* o_counter, uint8_t* o_crc, uint8_t* o_dbsn, int32_t* o_pick, uint8_t* o_status,
+                                uint8_t* pdu_kind, uint8_t* pdu_slot, int32_t* pdu_burst, int32_t* pdu_len, uint8_t* pdu_bytes,
+                                uint8_t* pdu_crc4, uint8_t* pdu_block_crc, int32_t* pdu_header9, int max_pdus, int32_t* n_pdus,
+                                hipStream_t st);
 hipError_t ddn_dev_k5_nxdn(const uint8_t* sym, const uint8_t* rel, int n, int n_steps, int n_bits, uint16_t* metrics_io,
                            uint8_t* out, int out_stride, hipStream_t st);
 hipError_t ddn_dev_k5_m17(const uint16_t* in, int n, int in_len, int u_len, const DdnPuncture* pu, uint8_t* out,

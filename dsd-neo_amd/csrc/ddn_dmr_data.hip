@@ -18,7 +18,8 @@
 //                        voice burst with VC 6 the 8 x 16 matrix dmr_dburst_handle_emb() (:363-394) builds from bursts B..E
 //   k_dmr_emb_finish     the 5-bit checksum of the 77 bits BPTC(128,77) returns (ComputeCrc5Bit(), dmr_utils.c:365-392)
 // Not here: everything that needs the protocol layer's running state (state->data_conf_data, the DBSN sequence, the block
-// assembler: src/protocol/dmr/dmr_block.c) - where the reference's choice depends on it, both answers are given.
+// assembler: src/protocol/dmr/dmr_block.c) - where the reference's choice depends on it, both answers are given.  ddn_dmr_pdu.hip
+// keeps that state per channel and makes the choice, burst by burst, up to the completed PDU.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

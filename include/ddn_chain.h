@@ -22,6 +22,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "ddn_fsk4.h" /* ddn_dmr_pdu_output */
 #include "ddn_hip.h" /* DDN_OK ..., DDN_IN_*, ddn_last_error() */
 #ifdef __cplusplus
 extern "C" {
@@ -355,7 +356,8 @@ typedef struct ddn_fsk4_chain_results { /* device pointers, S = n_channels * max
      *           applied (cheapest candidate with a good CRC9, else the cheapest; confirmed_crc = a good CRC9 was found); pool = every
      *           candidate in the reference's order {metric, 18 bytes} with {CRC9 ok, DBSN} in the entry's two pad bytes, for the
      *           caller that tracks state->data_dbsn_expected.
-     * The protocol layer's running state (confirmed / unconfirmed, DBSN sequence, block assembly: dmr_block.c) is the caller's. */
+     * The protocol layer's running state (confirmed / unconfirmed, DBSN sequence, block assembly: dmr_block.c) is applied on the
+     * device once ddn_fsk4_chain_set_dmr_pdu_slots has enabled it (ddn_dmr_pdu_chain_results below); until then it is the caller's. */
     int dmr_data_bursts;                 /* entries per channel and call */
     const int32_t* d_dmr_n_data;         /* [B] */
     const int32_t* d_dmr_data_start;     /* [B][dmr_data_bursts] row index of the burst's first CACH dibit (-1: unused) */
@@ -554,6 +556,26 @@ typedef struct ddn_m17_data_chain_results { /* device pointers valid until the n
 } ddn_m17_data_chain_results;
 int ddn_fsk4_chain_set_m17_packet_slots(ddn_fsk4_chain* c, int max_packets);
 int ddn_fsk4_chain_get_m17_data_results(ddn_fsk4_chain* c, ddn_m17_data_chain_results* out);
+
+/* ---- DMR data PDUs (protocol DDN_FSK4_DMR, handlers = 1), opt-in: ddn_fsk4_chain_set_dmr_pdu_slots(c, max_pdus) before the first run
+ * - 1 .. 8 completed PDUs stored per channel and call; any other value, handlers = 0, a chain that has run or another protocol is
+ * DDN_EINVAL.  Until it is called the chain launches nothing for it and ddn_fsk4_chain_get_dmr_pdu_results is DDN_EINVAL.  Enabled,
+ * every call runs ddn_dmr_pdu_marks_batch -> ddn_dmr_pdu_walk_batch (include/ddn_fsk4.h: scope, status bytes, PDU fields) behind the
+ * data-burst stage, over the arrays ddn_fsk4_chain_results names as d_dmr_data_* / d_dmr_r34_*: entry c * dmr_data_bursts + k here is
+ * the same burst as there.  Both time slots' header state, data_block_crc_valid, the two dmr_pdu_sf rows and the run of hunted symbols
+ * behind the last lock are carried per channel across calls and through flush, so a PDU whose header and last block lie in different
+ * calls completes once, in the call that holds its last burst.  ddn_fsk4_chain_config and ddn_fsk4_chain_results keep their sizes. */
+typedef struct ddn_dmr_pdu_chain_results { /* device pointers valid until the next run */
+    int dmr_data_bursts;    /* entries per channel and call (= ddn_fsk4_chain_results.dmr_data_bursts) */
+    int max_marks;          /* resets / carrier losses stored per channel and call */
+    const int32_t* d_n_resets;     /* [n_channels] dmr_reset_blocks() calls the loop's events name in this call */
+    const int32_t* d_reset_before; /* [n_channels][max_marks] the index of the burst each precedes */
+    const int32_t* d_n_losses;     /* [n_channels] carrier losses of this call */
+    const int32_t* d_loss_before;  /* [n_channels][max_marks] */
+    ddn_dmr_pdu_output out;        /* per burst and per completed PDU; out.max_pdus = P */
+} ddn_dmr_pdu_chain_results;
+int ddn_fsk4_chain_set_dmr_pdu_slots(ddn_fsk4_chain* c, int max_pdus);
+int ddn_fsk4_chain_get_dmr_pdu_results(ddn_fsk4_chain* c, ddn_dmr_pdu_chain_results* out);
 
 /* ---- a mixed batch (BASELINE configs[3]): P25 Phase 1 + DMR + NXDN48 channel groups of one GPU, every receive loop with the
  * reference's handlers inside it; one stream per group inside the object, the groups' stages lined up (the three front ends, then the

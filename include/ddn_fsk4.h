@@ -381,6 +381,83 @@ int ddn_edacs_frame_decode_batch(const uint8_t* d_records10, size_t stride_symbo
  * kind 1 = FACCH1 (80 bits + CRC12, nxdn_dcr_utils.c:21-42); kind + 2 = the same on rows of one bit per byte (what
  * ddn_fec_trellis_decode_batch writes); d_ok [n] = 1 when the field's CRC matches */
 int ddn_nxdn_crc_check_batch(const uint8_t* d_bytes, int stride, size_t n, int kind, uint8_t* d_ok, void* hip_stream);
+
+/* ---- DMR data PDUs: the protocol layer behind the dispatched data bursts (ddn_dmr_pdu.hip) ---------------------------------------
+ * ddn_dmr_pdu_walk_batch walks each channel's data bursts of a call in air order through what dmr_data_burst_handler()
+ * (src/protocol/dmr/dmr_dburst.c:812-845) does with them under dsd_state's running state: the profile under data_conf_data /
+ * data_header_format (:105-174), crc_correct and data_block_crc_valid, the rate 3/4 candidate pick against the expected DBSN
+ * (:428-468), the DBSN sequence (:651-680), dmr_dheader() (src/protocol/dmr/dmr_block.c:557-618), dmr_block_assembler() types 1 - 3
+ * (:1052-1710), the data terminator (dmr_flco.c:319-333); between the bursts dmr_reset_blocks() (dmr_block.c:1714-1748) and the
+ * carrier-loss reset (src/engine/engine.c:1957-2000,2041-2063) where the marks say so.  d_state (n_channels x
+ * ddn_dmr_pdu_state_bytes(), all zeros = a stream's start) carries both time slots' fields, data_block_crc_valid and the two 3072-byte
+ * dmr_pdu_sf rows from call to call: a PDU completes in the call that holds its last burst.
+ * Scope: the reference's default options only (aggressive_framesync = 1, dmr_crc_relaxed_default = 0: the RAS override never fires);
+ * branding (XPT, Cap+) is taken as unset - CSBK parsing, which sets it, stays on the host; a burst whose slot type did not decode
+ * (type > 11) is passed over; everything behind a completed PDU - decryption, LRRP / IP / text / UDT / CSBK message parsing, events -
+ * is the caller's.
+ * Input, D = n_channels * max_bursts entries, channel c's bursts at c * max_bursts + k for k < d_n_bursts[c] (the layout of
+ * ddn_fsk4_chain_results' d_dmr_data_* / d_dmr_r34_* arrays): time slot, data type, the 12 BPTC bytes, the 196 info bits, BPTC
+ * irrecoverable errors, the crc flags (bit 0: crc_correct while data_conf_data = 0, bit 1: the confirmed block's CRC9), the
+ * unconfirmed rate 3/4 payload, the rate 3/4 pool (ddn_r34_candidate [34] with {CRC9 ok, DBSN} in each entry's two pad bytes) and
+ * its length.  Marks, max_marks per channel, each list ascending: d_reset_before[c][j] / d_loss_before[c][j] = the index of the burst
+ * the j-th dmr_reset_blocks() / carrier loss of the call precedes (d_n_bursts[c]: behind the last burst). */
+typedef struct ddn_dmr_pdu_input {
+    int n_channels, max_bursts, max_marks;
+    const int32_t* d_n_bursts;       /* [n_channels] */
+    const uint8_t* d_slot;           /* [D] */
+    const uint8_t* d_type;           /* [D] */
+    const uint8_t* d_bytes12;        /* [D][12] */
+    const uint8_t* d_info196;        /* [D][196] */
+    const uint32_t* d_errs;          /* [D] */
+    const uint8_t* d_crc;            /* [D] */
+    const uint8_t* d_unconfirmed18;  /* [D][18] */
+    const void* d_pool;              /* [D][34] ddn_r34_candidate (include/ddn_hip.h) */
+    const int32_t* d_pool_n;         /* [D] */
+    const int32_t* d_n_resets;       /* [n_channels] */
+    const int32_t* d_reset_before;   /* [n_channels][max_marks] */
+    const int32_t* d_n_losses;       /* [n_channels] */
+    const int32_t* d_loss_before;    /* [n_channels][max_marks] */
+} ddn_dmr_pdu_input;
+/* Output.  Per burst [D]: the data_conf_data the burst was read under, data_block_counter before it, crc_correct, the DBSN (0xFF:
+ * none), the rate 3/4 pool index chosen (-1: none), and a status byte:
+ *   0 ignored (no effect on a PDU)   1 data header accepted      2 data header rejected for its CRC   3 data header with
+ *   irrecoverable BPTC errors        4 block filed               5 block filed, PDU completed         6 DBSN sequence error (blocks
+ *   reset, no dispatch)              7 MBC longer than 4 blocks  8 data terminator                    9 MBC header filed
+ * Per completed PDU, max_pdus slots per channel and call (P; d_n_pdus counts those past P too), slot c * P + j:
+ *   d_pdu_kind 1 data / 2 MBC / 3 UDT, d_pdu_slot, d_pdu_burst (index of the burst that completed it), d_pdu_len, d_pdu_bytes [3072]
+ *   (zeros behind the length), d_pdu_crc4 {data: CRC32 good (an MNIS header waives it); MBC / UDT: both CRCs good, header CRC good,
+ *   blocks CRC16 good, protect flag}, d_pdu_block_crc [128] data_block_crc_valid at completion, d_pdu_header9 {dpf, sap, blocks, poc,
+ *   confirmed, p_head, gi, source, target} */
+typedef struct ddn_dmr_pdu_output {
+    int max_pdus;
+    uint8_t* d_burst_conf;     /* [D] */
+    int32_t* d_burst_counter;  /* [D] */
+    uint8_t* d_burst_crc;      /* [D] */
+    uint8_t* d_burst_dbsn;     /* [D] */
+    int32_t* d_burst_pick;     /* [D] */
+    uint8_t* d_burst_status;   /* [D] */
+    int32_t* d_n_pdus;         /* [n_channels] */
+    uint8_t* d_pdu_kind;       /* [n_channels][P] */
+    uint8_t* d_pdu_slot;       /* [..] */
+    int32_t* d_pdu_burst;      /* [..] */
+    int32_t* d_pdu_len;        /* [..] */
+    uint8_t* d_pdu_bytes;      /* [..][3072] */
+    uint8_t* d_pdu_crc4;       /* [..][4] */
+    uint8_t* d_pdu_block_crc;  /* [..][128] */
+    int32_t* d_pdu_header9;    /* [..][9] */
+} ddn_dmr_pdu_output;
+size_t ddn_dmr_pdu_state_bytes(void);
+int ddn_dmr_pdu_walk_batch(const ddn_dmr_pdu_input* in, void* d_state, const ddn_dmr_pdu_output* out, void* hip_stream);
+/* The marks of a call from the receive loop's outputs: dmr_reset_blocks() at a kind-5 event whose slot type or TACT failed or that
+ * the colour-code gate rejected (dmr_data_finalize(), dmr_data.c:292-299) and at a kind-8 voice end with a failed TACT or EMB / sync
+ * (dmr_bs.c:671-680,937-947), each with the number of dispatched bursts (kind 6, VC 0) ahead of it in the event list; carrier loss at
+ * every 1800th symbol in a row of the call's new flags (rows of stride_symbols, from carry_symbols to carry_symbols + d_new[c]) that
+ * is neither in frame nor a sync - the loop restarts its count there - placed among the bursts' last symbols (d_burst_start + 143).
+ * The run of hunted symbols is carried in d_state. */
+int ddn_dmr_pdu_marks_batch(const int32_t* d_events, const int32_t* d_n_events, size_t max_events, const uint8_t* d_flags,
+                            size_t stride_symbols, int carry_symbols, const int32_t* d_new, const int32_t* d_burst_start,
+                            const int32_t* d_n_bursts, int n_channels, int max_bursts, void* d_state, int32_t* d_reset_before,
+                            int32_t* d_n_resets, int32_t* d_loss_before, int32_t* d_n_losses, int max_marks, void* hip_stream);
 #ifdef __cplusplus
 }
 #endif
