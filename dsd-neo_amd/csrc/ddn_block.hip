@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include <stdlib.h>
+#include "ddn_crc_dev.h"
 #include "ddn_device.h"
 #include "ddn_nid_dev.h"
 
@@ -458,8 +459,8 @@ ddn_dev_p25_lsd(uint8_t* bits16, const int16_t* llr16, int n, uint8_t* ok, hipSt
 }
 
 // ---- CRC-CCITT16 of decoded TSBK / LCCH blocks (src/protocol/p25/p25_crc.c:18-76) -------------------------------------------
-// polynomial 0x1021, zero start, MSB first, inverted; good when it equals the two bytes after the payload.  One thread per
-// block, a byte at a time through the 8-step bit recurrence (blocks are 12 bytes; there is nothing to tile).
+// ddn_crc::CCITT16; good when it equals the two bytes after the payload.  One thread per block, a byte at a time through the
+// 8-step bit recurrence (blocks are 12 bytes; there is nothing to tile).
 namespace {
 __global__ void
 k_p25_crc16(const uint8_t* __restrict__ bytes, int item_bytes, int n, uint8_t* __restrict__ ok) {
@@ -468,16 +469,7 @@ k_p25_crc16(const uint8_t* __restrict__ bytes, int item_bytes, int n, uint8_t* _
         return;
     }
     const uint8_t* b = bytes + (size_t)i * item_bytes;
-    unsigned crc = 0;
-    for (int k = 0; k < item_bytes - 2; k++) {
-        const unsigned v = b[k];
-#pragma unroll
-        for (int j = 7; j >= 0; j--) {
-            const unsigned bit = (v >> j) & 1u;
-            crc = (((crc >> 15) & 1u) ^ bit) ? (((crc << 1) ^ 0x1021u) & 0xFFFFu) : ((crc << 1) & 0xFFFFu);
-        }
-    }
-    crc ^= 0xFFFFu;
+    const unsigned crc = ddn_crc::of_bytes(ddn_crc::CCITT16, b, item_bytes - 2);
     ok[i] = crc == (((unsigned)b[item_bytes - 2] << 8) | b[item_bytes - 1]) ? 1 : 0;
 }
 } // namespace

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ddn_crc_dev.h"
 #include "ddn_device.h"
 
 namespace {
@@ -357,15 +358,11 @@ k_chain_pdu_gather(const uint8_t* __restrict__ rec, const int32_t* __restrict__ 
     llr[o * 196 + 2 * j + 1] = (int16_t)l1;
 }
 
+// a decoded 12-byte block (TSBK, PDU header): crc16_lb_bridge(bits, 80) == 0 (src/protocol/p25/p25_crc.c:18-36), CRC-CCITT over the
+// first 10 bytes against the next two
 __device__ __forceinline__ bool
-pdu_crc16_ok(const uint8_t* b12) { // crc16_lb_bridge(bits, 80) == 0 (src/protocol/p25/p25_crc.c:18-36): CRC-CCITT over 80 bits, inverted
-    uint32_t crc = 0;
-    for (int i = 0; i < 80; i++) {
-        const uint32_t bit = (b12[i >> 3] >> (7 - (i & 7))) & 1;
-        crc = (((crc >> 15) & 1) ^ bit) ? ((crc << 1) ^ 0x1021) & 0xFFFF : (crc << 1) & 0xFFFF;
-    }
-    crc ^= 0xFFFF;
-    return crc == (((uint32_t)b12[10] << 8) | b12[11]);
+block_crc16_ok(const uint8_t* b12) {
+    return ddn_crc::of_bytes(ddn_crc::CCITT16, b12, 10) == (((uint32_t)b12[10] << 8) | b12[11]);
 }
 
 // The reference's second header fallback (p25_mpdu_try_combined_header, :336-360): when the first header block fails its CRC16 the three
@@ -387,7 +384,7 @@ k_chain_pdu_combine(const uint8_t* __restrict__ rec, const int32_t* __restrict__
         const int cnt = counts[ch] < (int)max_sym ? counts[ch] : (int)max_sym;
         const int n_last = 56 + 97;
         want = sync_pos[slot] - 23 >= 0 && sync_pos[slot] - 23 + n_last + n_last / 35 < cnt
-               && !pdu_crc16_ok(blocks12 + (size_t)e * PB * 12) && !pdu_crc16_ok(blocks12 + ((size_t)e * PB + 1) * 12);
+               && !block_crc16_ok(blocks12 + (size_t)e * PB * 12) && !block_crc16_ok(blocks12 + ((size_t)e * PB + 1) * 12);
     }
     if (j == 0) {
         wanted[e] = want ? 1 : 0;
@@ -447,12 +444,9 @@ k_chain_pdu_r34_wanted(const int32_t* __restrict__ pdu_slot, const uint8_t* __re
 
 __device__ __forceinline__ uint32_t
 pdu_crc9(const uint8_t* b18) { // p25_mpdu_candidate_crc9(): 7 DBSN bits + the 16 payload bytes, ComputeCrc9Bit (dmr_utils.c:410-435)
-    uint32_t crc = 0;
-    for (int i = 0; i < 135; i++) {
-        const int bit = i < 7 ? (b18[0] >> (7 - i)) & 1 : (b18[2 + ((i - 7) >> 3)] >> (7 - ((i - 7) & 7))) & 1;
-        crc = (((crc >> 8) & 1) ^ (uint32_t)bit) ? ((crc << 1) ^ 0x059u) : (crc << 1);
-    }
-    return (crc & 0x1FFu) ^ 0x1FFu;
+    return ddn_crc::of_bits(ddn_crc::CRC9, 135, [&](int i) {
+        return i < 7 ? (b18[0] >> (7 - i)) & 1 : (b18[2 + ((i - 7) >> 3)] >> (7 - ((i - 7) & 7))) & 1;
+    });
 }
 
 // p25_mpdu_select_mbf34_candidate(:176-187): the first candidate whose CRC9 matches, else the cheapest
@@ -499,7 +493,7 @@ k_chain_pdu_finish(const int32_t* __restrict__ pdu_slot, const uint8_t* __restri
                    // 32 header from the three repetitions' summed LLRs, 64 header = bitwise majority of the three decoded repetitions
     if (!hdr_ok) { // the header said nothing: the reference has read three blocks and tries the other two as header repetitions
         for (int rep = 1; rep <= 2 && !hdr_ok; rep++) {
-            if (rep < end && rep - 1 < PB && vld[rep - 1] && pdu_crc16_ok(blk + (size_t)(rep - 1) * 12)) {
+            if (rep < end && rep - 1 < PB && vld[rep - 1] && block_crc16_ok(blk + (size_t)(rep - 1) * 12)) {
                 for (int i = 0; i < 12; i++) {
                     h[i] = blk[(size_t)(rep - 1) * 12 + i];
                 }
@@ -512,7 +506,7 @@ k_chain_pdu_finish(const int32_t* __restrict__ pdu_slot, const uint8_t* __restri
             const int nc = hcount[e] < 8 ? hcount[e] : 8;
             for (int k = 0; k < nc && !hdr_ok; k++) {
                 const uint8_t* cb = hcand16 + ((size_t)e * 8 + k) * 16;
-                if (pdu_crc16_ok(cb)) {
+                if (block_crc16_ok(cb)) {
                     for (int i = 0; i < 12; i++) {
                         h[i] = cb[i];
                     }
@@ -526,7 +520,7 @@ k_chain_pdu_finish(const int32_t* __restrict__ pdu_slot, const uint8_t* __restri
                     h[i] = (uint8_t)((a & b) | (a & cc) | (b & cc));
                 }
                 flags |= 64;
-                hdr_ok = pdu_crc16_ok(h) ? 1 : 0;
+                hdr_ok = block_crc16_ok(h) ? 1 : 0;
             }
         }
         if (!hdr_ok) {
@@ -552,16 +546,7 @@ k_chain_pdu_finish(const int32_t* __restrict__ pdu_slot, const uint8_t* __restri
         if (blks == 0) {
             crc32_ok = 1;
         } else if (blks == nd) {
-            const int len = 96 * blks - 32;
-            uint64_t crc = 0;
-            for (int i = 0; i < len; i++) {
-                crc <<= 1;
-                const int bit = (blk[i >> 3] >> (7 - (i & 7))) & 1;
-                if (((crc >> 32) ^ (uint64_t)bit) & 1) {
-                    crc ^= 0x04c11db7ull;
-                }
-            }
-            const uint32_t got = (uint32_t)((crc & 0xffffffffull) ^ 0xffffffffull);
+            const uint32_t got = ddn_crc::of_bytes(ddn_crc::CRC32, blk, 12 * blks - 4);
             const uint8_t* t = blk + (size_t)blks * 12 - 4;
             const uint32_t want = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | t[3];
             crc32_ok = got == want ? 1 : 0;
@@ -570,16 +555,11 @@ k_chain_pdu_finish(const int32_t* __restrict__ pdu_slot, const uint8_t* __restri
     if (r34 && all) { // p25_mpdu_compute_rate34_crc(:501-519): CRC32 over the blocks' 16 payload bytes but the last four
         if (blks > 0 && blks == nd) {
             const uint8_t* b18 = blocks18 + (size_t)e * PB * 18;
-            const int len = 128 * blks - 32;
-            uint64_t crc = 0;
-            for (int i = 0; i < len; i++) {
-                crc <<= 1;
-                const int bit = (b18[(size_t)(i >> 7) * 18 + 2 + ((i & 127) >> 3)] >> (7 - (i & 7))) & 1;
-                if (((crc >> 32) ^ (uint64_t)bit) & 1) {
-                    crc ^= 0x04c11db7ull;
-                }
+            uint32_t crc = ddn_crc::CRC32.init;
+            for (int i = 0; i < 16 * blks - 4; i++) {
+                crc = ddn_crc::byte(ddn_crc::CRC32, crc, b18[(size_t)(i >> 4) * 18 + 2 + (i & 15)]);
             }
-            const uint32_t got = (uint32_t)((crc & 0xffffffffull) ^ 0xffffffffull);
+            const uint32_t got = ddn_crc::finish(ddn_crc::CRC32, crc);
             const uint8_t* t = b18 + (size_t)(blks - 1) * 18 + 14;
             const uint32_t want = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | t[3];
             crc32_ok = got == want ? 1 : 0;
@@ -780,23 +760,8 @@ k_lpdu_scatter(DdnLongPdu lp) {
     lp.valid[d] = 1;
 }
 
-// crc32mbf (MSB first, polynomial 0x04C11DB7, initial 0, inverted at the end) a byte at a time
-struct LpduCrcTable {
-    uint32_t t[256];
-};
-constexpr LpduCrcTable
-lpdu_crc_table() {
-    LpduCrcTable r{};
-    for (uint32_t i = 0; i < 256; i++) {
-        uint32_t v = i << 24;
-        for (int k = 0; k < 8; k++) {
-            v = (v & 0x80000000u) ? (v << 1) ^ 0x04C11DB7u : (v << 1);
-        }
-        r.t[i] = v;
-    }
-    return r;
-}
-__constant__ LpduCrcTable g_lpdu_crc = lpdu_crc_table();
+// crc32mbf a byte at a time (a long unit has up to 2 k bytes, on one lane)
+__constant__ ddn_crc::ByteTable g_lpdu_crc = ddn_crc::byte_table(ddn_crc::CRC32);
 
 // one workgroup (a wavefront) per entry of a unit that ended in this call: its blocks copied from the carry buffer when it was
 // carried and the blocks never decoded zeroed (the lanes side by side), then one lane counts the decoded data blocks and runs the
@@ -855,12 +820,12 @@ k_lpdu_finish(DdnLongPdu lp) {
     if (!(flags & (8 | 16)) && decoded == nd) {
         const bool r34 = (flags & 4) != 0;
         const int len = (r34 ? 16 : 12) * nd - 4;
-        uint32_t crc = 0;
+        uint32_t crc = ddn_crc::CRC32.init;
         for (int i = 0; i < len; i++) {
             const uint8_t by = r34 ? lp.blocks18[(u + (size_t)(i >> 4)) * 18 + 2 + (i & 15)] : lp.blocks[u * 12 + (size_t)i];
-            crc = (crc << 8) ^ g_lpdu_crc.t[((crc >> 24) ^ by) & 0xFF];
+            crc = ddn_crc::byte(ddn_crc::CRC32, g_lpdu_crc, crc, by);
         }
-        crc ^= 0xFFFFFFFFu;
+        crc = ddn_crc::finish(ddn_crc::CRC32, crc);
         uint32_t want = 0;
         for (int i = len; i < len + 4; i++) {
             const uint8_t by = r34 ? lp.blocks18[(u + (size_t)(i >> 4)) * 18 + 2 + (i & 15)] : lp.blocks[u * 12 + (size_t)i];
@@ -979,21 +944,6 @@ k_u8_shr1(const uint8_t* __restrict__ in, size_t n, uint8_t* __restrict__ out) {
     }
 }
 
-__device__ __forceinline__ bool
-crc16_clean(const uint8_t* b) { // p25_crc.c:18-36 over 10 bytes against the next two
-    unsigned crc = 0;
-    for (int k = 0; k < 10; k++) {
-        const unsigned v = b[k];
-#pragma unroll
-        for (int j = 7; j >= 0; j--) {
-            const unsigned bit = (v >> j) & 1u;
-            crc = (((crc >> 15) & 1u) ^ bit) ? (((crc << 1) ^ 0x1021u) & 0xFFFFu) : ((crc << 1) & 0xFFFFu);
-        }
-    }
-    crc ^= 0xFFFFu;
-    return crc == (((unsigned)b[10] << 8) | b[11]);
-}
-
 __global__ void
 k_tsbk_select(const uint8_t* __restrict__ cand, const int32_t* __restrict__ counts, size_t n, uint8_t* __restrict__ out12,
               uint8_t* __restrict__ crc_ok, uint8_t* __restrict__ sel_out) {
@@ -1005,7 +955,7 @@ k_tsbk_select(const uint8_t* __restrict__ cand, const int32_t* __restrict__ coun
     const int cnt = counts[i];
     int sel = 0, ok = 0;
     for (int k = 0; k < cnt && k < 8; k++) {
-        if (crc16_clean(c + 16 * k)) {
+        if (block_crc16_ok(c + 16 * k)) {
             sel = k;
             ok = 1;
             break;

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ddn_crc_dev.h"
 #include "ddn_device.h"
 
 namespace {
@@ -156,9 +157,15 @@ k_dmr_data_prep(const int32_t* __restrict__ dstart, const uint8_t* __restrict__ 
     }
 }
 
+// ComputeCrc9Bit() (dmr_utils.c:410-435) of a confirmed block held one bit per byte: its payload (bits 16 .. 95, for rate 1 also
+// 100 .. 195), then the 7 DBSN bits
 __device__ __forceinline__ uint32_t
-crc9_step(uint32_t crc, int bit) { // ComputeCrc9Bit(), dmr_utils.c:410-435
-    return (((crc >> 8) & 1) ^ (uint32_t)(bit & 1)) ? ((crc << 1) ^ 0x059u) : (crc << 1);
+confirmed_crc9(const uint8_t* bits, bool rate1) {
+    uint32_t c9 = ddn_crc::bits_u8(ddn_crc::CRC9, ddn_crc::CRC9.init, 80, bits + 16);
+    if (rate1) {
+        c9 = ddn_crc::bits_u8(ddn_crc::CRC9, c9, 96, bits + 100);
+    }
+    return ddn_crc::finish(ddn_crc::CRC9, ddn_crc::bits_u8(ddn_crc::CRC9, c9, 7, bits));
 }
 
 __global__ void
@@ -193,18 +200,7 @@ k_dmr_data_finish(const uint8_t* __restrict__ type, const uint8_t* __restrict__ 
             }
         } else if (ty == 7) { // rate 1/2: unconfirmed blocks carry no CRC; confirmed: DBSN(7) | CRC9 | 10 bytes
             flags |= 1;
-            uint32_t ext = 0, c9 = 0;
-            for (int b = 7; b < 16; b++) {
-                ext = (ext << 1) | (bits[b] & 1);
-            }
-            ext ^= c_crcmask[7];
-            for (int b = 16; b < 96; b++) {
-                c9 = crc9_step(c9, bits[b]);
-            }
-            for (int b = 0; b < 7; b++) {
-                c9 = crc9_step(c9, bits[b]);
-            }
-            if (((c9 & 0x1FF) ^ 0x1FF) == ext) {
+            if (confirmed_crc9(bits, false) == (ddn_crc::field_u8(bits + 7, 9) ^ c_crcmask[7])) {
                 flags |= 2;
             }
         } else if (ty == 8) {
@@ -212,35 +208,13 @@ k_dmr_data_finish(const uint8_t* __restrict__ type, const uint8_t* __restrict__ 
         } else if (ty == 10) { // rate 1: the 196 info bits as they are; confirmed: DBSN(7) | CRC9 | 22 bytes
             flags |= 1;
             const uint8_t* in = info + (size_t)i * 196;
-            uint32_t ext = 0, c9 = 0;
-            for (int b = 7; b < 16; b++) {
-                ext = (ext << 1) | (in[b] & 1);
-            }
-            ext ^= c_crcmask[10];
-            for (int b = 16; b < 96; b++) {
-                c9 = crc9_step(c9, in[b]);
-            }
-            for (int b = 100; b < 196; b++) {
-                c9 = crc9_step(c9, in[b]);
-            }
-            for (int b = 0; b < 7; b++) {
-                c9 = crc9_step(c9, in[b]);
-            }
-            if (((c9 & 0x1FF) ^ 0x1FF) == ext) {
+            if (confirmed_crc9(in, true) == (ddn_crc::field_u8(in + 7, 9) ^ c_crcmask[10])) {
                 flags |= 2;
             }
         } else if (ty != 9) { // PI, CSBK, MBC header / continuation, data header, USBD: CRC-CCITT over the first 80 bits
             const int len = c_crclen[ty];
-            uint32_t ext = 0, c16 = 0;
-            for (int b = 0; b < len; b++) {
-                ext = (ext << 1) | (bits[96 - len + b] & 1);
-            }
-            ext ^= c_crcmask[ty];
-            for (int b = 0; b < 80; b++) { // ComputeCrcCCITT(), dmr_utils.c:253-275
-                c16 = ((((c16 >> 15) & 1) ^ (uint32_t)(bits[b] & 1)) ? ((c16 << 1) ^ 0x1021u) : (c16 << 1)) & 0xFFFFu;
-            }
-            c16 ^= 0xFFFFu;
-            if (c16 == ext) {
+            const uint32_t ext = ddn_crc::field_u8(bits + 96 - len, len) ^ c_crcmask[ty];
+            if (ddn_crc::of_bits_u8(ddn_crc::CCITT16, 80, bits) == ext) { // ComputeCrcCCITT(), dmr_utils.c:253-275
                 flags |= 1;
             }
         }

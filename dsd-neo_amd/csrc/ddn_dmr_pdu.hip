@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ddn_crc_dev.h"
 #include "ddn_device.h"
 
 // What a channel carries from call to call (all zeros = a stream's start: `live` = 0 reads as dsd_init.c / dmr_reset_blocks() leave the
@@ -90,61 +91,6 @@ row_clear(uint8_t* sf, Slot& s, int lane, bool whole) { // only what was written
 __device__ __forceinline__ void
 valid_clear(uint8_t* v, int lane) {
     reinterpret_cast<uint16_t*>(v)[lane] = 0;
-}
-
-// bit-serial CRC of width W (16: x^16 + x^12 + x^5 + 1, 32: 0x04C11DB7), initial value 0, most significant bit first
-template <int W>
-__device__ __forceinline__ uint32_t
-crc_byte(uint32_t crc, uint32_t byte) {
-    constexpr uint32_t poly = W == 16 ? 0x1021u : 0x04C11DB7u, mask = W == 16 ? 0xFFFFu : 0xFFFFFFFFu;
-#pragma unroll
-    for (int q = 7; q >= 0; q--) {
-        const uint32_t fb = ((crc >> (W - 1)) ^ (byte >> q)) & 1u;
-        crc = (crc << 1) & mask;
-        crc ^= fb ? poly : 0u;
-    }
-    return crc;
-}
-template <int W>
-__device__ __forceinline__ uint32_t
-gf2_mulmod(uint32_t a, uint32_t b) { // a * b mod the generator, both of degree < W
-    constexpr uint32_t poly = W == 16 ? 0x1021u : 0x04C11DB7u, mask = W == 16 ? 0xFFFFu : 0xFFFFFFFFu;
-    uint32_t r = 0;
-    for (int i = W - 1; i >= 0; i--) {
-        const uint32_t hi = (r >> (W - 1)) & 1u;
-        r = (r << 1) & mask;
-        r ^= hi ? poly : 0u;
-        r ^= ((b >> i) & 1u) ? a : 0u;
-    }
-    return r;
-}
-// The CRC of n bytes get(0) .. get(n - 1) over the wavefront.  A CRC with initial value 0 is linear and blind to leading zeros, so the
-// message is right-aligned on 64 spans of `per` bytes: every lane runs its span from 0, and a tree folds them - the left half of a
-// pair times x^(8 * per * width of the right half), plus the right half.  Every lane returns the total.
-template <int W, class Get>
-__device__ __forceinline__ uint32_t
-wave_crc(int n, int lane, Get get) {
-    const int per = (n + 63) / 64;
-    const int first = n - (64 - lane) * per;
-    uint32_t v = 0;
-    for (int i = 0; i < per; i++) {
-        const int j = first + i;
-        if (j >= 0) {
-            v = crc_byte<W>(v, get(j));
-        }
-    }
-    uint32_t m = 1; // x^(8 * per)
-    for (int i = 0; i < per; i++) {
-        m = crc_byte<W>(m, 0);
-    }
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t right = (uint32_t)__shfl_down((int)v, s, 64);
-        if ((lane & (2 * s - 1)) == 0) {
-            v = gf2_mulmod<W>(v, m) ^ right;
-        }
-        m = gf2_mulmod<W>(m, m);
-    }
-    return (uint32_t)__shfl((int)v, 0, 64);
 }
 
 // a completed row -> the channel's next PDU slot (the first max_pdus of a call are stored, all are counted)
@@ -218,7 +164,7 @@ assemble(const Out& o, size_t ch, int& np, uint8_t* sf, uint8_t* valid, Slot& s,
             uint32_t ext = 0, comp = 0;
             if (ctr >= 4) {
                 ext = ((uint32_t)sf[ctr - 4] << 24) | ((uint32_t)sf[ctr - 3] << 16) | ((uint32_t)sf[ctr - 2] << 8) | (uint32_t)sf[ctr - 1];
-                comp = wave_crc<32>(ctr - 4, lane, [&](int j) { return (uint32_t)sf[j ^ 1]; });
+                comp = ddn_crc::wave_crc(ddn_crc::CRC32, ctr - 4, lane, [&](int j) { return (uint32_t)sf[j ^ 1]; }); // (not inverted)
                 comp = __builtin_bswap32(comp);
             }
             const int ok = (comp == ext || (s.hfmt == 0xF && s.sap == 1)) ? 1 : 0;
@@ -251,7 +197,8 @@ assemble(const Out& o, size_t ch, int& np, uint8_t* sf, uint8_t* valid, Slot& s,
                     n = n < ROW ? n : ROW;
                     const int eo = 12 * (1 + bc) - 2;
                     const uint32_t ext = ((eo < n ? (uint32_t)sf[eo] : 0u) << 8) | (eo + 1 < n ? (uint32_t)sf[eo + 1] : 0u);
-                    const uint32_t comp = wave_crc<16>(mbytes - 2, lane, [&](int j) { return 12 + j < n ? (uint32_t)sf[12 + j] : 0u; }) ^ 0xFFFFu;
+                    const uint32_t comp = ddn_crc::finish(
+                        ddn_crc::CCITT16, ddn_crc::wave_crc(ddn_crc::CCITT16, mbytes - 2, lane, [&](int j) { return 12 + j < n ? (uint32_t)sf[12 + j] : 0u; }));
                     if (comp == ext) {
                         lb = 1;
                         blocks = bc;
@@ -281,8 +228,8 @@ assemble(const Out& o, size_t ch, int& np, uint8_t* sf, uint8_t* valid, Slot& s,
             limit = limit < 72 ? limit : 72;
             int nb = blocks * 12 - 2;
             nb = nb < 72 ? nb : 72;
-            const uint32_t comp =
-                wave_crc<16>(nb, lane, [&](int j) { return (j < limit && 12 + j < total) ? (uint32_t)sf[12 + j] : 0u; }) ^ 0xFFFFu;
+            const uint32_t comp = ddn_crc::finish(
+                ddn_crc::CCITT16, ddn_crc::wave_crc(ddn_crc::CCITT16, nb, lane, [&](int j) { return (j < limit && 12 + j < total) ? (uint32_t)sf[12 + j] : 0u; }));
             const int good1 = comp == ext ? 1 : 0;
             pdu_emit(o, ch, np, sf, valid, s, slot, burst, is_udt ? KIND_UDT : KIND_MBC, (1 + blocks) * block_len, good0 & good1, good0, good1,
                      pf, lane);

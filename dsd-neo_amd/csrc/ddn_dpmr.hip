@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "ddn_api_util.h"
+#include "ddn_crc_dev.h"
 #include "ddn_device.h"
 #include "ddn_fec3.h"
 #include "ddn_fsk4.h"
@@ -78,11 +79,7 @@ decode_cch(const uint8_t* dib36, const uint8_t* h128, uint8_t* b48, uint8_t* ham
             b48[w * 8 + j] = (uint8_t)((word >> j) & 1u);
         }
     }
-    unsigned crc = 0;
-    for (int i = 0; i < 41; i++) {
-        crc = ((((crc >> 6) & 1u) ^ b48[i]) ? ((crc << 1) ^ 0x09u) : (crc << 1)) & 0x7Fu;
-    }
-    *crc_ok = crc == value_of(b48 + 41, 7) ? 1 : 0;
+    *crc_ok = ddn_crc::of_bits_u8(ddn_crc::DPMR_CRC7, 41, b48) == value_of(b48 + 41, 7) ? 1 : 0;
 }
 
 // One workgroup per sync slot: the 372 dibits into LDS, lanes 0 / 1 decode a CCH each, lane 2 the colour code, then every lane

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "ddn_api_util.h"
+#include "ddn_crc_dev.h"
 #include "ddn_expf.h"
 #include "ddn_fsk4.h"
 #include "ddn_internal.h"
@@ -61,17 +62,9 @@ gmsk_cost(float symbol, const float* thr) {
     return (uint32_t)q;
 }
 
-__device__ __forceinline__ uint32_t
-dstar_crc16(const uint8_t* d, int n) { // CRC-16/X25, returned byte-swapped (dstar_crc16)
-    uint32_t crc = 0xFFFFu;
-    for (int i = 0; i < n; i++) {
-        crc ^= d[i];
-        for (int b = 0; b < 8; b++) {
-            crc = (crc & 1u) ? ((crc >> 1) ^ 0x8408u) : (crc >> 1);
-        }
-    }
-    crc = (~crc) & 0xFFFFu;
-    return ((crc << 8) | (crc >> 8)) & 0xFFFFu;
+__device__ __forceinline__ bool
+header_crc_ok(const uint8_t* h41) { // dstar_crc16() over 39 octets; the frame carries the low byte first
+    return ddn_crc::of_bytes(ddn_crc::DSTAR_X25, h41, 39) == (((uint32_t)h41[40] << 8) | h41[39]);
 }
 
 // slot (ch, k) of the loop's outputs: its pattern row and first symbol, or false when the slot holds no sync / its part is not inside
@@ -191,7 +184,7 @@ k_dstar_header(const uint8_t* __restrict__ rec, size_t stride, const int32_t* __
     }
     __syncthreads();
     if (lane == 0) {
-        crc_ok[slot] = (uint8_t)(dstar_crc16(h, 39) == (((uint32_t)h[39] << 8) | h[40]) ? 1 : 0);
+        crc_ok[slot] = (uint8_t)(header_crc_ok(h) ? 1 : 0);
         valid[slot] = 1;
     }
 }
@@ -285,7 +278,7 @@ k_dstar_voice(const uint8_t* __restrict__ rec, size_t stride, const int32_t* __r
                 hd[i] = 0;
             }
         }
-        sd_crc_ok[slot] = (uint8_t)(dstar_crc16(hd, 39) == (((uint32_t)hd[39] << 8) + hd[40]) ? 1 : 0);
+        sd_crc_ok[slot] = (uint8_t)(header_crc_ok(hd) ? 1 : 0);
         sb[0] = by[0];
     }
     __syncthreads();

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ddn_crc_dev.h"
 #include "ddn_expf.h"
 #include "ddn_fec3.h"
 #include "ddn_tables_fec3.h"
@@ -116,22 +117,11 @@ k_m17_lsf_finish(const uint8_t* __restrict__ dec, int dec_stride, const uint32_t
     const int ch = slot / lmax;
     const size_t so = (size_t)ch * max_syncs + k;
     const uint8_t* by = dec + (size_t)slot * dec_stride + 1; // viterbi_decode()'s bytes 1 .. 30
-    uint32_t crc = 0xFFFFu;
     for (int i = 0; i < 30; i++) {
-        const uint8_t b = by[i];
-        lsf30[so * 30 + i] = b;
-        if (i < 28) {
-            crc ^= (uint32_t)b << 8;
-            for (int q = 0; q < 8; q++) {
-                crc <<= 1;
-                if (crc & 0x10000u) {
-                    crc = (crc ^ 0x5935u) & 0xFFFFu;
-                }
-            }
-        }
+        lsf30[so * 30 + i] = by[i];
     }
     const uint32_t ext = ((uint32_t)by[28] << 8) | by[29];
-    status[so] = (crc & 0xFFFFu) == ext ? 2 : 1;
+    status[so] = ddn_crc::of_bytes(ddn_crc::M17, by, 28) == ext ? 2 : 1;
     if (path_cost) {
         path_cost[so] = cost[slot];
     }
@@ -271,20 +261,10 @@ k_m17_lich(const uint8_t* __restrict__ sync_pat, const int32_t* __restrict__ n_s
                 a[5 * cnt + i] = lich6[so * 6 + i];
             }
             if (cnt == 5) { // M17finalizeLICH: CRC over the reassembled LSF, then the buffer is cleared (:250)
-                uint32_t crc = 0xFFFFu;
                 for (int i = 0; i < 30; i++) {
                     lich_lsf30[so * 30 + i] = a[i];
-                    if (i < 28) {
-                        crc ^= (uint32_t)a[i] << 8;
-                        for (int q = 0; q < 8; q++) {
-                            crc <<= 1;
-                            if (crc & 0x10000u) {
-                                crc = (crc ^ 0x5935u) & 0xFFFFu;
-                            }
-                        }
-                    }
                 }
-                lich_status[so] = (crc & 0xFFFFu) == (((uint32_t)a[28] << 8) | a[29]) ? 2 : 1;
+                lich_status[so] = ddn_crc::of_bytes(ddn_crc::M17, a, 28) == (((uint32_t)a[28] << 8) | a[29]) ? 2 : 1;
                 for (int i = 0; i < 30; i++) {
                     a[i] = 0;
                 }
@@ -383,19 +363,12 @@ k_ysf_fich_finish(const uint8_t* __restrict__ dec, int dec_stride, const uint32_
             fich = (fich << 1) | ((w >> q) & 1u);
         }
     }
-    uint32_t crc = 0; // ysf_crc16 over the 48 bits: a good frame leaves 0
-    for (int i = 0; i < 48; i++) {
-        const uint32_t bit = (uint32_t)((fich >> (47 - i)) & 1u);
-        crc = ((crc << 1) | bit) & 0x1ffffu;
-        if (crc & 0x10000u) {
-            crc = (crc & 0xffffu) ^ 0x1021u;
-        }
-    }
-    crc ^= 0xffffu;
+    // ysf_crc16 divides all 48 bits and wants 0xFFFF left: the CRC of the first 32 against the last 16
+    const uint32_t crc = ddn_crc::of_bits(ddn_crc::CCITT16, 32, [&](int i) { return (uint32_t)((fich >> (47 - i)) & 1u); });
     for (int i = 0; i < 4; i++) {
         fich4[so * 4 + i] = (uint8_t)((fich >> (40 - 8 * i)) & 0xFF);
     }
-    status[so] = (crc & 0xffffu) != 0 ? 3 : (bad ? 2 : 1); // (the reference's err: -2 wins over -1)
+    status[so] = crc != (uint32_t)(fich & 0xFFFFu) ? 3 : (bad ? 2 : 1); // (the reference's err: -2 wins over -1)
     if (v_error) {
         v_error[so] = cost[slot];
     }
@@ -625,19 +598,12 @@ k_ysf_dch_finish(const uint8_t* __restrict__ decA, const uint32_t* __restrict__ 
     }
     const uint8_t* by = vd2 ? decA + (size_t)slot * 16 : decB + (size_t)(slot * 2 + blk) * 32;
     const int nbits = vd2 ? 96 : 176;
-    uint32_t crc = 0;
-    for (int i = 0; i < nbits; i++) {
-        const int b = 8 + i;
-        const uint32_t bit = (by[b >> 3] >> (7 - (b & 7))) & 1u;
-        crc = ((crc << 1) | bit) & 0x1ffff;
-        if (crc & 0x10000) {
-            crc = (crc & 0xffff) ^ 0x1021u;
-        }
-    }
-    crc = (crc ^ 0xffff) & 0xffff;
+    // ysf_crc16 over message + field (decoded bits 8 .., byte-aligned) leaves 0xFFFF: the CRC of the message against the field
+    const int nmsg = (nbits - 16) / 8;
+    const bool crc_ok = ddn_crc::of_bytes(ddn_crc::CCITT16, by + 1, nmsg) == (((uint32_t)by[1 + nmsg] << 8) | by[2 + nmsg]);
     unsigned l = 0x1C9;
     uint8_t* out = dch40 + (so * 2 + blk) * 20;
-    for (int i = 0; i < (nbits - 16) / 8; i++) {
+    for (int i = 0; i < nmsg; i++) {
         int o = 0;
         for (int q = 0; q < 8; q++) {
             const int b = 8 + 8 * i + q;
@@ -645,7 +611,7 @@ k_ysf_dch_finish(const uint8_t* __restrict__ decA, const uint32_t* __restrict__ 
         }
         out[i] = (uint8_t)o;
     }
-    dch_status[so * 2 + blk] = crc == 0 ? 1 : 3;
+    dch_status[so * 2 + blk] = crc_ok ? 1 : 3;
     dch_cost[so * 2 + blk] = vd2 ? pcA[slot] : pcB[slot * 2 + blk];
 }
 

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ddn_crc_dev.h"
 #include "ddn_expf.h"
 
 // What a channel carries from call to call (all zeros = a stream's start; its size is ddn_m17_data_state_bytes()).
@@ -177,21 +178,6 @@ m17_brt_init(int32_t* b) { // m17_prbs9_rx_init(rx, 1)
     b[0] = 0, b[1] = 1, b[2] = 0, b[3] = 0, b[4] = 0, b[5] = 0, b[6] = 0, b[7] = 0;
 }
 
-__device__ __forceinline__ uint32_t
-m17_crc16_dev(const uint8_t* in, int len) { // m17_crc16(), m17_algorithms.c:19-35
-    uint32_t crc = 0xFFFFu;
-    for (int i = 0; i < len; i++) {
-        crc ^= (uint32_t)in[i] << 8;
-        for (int q = 0; q < 8; q++) {
-            crc <<= 1;
-            if (crc & 0x10000u) {
-                crc = (crc ^ 0x5935u) & 0xFFFFu;
-            }
-        }
-    }
-    return crc & 0xFFFFu;
-}
-
 // One lane per channel.  k_m17_lich's buffer (state->m17_lsf) is not touched here although processM17PKT() and the carrier-loss reset
 // zero it too: a stream sync is only accepted after an LSF or a stream sync (dsd_frame_sync.c:972-992), and a complete LSF overwrites
 // all thirty bytes, so no LICH chunk ever lands in a buffer that either clear would have changed - neither is observable there.
@@ -255,7 +241,7 @@ k_m17_data_walk(const uint8_t* __restrict__ sync_pat, const int32_t* __restrict_
                     int app = cnt * 25 + val - 2;
                     app = app > 823 ? 823 : app;
                     const int end = ptr + val;
-                    const bool ok = m17_crc16_dev(buf, app) == (((uint32_t)buf[app] << 8) | buf[app + 1]);
+                    const bool ok = ddn_crc::of_bytes(ddn_crc::M17, buf, app) == (((uint32_t)buf[app] << 8) | buf[app + 1]);
                     if (np < max_packets) {
                         const size_t po = (size_t)ch * max_packets + np;
                         uint8_t* o = packet + po * 832;

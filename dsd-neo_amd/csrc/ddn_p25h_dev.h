@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ddn_crc_dev.h"
 #include "ddn_device.h"
 #include "ddn_nid_dev.h"
 #include "ddn_slicer_dev.h"
@@ -94,16 +95,12 @@ static_assert(half_rate_nibbles_distinct(), "half_rate_hard_path_wave: one branc
 
 __device__ __forceinline__ int
 crc16_ok(const uint32_t w[3]) { // p25_crc.c:18-36 over bytes 0..9 of the 12 (big-endian in the words' byte order below)
-    unsigned crc = 0;
+    unsigned crc = ddn_crc::CCITT16.init;
+#pragma unroll // all 80 steps in line, as the compiler laid the two loops out when the step was written here
     for (int k = 0; k < 10; k++) {
-        const unsigned v = (w[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-#pragma unroll
-        for (int j = 7; j >= 0; j--) {
-            const unsigned bit = (v >> j) & 1u;
-            crc = (((crc >> 15) & 1u) ^ bit) ? (((crc << 1) ^ 0x1021u) & 0xFFFFu) : ((crc << 1) & 0xFFFFu);
-        }
+        crc = ddn_crc::byte(ddn_crc::CCITT16, crc, (w[k >> 2] >> (8 * (k & 3))) & 0xFFu);
     }
-    crc ^= 0xFFFFu;
+    crc = ddn_crc::finish(ddn_crc::CCITT16, crc);
     const unsigned b10 = (w[2] >> 16) & 0xFFu, b11 = (w[2] >> 24) & 0xFFu;
     return crc == ((b10 << 8) | b11);
 }
@@ -282,18 +279,13 @@ wave_xor(uint32_t v) {
            ^ (uint32_t)__builtin_amdgcn_readlane((int)v, 32) ^ (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
 }
 
-// CRC16 (p25_crc.c:18-36: 0x1021, zero start, inverted) of bytes 0..9 against bytes 10..11, the wavefront on it: the register
-// is linear in the message, so lane j adds in the contribution of message bits j and j + 64 (sc.crc_cols: the register after
-// shifting a lone one through the remaining bits) and a wave-wide XOR finishes.  by[] is the same in every lane.
+// CRC16 (ddn_crc::CCITT16) of bytes 0..9 against bytes 10..11, the wavefront on it: the register is linear in the message, so
+// lane j adds in the contribution of message bits j and j + 64 (sc.crc_cols, ddn_crc::column) and a wave-wide XOR finishes.
+// by[] is the same in every lane.
 __device__ inline void
 crc_cols_fill(uint16_t* cols, int lane) { // lanes 0..63 of one wave
     for (int i = lane; i < 80; i += 64) {
-        unsigned crc = 0;
-        for (int k = 0; k < 80; k++) {
-            const unsigned bit = (k == i) ? 1u : 0u;
-            crc = (((crc >> 15) & 1u) ^ bit) ? (((crc << 1) ^ 0x1021u) & 0xFFFFu) : ((crc << 1) & 0xFFFFu);
-        }
-        cols[i] = (uint16_t)crc;
+        cols[i] = (uint16_t)ddn_crc::column(ddn_crc::CCITT16, 80, i);
     }
 }
 __device__ __forceinline__ int
@@ -303,7 +295,7 @@ crc16_ok_wave(const Scratch& sc, const uint32_t by[3], int lane) {
     if (lane < 16) {
         v ^= msg_bit(lane + 64) ? sc.crc_cols[lane + 64] : 0u;
     }
-    const uint32_t crc = wave_xor(v) ^ 0xFFFFu;
+    const uint32_t crc = ddn_crc::finish(ddn_crc::CCITT16, wave_xor(v));
     const uint32_t b10 = (by[2] >> 16) & 0xFFu, b11 = (by[2] >> 24) & 0xFFu;
     return crc == ((b10 << 8) | b11);
 }

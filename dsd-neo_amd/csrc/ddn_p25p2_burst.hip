@@ -14,6 +14,7 @@
 
 #include <stdint.h>
 
+#include "ddn_crc_dev.h"
 #include "ddn_device.h"
 #include "ddn_tables_isch.h"
 
@@ -105,30 +106,10 @@ k_p2_mac_crc(int kind, const uint8_t* __restrict__ payload_bits, int n, uint8_t*
     }
     const int n_pl = kind == 0 ? 156 : 180, len = n_pl - 12;
     const uint8_t* b = payload_bits + (size_t)i * n_pl;
-    uint32_t reg = 0; // the long division: 13-bit register, the polynomial's bits 1 1000 1001 0111
-    for (int k = 0; k < len + 12; k++) {
-        reg = (reg << 1) | (k < len ? (uint32_t)(b[k] & 1) : 0u);
-        if (reg & 0x1000u) {
-            reg ^= 0x1897u;
-        }
-    }
-    uint32_t got = 0;
-    for (int k = 0; k < 12; k++) {
-        got = (got << 1) | (uint32_t)(b[len + k] & 1);
-    }
-    crc12_ok[i] = ((reg ^ 0xFFFu) & 0xFFFu) == got ? 1 : 0;
+    // (the reference divides the message with twelve zeros appended: the ordinary CRC)
+    crc12_ok[i] = ddn_crc::of_bits_u8(ddn_crc::P25_CRC12, len, b) == ddn_crc::field_u8(b + len, 12) ? 1 : 0;
     if (crc16_ok) {
-        uint32_t c = 0, g16 = 0;
-        if (kind == 1) {
-            for (int k = 0; k < 164; k++) {
-                c = ((((c >> 15) & 1u) ^ (uint32_t)(b[k] & 1)) ? ((c << 1) ^ 0x1021u) : (c << 1)) & 0xFFFFu;
-            }
-            c ^= 0xFFFFu;
-            for (int k = 0; k < 16; k++) {
-                g16 = (g16 << 1) | (uint32_t)(b[164 + k] & 1);
-            }
-        }
-        crc16_ok[i] = (kind == 1 && c == g16) ? 1 : 0;
+        crc16_ok[i] = (kind == 1 && ddn_crc::of_bits_u8(ddn_crc::CCITT16, 164, b) == ddn_crc::field_u8(b + 164, 16)) ? 1 : 0;
     }
 }
 

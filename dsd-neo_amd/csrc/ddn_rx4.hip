@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <stdint.h>
 
+#include "ddn_crc_dev.h"
 #include "ddn_device.h"
 #include "ddn_slicer_dev.h"
 #include "ddn_fsk4h_dev.h"
@@ -1978,9 +1979,8 @@ k_nxdn_frame_gather(const uint8_t* __restrict__ rec, const int32_t* __restrict__
     }
 }
 
-// CRC of a decoded NXDN field, bit-serial as the reference computes it (crc6: nxdn_deperm.c:1246-1261, x^6+x^5+x^2+x+1;
-// crc12f: nxdn_dcr_utils.c:21-42, x^12+x^11+x^3+x^2+x+1; registers start all ones): kind 0 = SACCH (26 + 6 bits), 1 = FACCH1
-// (80 + 12).  bytes = the K = 5 decoder's output rows, MSB first.
+// CRC of a decoded NXDN field, bit-serial as the reference computes it (ddn_crc::NXDN_CRC6 / NXDN_CRC12F, registers start all
+// ones): kind 0 = SACCH (26 + 6 bits), 1 = FACCH1 (80 + 12).  bytes = the K = 5 decoder's output rows, MSB first.
 __global__ void
 k_nxdn_crc(const uint8_t* __restrict__ bytes, int stride, int n, int kind, uint8_t* __restrict__ ok) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1990,23 +1990,14 @@ k_nxdn_crc(const uint8_t* __restrict__ bytes, int stride, int n, int kind, uint8
     const uint8_t* b = bytes + (size_t)i * stride;
     const bool bitrows = (kind & 2) != 0; // rows hold one bit per byte (trellis_decode output) instead of packed bytes
     kind &= 1;
-    const int nd = kind == 0 ? 26 : 80, nc = kind == 0 ? 6 : 12;
-    const unsigned poly = kind == 0 ? 0x27u : 0x80Fu; // x^5+x^2+x+1 / x^11+x^3+x^2+x+1 below the leading term
-    const unsigned top = 1u << (nc - 1), mask = (1u << nc) - 1u;
-    unsigned crc = mask;
-    for (int k = 0; k < nd; k++) {
-        const unsigned in = bitrows ? (b[k] & 1u) : ((b[k >> 3] >> (7 - (k & 7))) & 1u);
-        const unsigned fb = ((crc & top) ? 1u : 0u) ^ in;
-        crc = (crc << 1) & mask;
-        if (fb) {
-            crc ^= poly;
-        }
-    }
+    const int nd = kind == 0 ? 26 : 80;
+    const ddn_crc::Code code = kind == 0 ? ddn_crc::NXDN_CRC6 : ddn_crc::NXDN_CRC12F;
+    auto in = [&](int k) { return bitrows ? (b[k] & 1u) : ((b[k >> 3] >> (7 - (k & 7))) & 1u); };
     unsigned got = 0;
-    for (int k = nd; k < nd + nc; k++) {
-        got = (got << 1) | (bitrows ? (b[k] & 1u) : ((b[k >> 3] >> (7 - (k & 7))) & 1u));
+    for (int k = nd; k < nd + code.width; k++) {
+        got = (got << 1) | in(k);
     }
-    ok[i] = crc == got ? 1 : 0;
+    ok[i] = ddn_crc::of_bits(code, nd, in) == got ? 1 : 0;
 }
 
 template <int CPW, int MAXW, int PROTO, bool HM>

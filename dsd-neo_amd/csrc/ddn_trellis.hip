@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ddn_crc_dev.h"
 #include "ddn_device.h"
 
 namespace {
@@ -1020,15 +1021,8 @@ k_dmr_r34_pick(const uint8_t* __restrict__ td98, const uint8_t* __restrict__ rel
                 prev = next;
             }
             // DBSN(7) | CRC9 ^ 0x1FF | 16 bytes: ComputeCrc9Bit over the 128 payload bits, then the DBSN
-            uint32_t c9 = 0;
-            for (int b = 16; b < 144; b++) {
-                const int bit = (b18[b >> 3] >> (7 - (b & 7))) & 1;
-                c9 = (((c9 >> 8) & 1) ^ (uint32_t)bit) ? ((c9 << 1) ^ 0x059u) : (c9 << 1);
-            }
-            for (int b = 0; b < 7; b++) {
-                const int bit = (b18[0] >> (7 - b)) & 1;
-                c9 = (((c9 >> 8) & 1) ^ (uint32_t)bit) ? ((c9 << 1) ^ 0x059u) : (c9 << 1);
-            }
+            uint32_t c9 = ddn_crc::bytes(ddn_crc::CRC9, ddn_crc::CRC9.init, b18 + 2, 16);
+            c9 = ddn_crc::bits(ddn_crc::CRC9, c9, 7, [&](int b) { return (b18[0] >> (7 - b)) & 1; });
             const uint32_t ext = ((((uint32_t)b18[0] & 1u) << 8) | b18[1]) ^ 0x1FFu;
             uint8_t* o = pool + count * 24;
             o[0] = (uint8_t)metric;
@@ -1038,7 +1032,7 @@ k_dmr_r34_pick(const uint8_t* __restrict__ td98, const uint8_t* __restrict__ rel
             for (int b = 0; b < 18; b++) {
                 o[4 + b] = b18[b];
             }
-            o[22] = (((c9 & 0x1FFu) ^ 0x1FFu) == ext) ? 1 : 0;
+            o[22] = ddn_crc::finish(ddn_crc::CRC9, c9) == ext ? 1 : 0;
             o[23] = (uint8_t)(b18[0] >> 1);
             count++;
         }

@@ -278,8 +278,8 @@ def nxdn_frame_fields(dibits182, rel182):
             np.array(fs, np.uint8).reshape(2, 96, 2), np.array(fr, np.uint8).reshape(2, 96, 2))
 
 
-def nxdn_crc_ok(bits, kind):
-    """kind 0: 26 + CRC6 (x^6+x^5+x^2+x+1), kind 1: 80 + CRC12 (x^12+x^11+x^3+x^2+x+1); registers start all ones"""
+def nxdn_crc(bits, kind):
+    """kind 0: CRC6 (x^6+x^5+x^2+x+1) of the first 26 bits, kind 1: CRC12 (x^12+x^11+x^3+x^2+x+1) of the first 80; registers start all ones"""
     nd, nc, poly = (26, 6, 0x27) if kind == 0 else (80, 12, 0x80F)
     crc, mask, top = (1 << nc) - 1, (1 << nc) - 1, 1 << (nc - 1)
     for b in bits[:nd]:
@@ -287,7 +287,13 @@ def nxdn_crc_ok(bits, kind):
         crc = (crc << 1) & mask
         if fb:
             crc ^= poly
-    return crc == bits_int(bits[nd:nd + nc])
+    return crc
+
+
+def nxdn_crc_ok(bits, kind):
+    """the 26 + 6 (kind 0) / 80 + 12 (kind 1) bits of a decoded field: the CRC of the first part equals the second"""
+    nd, nc = (26, 6) if kind == 0 else (80, 12)
+    return nxdn_crc(bits, kind) == bits_int(bits[nd:nd + nc])
 
 
 def nxdn_superframes(sacch_rows):

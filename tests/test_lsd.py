@@ -146,3 +146,32 @@ def test_crc16_gpu_vs_oracle(built):
     assert l.crc16_lb_bridge(np.unpackbits(b[0]).astype(np.int32).ctypes.data, 80) == 0
     assert l.crc16_lb_bridge(np.unpackbits(b[1]).astype(np.int32).ctypes.data, 80) == 65535
     assert l.crc16_lb_bridge(np.zeros(300, np.int32).ctypes.data, 224) == 65535   # beyond the reference's 190-bit buffer
+
+
+@pytest.mark.gpu
+def test_tsbk_select_takes_the_first_clean_candidate(built):
+    """ddn_fec_p25_tsbk_select_batch (tsbk_select_crc_candidate(), p25p1_tsbk.c:108-130) on five items of eight {12 bytes, metric}
+    candidates: a clean first one; one message bit flipped, one check-field bit flipped, then a clean one; none clean (the best stays);
+    no candidates (zeros); only the eighth clean - the verdict per candidate is the oracle's"""
+    import torch
+    l = ddn.lib()
+    b, o = _crc_cases(21, 16)
+    clean, dirty = b[0::2], b[1::2]
+    assert all(o.orc_p25_crc16_ok(np.ascontiguousarray(v).ctypes.data, 10) == 0 for v in clean)
+    cand = np.zeros((5, 8, 16), np.uint8)
+    cand[:, :, :12] = dirty[np.arange(40).reshape(5, 8) % 8]
+    counts = np.array([3, 3, 2, 0, 8], np.int32)
+    cand[0, 0, :12] = clean[0]
+    cand[1, 0, :12], cand[1, 1, :12], cand[1, 2, :12] = clean[1], clean[2], clean[3]
+    cand[1, 0, 4] ^= 0x10
+    cand[1, 1, 11] ^= 0x01
+    cand[4, 7, :12] = clean[4]
+    want_ok = np.array([[o.orc_p25_crc16_ok(np.ascontiguousarray(cand[i, k, :12]).ctypes.data, 10) == 0 for k in range(8)] for i in range(5)])
+    assert want_ok[:, :3].tolist() == [[1, 0, 0], [0, 0, 1], [0, 0, 0], [0, 0, 0], [0, 0, 0]] and want_ok[4, 7]
+    d_c, d_n = torch.from_numpy(cand).cuda(), torch.from_numpy(counts).cuda()
+    out, ok, sel = (torch.full(s, 0xEE, dtype=torch.uint8, device="cuda") for s in ((5, 12), (5,), (5,)))
+    assert l.ddn_fec_p25_tsbk_select_batch(d_c.data_ptr(), d_n.data_ptr(), 5, out.data_ptr(), ok.data_ptr(), sel.data_ptr(), None) == 0
+    torch.cuda.synchronize()
+    assert ok.cpu().tolist() == [1, 1, 0, 0, 1] and sel.cpu().tolist() == [0, 2, 0, 0, 7]
+    want = np.stack([cand[0, 0, :12], cand[1, 2, :12], cand[2, 0, :12], np.zeros(12, np.uint8), cand[4, 7, :12]])
+    assert np.array_equal(out.cpu().numpy(), want)

@@ -196,6 +196,29 @@ def test_trellis_decode_batch_and_dropin(built):
     assert l.ddn_fec_trellis_decode_host(src.ctypes.data, 10, 1, 32, got.ctypes.data, 32) != 0       # row too short for the lookahead
 
 
+@pytest.mark.parametrize("kind", [0, 1, 2, 3])
+def test_nxdn_crc_check_good_and_broken(built, kind):
+    """ddn_nxdn_crc_check_batch on three fields per kind (0 SACCH 26 + 6, 1 FACCH1 80 + 12 as packed bytes, 2 / 3 the same as bit rows):
+    clean, one message bit flipped, one check bit flipped - the verdicts of tests/rx4.py's restatement"""
+    import torch
+    rng = np.random.default_rng(70 + kind)
+    nd, nc = (26, 6) if kind & 1 == 0 else (80, 12)
+    rows = np.zeros((3, 96), np.uint8)
+    rows[:, :nd] = rng.integers(0, 2, (3, nd))
+    for r in rows:
+        c = rx4.nxdn_crc(r, kind & 1)
+        r[nd:nd + nc] = [(c >> (nc - 1 - i)) & 1 for i in range(nc)]
+    rows[1, nd // 2] ^= 1
+    rows[2, nd + 1] ^= 1
+    want = [rx4.nxdn_crc_ok(r, kind & 1) for r in rows]
+    assert want == [True, False, False]
+    x = rows if kind & 2 else np.packbits(rows, axis=1)
+    d, ok = torch.from_numpy(np.ascontiguousarray(x)).cuda(), torch.full((3,), 0xEE, dtype=torch.uint8, device="cuda")
+    assert ddn.lib().ddn_nxdn_crc_check_batch(d.data_ptr(), x.shape[1], 3, kind, ok.data_ptr(), None) == 0
+    torch.cuda.synchronize()
+    assert ok.cpu().tolist() == [1, 0, 0]
+
+
 def test_nxdn48_known_answer_on_device(built):
     """NXDN48 capture, everything after the front end on the device: receive loop -> frame gather (de-scramble, LICH, SACCH /
     FACCH1 de-interleave + de-puncture) -> K=5 soft decode -> CRC6 -> greedy retry for the rows that failed -> CRC6; the host

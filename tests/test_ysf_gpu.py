@@ -470,3 +470,53 @@ def test_generated_voice_of_every_mode_to_pcm_through_the_chain_object(built):
                 assert not g[1][nf:].any() and np.array_equal(g[2][:nf], ro[0]), (key, c, f["pos"])
                 total[key] += nf
     assert total["a"] >= 2 * (3 * 4 + 2 * 5) - 9 and total["i"] >= 2 * (2 + 5), total
+
+
+def test_data_channel_blocks_with_good_and_broken_crc16(built):
+    """the 176-bit data channel (tests/ysfgen.py's encoder: whitening, CRC-CCITT16, K = 5 code, 20 x 9 interleave): a full-rate data
+    frame {clean block, block with one message bit flipped before the encoder}, one {one check-field bit flipped, clean block} and a V/D
+    mode 1 frame with a clean block - statuses 1 / 3 and the data bytes as the CPU pipeline gives them, and as they were sent"""
+    import torch
+    import p25gen
+    import ysfgen
+    l = ddn.lib()
+    rng = np.random.default_rng(47)
+    data = rng.integers(0, 256, (5, 20)).astype(np.uint8)
+    blk = ysfgen.dch_dibits
+    plan = [(0, 1, {}),
+            (0, 1, dict(payload=ysfgen.data_payload([blk(data[0]), blk(data[1], flip=77)], rng))),
+            (1, 1, dict(payload=ysfgen.data_payload([blk(data[2], flip=165), blk(data[3])], rng))),
+            (1, 0, dict(fn=1, ft=6, payload=ysfgen.data_payload([blk(data[4])], rng))),
+            (2, 1, {})]
+    dib = np.concatenate([ysfgen.frame(rng, fi, dt, **kw) for fi, dt, kw in plan] + [rng.integers(0, 4, 60).astype(np.uint8)])
+    x = p25gen.modulate_disc(dib, lead=260, noise=250.0, seed=3)[None]
+    B, n = x.shape
+    rx = ddn.Fsk4Rx(B, ddn.FSK4_YSF)
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda")
+    p = lambda t: t.data_ptr()
+    d = torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    ms, my = l.ddn_fsk4_rx_max_symbols(rx.h, n), l.ddn_fsk4_rx_max_syncs(rx.h, n)
+    rec, fl, pay = z((B, ms, 10), torch.uint8), z((B, ms), torch.uint8), z((B, ms, 2), torch.uint8)
+    cnt, ns, spos = z((B,), torch.int32), z((B,), torch.int32), z((B, my), torch.int32)
+    spat, pre, prel = z((B, my), torch.uint8), z((B, my, 90), torch.uint8), z((B, my, 90), torch.uint8)
+    assert l.ddn_fsk4_rx_run(rx.h, p(d), n, p(rec), p(fl), p(pay), p(cnt), ms, p(spos), p(spat), p(pre), p(prel), p(ns), my, None) == 0
+    f4, st, ve = z((B, my, 4), torch.uint8), z((B, my), torch.uint8), z((B, my), torch.int32)
+    assert l.ddn_ysf_fich_decode_batch(p(rec), ms, p(cnt), p(spos), p(ns), B, my, p(f4), p(st), p(ve), None) == 0
+    last = z((B, 2), torch.uint8)
+    info, dch, dst = z((B, my, 2), torch.uint8), z((B, my, 2, 20), torch.uint8), z((B, my, 2), torch.uint8)
+    dcost, ambe, errs = z((B, my, 2), torch.int32), z((B, my, 5, 49), torch.uint8), z((B, my, 5), torch.uint8)
+    fr, nfr = z((B, my, 5, 184), torch.uint8), z((B, my), torch.uint8)
+    assert l.ddn_ysf_payload_decode_batch(p(rec), ms, p(cnt), p(spos), p(ns), B, my, p(f4), p(st), p(last), p(info), p(dch), p(dst),
+                                          p(dcost), p(ambe), p(errs), p(fr), p(nfr), None) == 0, l.ddn_last_error()
+    torch.cuda.synchronize()
+    g = lambda t: t.cpu().numpy()
+    st, info, dch, dst, dcost, ambe, errs, fr, nfr = g(st), g(info), g(dch), g(dst), g(dcost).view(np.uint32), g(ambe), g(errs), g(fr), g(nfr)
+    want = rx4.OracleFsk4Rx(rx4.profile(rx4.PROTO_YSF)).run(x[0], max_sync=my)
+    frames, _ = ysf.decode_payloads(want)
+    mine = [k for k in range(int(g(ns)[0])) if st[0, k] != 0]
+    assert [int(g(spos)[0, k]) for k in mine] == [f["pos"] for f in frames]
+    for k, f in zip(mine, frames):
+        _payload_equal(info[0, k], dch[0, k], dst[0, k], dcost[0, k], ambe[0, k], errs[0, k], f, k, fr[0, k], nfr[0, k])
+    seen = [(int(info[0, k, 0]), dst[0, k].tolist(), dch[0, k]) for k in mine[-4:-1]]     # the three frames before the terminator
+    assert [(s[0], s[1]) for s in seen] == [(8, [1, 3]), (8, [3, 1]), (1, [1, 0])], [(s[0], s[1]) for s in seen]
+    assert np.array_equal(seen[0][2][0], data[0]) and np.array_equal(seen[1][2], data[2:4]) and np.array_equal(seen[2][2][0], data[4])

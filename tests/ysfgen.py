@@ -100,10 +100,50 @@ def fich_dibits(fi, dt, cm=1, bn=0, bt=0, fn=0, ft=0, mr=0, vp=1, st=0, sc=0, cs
     return inp
 
 
-def frame(rng, fi, dt, break_fich=False, **kw):
-    """-> 480 dibits: sync + FICH + random payload (break_fich: enough FICH dibits flipped for Golay / CRC to fail)"""
+def pn95(n):
+    """the whitening sequence: x^9 + x^4 + 1 seeded 0x1C9, LSB out, restarted every 512 bits"""
+    out, l = [], 0
+    for i in range(n):
+        if i % 512 == 0:
+            l = 0x1C9
+        out.append(l & 1)
+        l = (l >> 1) | ((((l >> 4) ^ l) & 1) << 8)
+    return np.array(out, np.uint8)
+
+
+def dch_dibits(data20, flip=None):
+    """20 data bytes -> the 180 dibits of one DCH block as ysf_conv_dch reads them: whitened, CRC-CCITT16 (inverted) behind them, the
+    K = 5 code, the 20 x 9 interleave.  flip: one of the 176 bits inverted before the encoder (< 160 message, >= 160 check field)"""
+    import rx4
+    m = np.unpackbits(np.asarray(data20, np.uint8)) ^ pn95(160)
+    c = rx4.crc_ccitt_bits(m) ^ 0xFFFF
+    tb = np.concatenate([m, [(c >> (15 - i)) & 1 for i in range(16)]]).astype(np.uint8)
+    assert _o().orc_ysf_crc16(tb.ctypes.data, 176) == 0
+    if flip is not None:
+        tb[flip] ^= 1
+    buf = conv_k5(tb)                       # 180 dibits; the decoder reads buf[j + 9 i] = input[i + 20 j]
+    inp = np.zeros(180, np.uint8)
+    for i in range(20):
+        for j in range(9):
+            inp[i + 20 * j] = buf[9 * i + j]
+    return inp
+
+
+def data_payload(blocks, rng):
+    """-> the 360 payload dibits: two DCH blocks = a full-rate data frame (their 36-dibit chunks in turn); one = a V/D mode 1 frame
+    (five chunks, each followed by 36 random voice dibits)"""
+    p = rng.integers(0, 4, 360).astype(np.uint8)
+    step = 36 * len(blocks) if len(blocks) == 2 else 72
+    for b, d in enumerate(blocks):
+        for i in range(5):
+            p[step * i + 36 * b:step * i + 36 * b + 36] = d[36 * i:36 * i + 36]
+    return p
+
+
+def frame(rng, fi, dt, break_fich=False, payload=None, **kw):
+    """-> 480 dibits: sync + FICH + payload, random unless given (break_fich: enough FICH dibits flipped for Golay / CRC to fail)"""
     f = fich_dibits(fi, dt, **kw)
     if break_fich:
         k = rng.choice(100, 40, replace=False)
         f[k] ^= rng.integers(1, 4, 40).astype(np.uint8)
-    return np.concatenate([SYNC, f, rng.integers(0, 4, 360).astype(np.uint8)])
+    return np.concatenate([SYNC, f, rng.integers(0, 4, 360).astype(np.uint8) if payload is None else payload])
