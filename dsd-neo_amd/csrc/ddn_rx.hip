@@ -2118,6 +2118,12 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
     int dbg_n[3] = {0, 0, 0}, dbg_kind = -1;
     long long dbg_blk[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dbg_bt = 0; // bulk hunting pass, by section
 #define DBG_BLK(k) do { if (DDN_RX_CYCLES && (cfg.dbg & 8192)) { const long long n_ = (long long)clock64(); dbg_blk[k] += n_ - dbg_bt; dbg_bt = n_; } } while (0)
+    // two / four lanes per recurrence wave: the same sections as 32-bit sums (the kernel has no registers to spare; a launch's
+    // passes stay far below 2^32 cycles): [0..5] as dbg_blk, [6] symbols, [7] owners, [8] the crossing masks' part of [1],
+    // [9] passes of several owners
+    uint32_t dbg_b[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, dbg_b0 = 0;
+#define DBG_B(k) do { if (DDN_RX_CYCLES && (cfg.dbg & 8192)) { const uint32_t n_ = (uint32_t)clock64(); dbg_b[k] += n_ - dbg_b0; dbg_b0 = n_; } } while (0)
+#define DBG_B2(k, k2) do { if (DDN_RX_CYCLES && (cfg.dbg & 8192)) { const uint32_t n_ = (uint32_t)clock64(); dbg_b[k] += n_ - dbg_b0; dbg_b[k2] += n_ - dbg_b0; dbg_b0 = n_; } } while (0)
     long long dbg_run[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // lean runs: count, trips, -, -, -, runs polling a mailbox, cycles inside the run, phases
     long long dbg_ent[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // a lean run's entry, by part: queue hand-over, lean tests + entry proof, run length
     if (HM && loader) {
@@ -2345,13 +2351,17 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                     // ---- (round 5) two / four channels per recurrence wave: every hunting lane's pass at once ------------------------
                     // A channel of such a wave has a ROW of 64 / LPR >= 16 lanes and a pass is at most 15 symbols, so every owner's
                     // pass fits its own row: the owner's words are broadcast over its row, lane l of a row is symbol l of that row's
-                    // owner (mean, sign, history word, sync compare, stores, extrema), the owner lanes read their rows' results.  The
+                    // owner (mean, sign, history word, sync compare, stores, extrema), the rows push their results to the owner lanes.  The
                     // slip chain: one owner - the crossing mask by three wave-wide ballots and the chain on scalars (as before);
                     // several owners (1.4 per pass on the bench traffic, 2.4 on voice calls whose frames end together) - the mask
                     // 64 / LPR samples per owner and ballot, the chain per row on the vector unit (its words are uniform inside a row).
                     if constexpr (LPR == 2 || LPR == 4) {
                     if (__builtin_expect(bm != 0, 0)) {
                         const long long bt0 = (DDN_RX_CYCLES && (cfg.dbg & 8192)) ? (long long)clock64() : 0;
+                        if (DDN_RX_CYCLES && (cfg.dbg & 8192)) {
+                            dbg_b0 = (uint32_t)bt0;
+                            dbg_b[7] += __popcll(bm);
+                        }
                         constexpr int OW = 64 / LPR;
                         constexpr int CAP = OW < 17 ? OW - 1 : 16; // (lane `m` of the row holds the start after the pass)
                         constexpr unsigned long long GM = OW == 32 ? 0xFFFFFFFFull : 0xFFFFull;
@@ -2368,58 +2378,76 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                             while (b2) {
                                 const int ow = __ffsll((long long)b2) - 1;
                                 b2 &= b2 - 1;
+                                // (the owner's words by v_readlane: ow is wave-uniform, no trip through the LDS crossbar)
+                                auto rlf = [&](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), ow)); };
                                 const int sp0s = __builtin_amdgcn_readlane(sp, ow), c0s = __builtin_amdgcn_readlane(s.hist_count, ow);
-                                const float cen_s = __shfl(s.center, ow), ls_s = __shfl(s.lastsample, ow);
-                                float hl = __shfl(s.maxref * 1.25f, ow), ll = __shfl(s.minref * 1.25f, ow);
-                                const float hl_n = __shfl(s.max * 1.25f, ow), ll_n = __shfl(s.min * 1.25f, ow);
+                                const float cen_s = rlf(s.center), ls_s = rlf(s.lastsample);
+                                float hl = rlf(s.maxref * 1.25f), ll = rlf(s.minref * 1.25f);
+                                const float hl_n = rlf(s.max * 1.25f), ll_n = rlf(s.min * 1.25f);
                                 const float* prs = (__builtin_amdgcn_readlane(s.filter_on, ow) ? &L.flt[rw * LPR + ow][0] : &L.raw[rw * LPR + ow][0]) + base;
                                 int q = sp0s, sm = 0, jit = __builtin_amdgcn_readlane(s.jitter, ow);
                                 int lim = c0s < 8 ? 8 - c0s : CAP;
+                                // the staged samples sp0s .. tn - 1 and their predecessors, read once and all at once (lane + 64 r; a lane past
+                                // the tile reads the pass's first sample and counts for nothing): the second phase compares them again
+                                float xs[3], xps[3];
+#pragma unroll
+                                for (int r = 0; r < 3; r++) {
+                                    const int a = sp0s + lane + 64 * r;
+                                    xs[r] = prs[a < tn ? a : sp0s];
+                                    xps[r] = prs[(a < tn && a > sp0s) ? a - 1 : sp0s];
+                                }
+                                xps[0] = lane == 0 ? ls_s : xps[0];
+                                DBG_B(0);
                                 for (int ph = 0; ph < 2; ph++) {
                                     unsigned long long cm[3];
                                     q = __builtin_amdgcn_readfirstlane(q);
                                     sm = __builtin_amdgcn_readfirstlane(sm);
                                     jit = __builtin_amdgcn_readfirstlane(jit);
-#pragma unroll
-                                    for (int r = 0; r < 3; r++) {
-                                        cm[r] = 0ull;
-                                        if (q + 64 * r < tn) {
-                                            const int a = q + lane + 64 * r;
-                                            bool hit = false;
-                                            if (a < tn) {
-                                                const float x = prs[a];
-                                                const float xp = (a == sp0s) ? ls_s : prs[a - 1];
-                                                hit = (x > cen_s) ? (!(x > hl) && xp < cen_s) : (!(x < ll) && xp > cen_s);
-                                            }
-                                            cm[r] = __ballot(hit);
-                                        }
-                                    }
-                                    bool full = false;
                                     auto uni64 = [](unsigned long long v) {
                                         const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
                                         const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
                                         return ((unsigned long long)hi << 32) | lo;
                                     };
-                                    cm[0] = uni64(cm[0]);
-                                    cm[1] = uni64(cm[1]);
-                                    cm[2] = uni64(cm[2]);
-                                    while (sm < lim) {
+#pragma unroll
+                                    for (int r = 0; r < 3; r++) { // bit a - sp0s of the mask: the crossing test of sample a
+                                        const float x = xs[r], xp = xps[r];
+                                        const bool hit = (sp0s + lane + 64 * r < tn)
+                                                         && ((x > cen_s) ? (!(x > hl) && xp < cen_s) : (!(x < ll) && xp > cen_s));
+                                        cm[r] = uni64(__ballot(hit));
+                                    }
+                                    if (ph == 1) { // the chain goes on at q: the mask's bit 0 is sample q (q - sp0s < 128: eight symbols at most)
+                                        int d = q - sp0s;
+                                        if (d >= 64) {
+                                            cm[0] = cm[1];
+                                            cm[1] = cm[2];
+                                            cm[2] = 0ull;
+                                            d -= 64;
+                                        }
+                                        cm[0] = (cm[0] >> d) | ((cm[1] << 1) << (63 - d));
+                                        cm[1] = (cm[1] >> d) | ((cm[2] << 1) << (63 - d));
+                                        cm[2] >>= d;
+                                    }
+                                    DBG_B2(1, 8);
+                                    // one symbol per round, on scalars; it ends at the symbol limit or in front of a symbol that does not
+                                    // fit the tile (`full`)
+                                    while (true) {
                                         const int c = (int)((i0tab >> (2 * (jit + 1))) & 3u), i0 = c - 1;
-                                        const int cnt = whole - i0;
-                                        if (q + cnt > tn) {
-                                            full = true;
+                                        const int cnt = whole - i0, qn = q + cnt;
+                                        if (sm >= lim || qn > tn) {
                                             break;
                                         }
                                         asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(mypk) : "s"((q + 256) | (c << 10) | ((jit + 1) << 12)), "s"(ow * OW + sm) : "m0");
-                                        const int k0 = i0 < 0 ? 1 : 0; // a crossing at symbol index -1 latches nothing
-                                        const uint32_t wv = (uint32_t)(cm[0] >> k0) & ((1u << (cnt - k0)) - 1u);
-                                        jit = wv ? i0 + k0 + (__ffs((int)wv) - 1) : -1;
+                                        // the symbol's samples are indices i0 .. of the symbol; a crossing at index -1 latches nothing
+                                        const uint32_t wv = (uint32_t)cm[0] & ((1u << cnt) - 1u) & ~((uint32_t)i0 >> 31);
+                                        jit = wv ? i0 + (__ffs((int)wv) - 1) : -1;
                                         cm[0] = (cm[0] >> cnt) | (cm[1] << (64 - cnt));
                                         cm[1] = (cm[1] >> cnt) | (cm[2] << (64 - cnt));
                                         cm[2] >>= cnt;
-                                        q += cnt;
+                                        q = qn;
                                         sm++;
                                     }
+                                    const bool full = sm < lim;
+                                    DBG_B(1);
                                     if (full || lim >= CAP) {
                                         break;
                                     }
@@ -2437,6 +2465,10 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                             int lim = __shfl(s.hist_count, g);
                             lim = lim < 8 ? 8 - lim : CAP;
                             bool gdone = !gact; // this row's chain has ended
+                            if (DDN_RX_CYCLES && (cfg.dbg & 8192)) {
+                                dbg_b[9]++;
+                            }
+                            DBG_B(0);
                             for (int ph = 0; ph < 2; ph++) {
                                 unsigned long long cm0 = 0ull, cm1 = 0ull, cm2 = 0ull;
                                 constexpr int PW = 64 / OW; // ballots per 64-bit word
@@ -2458,6 +2490,7 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                                     cm1 = wd == 1 ? word : cm1;
                                     cm2 = wd == 2 ? word : cm2;
                                 }
+                                DBG_B2(1, 8);
                                 bool full = false;
                                 while (true) {
                                     const bool go = !gdone && !full && m < lim;
@@ -2484,6 +2517,7 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                                         }
                                     }
                                 }
+                                DBG_B(1);
                                 if (ph == 1) {
                                     break;
                                 }
@@ -2509,7 +2543,11 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                         const int myq = (mypk & 1023) - 256, myi0 = ((mypk >> 10) & 3) - 1, myjin = ((mypk >> 12) & 15) - 1;
                         const int c0 = __shfl(s.hist_count, g);
                         const uint32_t h0 = (uint32_t)__shfl((int)s.hist_bits, g);
+                        const int o_o = __shfl(o, g);
+                        const int sh_o = __shfl(s.shead, g), li_o = __shfl(s.lidx, g), si_o = __shfl(s.sidx, g);
                         float sym = 0.0f;
+                        // (the sample in front of this lane's start: the owner's last sample if the pass ends here - lane 0 is no such end)
+                        const float lsp = (gact && l > 0 && l <= m) ? pr[myq - 1] : 0.0f;
                         if (gact && l < m) {
                             const float* pw = pr + myq + ((whole - 1) / 2 - 2 - myi0);
                             float acc = 0.0f;
@@ -2527,8 +2565,7 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                         if (smg) {
                             m = __ffs((int)smg) - 1;
                         }
-                        const int o_o = __shfl(o, g);
-                        const int sh_o = __shfl(s.shead, g), li_o = __shfl(s.lidx, g), si_o = __shfl(s.sidx, g);
+                        DBG_B(2);
                         if (gact && l < m) { // symbol history, level window, extrema window, record
                             int k = sh_o + l;
                             L.sh[k >= 24 ? k - 24 : k][cln] = sym;
@@ -2541,6 +2578,7 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                                 store_record(rec + (cho * max_sym + oo) * 10, flags + cho * max_sym + oo, sym, sym > 0.0f ? 1 : 3, 0, 0, 0, 0);
                             }
                         }
+                        DBG_B(3);
                         float a1 = (gact && l < m) ? sym : inf, a2 = inf, b1 = (gact && l < m) ? sym : -inf, b2 = -inf;
                         // (a pass is at most 16 symbols: lanes 0 .. 15 of the row = one DPP row; quad swaps, then the row rotated by 4 and
                         // by 8 - every step joins disjoint sets of lanes, so no value is counted twice)
@@ -2555,34 +2593,46 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
         two_max_insert(p1, b1, b2);                                                                                                         \
         two_max_insert(p2, b1, b2);                                                                                                         \
     } while (0)
-                        DDN_ROW_STEP(0xB1);  // quad_perm [1,0,3,2]
+                        { // quad_perm [1,0,3,2]: every lane's second values are still +inf / -inf, and inserting those changes nothing
+                            const float o1 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a1), 0xB1, 0xF, 0xF, true));
+                            const float p1 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(b1), 0xB1, 0xF, 0xF, true));
+                            two_min_insert(o1, a1, a2);
+                            two_max_insert(p1, b1, b2);
+                        }
                         DDN_ROW_STEP(0x4E);  // quad_perm [2,3,0,1]
                         DDN_ROW_STEP(0x124); // row_ror:4
                         DDN_ROW_STEP(0x128); // row_ror:8
 #undef DDN_ROW_STEP
-                        // the owner lanes (lane = channel of this wave) read their row's results
-                        const int orow = (lane < LPR ? lane : 0) * OW;
-                        const int m_own = __shfl(m, orow);
-                        const int src1 = orow + (m_own > 0 ? m_own - 1 : 0);
-                        const int qf = __shfl(myq, orow + m_own), jf = __shfl(myjin, orow + m_own);
-                        const int il = __shfl(myi0, src1);
-                        const uint32_t hf = (uint32_t)__shfl((int)hj, src1);
-                        a1 = __shfl(a1, orow), a2 = __shfl(a2, orow), b1 = __shfl(b1, orow), b2 = __shfl(b2, orow);
+                        DBG_B(4);
+                        // the owner lanes (lane = channel of this wave) take their row's results: the lanes that hold them push them there
+                        // (ds_permute) - one trip through the crossbar, where fetching them (the count first, then the words of lanes
+                        // m and m - 1) takes two and the sample in front of the next symbol a third.  Every other lane pushes to lane
+                        // 63, which is no owner's.
+                        const int l1 = m > 0 ? m - 1 : 0;
+                        const int tm = ((gact && l == m) ? g : 63) * 4, t1 = ((gact && l == l1) ? g : 63) * 4, t0 = ((gact && l == 0) ? g : 63) * 4;
+                        const int pkf = __builtin_amdgcn_ds_permute(tm, mypk);
+                        const float lsf = __int_as_float(__builtin_amdgcn_ds_permute(tm, __float_as_int(lsp)));
+                        const int il = __builtin_amdgcn_ds_permute(t1, myi0);
+                        const uint32_t hf = (uint32_t)__builtin_amdgcn_ds_permute(t1, (int)hj);
+                        const int m_own = __builtin_amdgcn_ds_permute(t0, m);
+                        a1 = __int_as_float(__builtin_amdgcn_ds_permute(t0, __float_as_int(a1)));
+                        a2 = __int_as_float(__builtin_amdgcn_ds_permute(t0, __float_as_int(a2)));
+                        b1 = __int_as_float(__builtin_amdgcn_ds_permute(t0, __float_as_int(b1)));
+                        b2 = __int_as_float(__builtin_amdgcn_ds_permute(t0, __float_as_int(b2)));
+                        const int qf = (pkf & 1023) - 256, jf = ((pkf >> 12) & 15) - 1;
                         if (lane < LPR && (be & fitsn)) {
                             if (m_own == 0) { // the next symbol completes a sync: the standard trip's
                                 blk_o = o;
                             } else {
-                                const float* prow = (s.filter_on ? &L.flt[ln][0] : &L.raw[ln][0]) + base;
-                                const float lsf = prow[qf - 1];
                                 two_min_insert(a1, pc1, pc2);
                                 two_min_insert(a2, pc1, pc2);
                                 two_max_insert(b1, pc3, pc4);
                                 two_max_insert(b2, pc3, pc4);
                                 npc += m_own;
                                 wabs = fmaxf(wabs, fmaxf(fabsf(a1), fabsf(b1))); // the pass's smallest and largest symbol
-                                s.shead = (s.shead + m_own) % 24;
+                                s.shead = s.shead + m_own >= 24 ? s.shead + m_own - 24 : s.shead + m_own; // (m_own <= 16)
                                 s.scount = s.scount + m_own < 24 ? s.scount + m_own : 24;
-                                s.lidx = (s.lidx + m_own) % 24;
+                                s.lidx = s.lidx + m_own >= 24 ? s.lidx + m_own - 24 : s.lidx + m_own;
                                 s.level_count = s.level_count + m_own < 24 ? s.level_count + m_own : 24;
                                 s.sidx = (s.sidx + m_own) & (SS - 1);
                                 s.hist_bits = hf;
@@ -2604,7 +2654,11 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                                 o += m_own;
                             }
                         }
+                        DBG_B(5);
                         if (DDN_RX_CYCLES && (cfg.dbg & 8192)) { // the pass is no trip: its cycles are kept apart
+                            for (int j = 0; j < LPR; j++) {
+                                dbg_b[6] += ((bm >> j) & 1ull) ? __builtin_amdgcn_readlane(m_own, j) : 0;
+                            }
                             const long long now = (long long)clock64();
                             dbg_sec[6] += now - bt0;
                             dbg_sec[7]++;
@@ -3481,11 +3535,20 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
             d[k] = reinterpret_cast<const uint8_t*>(v)[k];
         }
         if (wave == 0) { // the recurrence wave's standard-trip sections, one block further down; its lean-run figures, another one
+            long long dbg_blk2[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // {the crossing masks' part of dbg_blk[1], passes of several owners}
+            if constexpr (LPR == 2 || LPR == 4) {
+                for (int k = 0; k < 8; k++) {
+                    dbg_blk[k] = dbg_b[k];
+                }
+                dbg_blk2[0] = dbg_b[8];
+                dbg_blk2[1] = dbg_b[9];
+            }
             uint8_t* d2 = rec + ((size_t)ch0 + 1) * max_sym * 10 - 256;
             for (int k = 0; k < 64; k++) {
                 d2[k] = reinterpret_cast<const uint8_t*>(dbg_sec)[k];
                 d2[k - 64] = reinterpret_cast<const uint8_t*>(dbg_run)[k];
                 d2[k - 128] = reinterpret_cast<const uint8_t*>(dbg_blk)[k];
+                d2[k - 320] = reinterpret_cast<const uint8_t*>(dbg_blk2)[k];
                 d2[k - 256] = reinterpret_cast<const uint8_t*>(dbg_ent)[k];
             }
         }

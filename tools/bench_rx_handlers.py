@@ -108,6 +108,10 @@ for mode, cpw in [(m, int(c)) for m, c in (x.split(":") for x in os.environ.get(
         blk = np.stack([r[c, -384:-320] for c in range(0, B, cpw)]).copy().view(np.int64).sum(axis=0)
         extra += "\n   bulk pass per owner lane (%.2f owners per pass, %.1f symbols each): set-up %.0f masks + slip chain %.0f means + sync test %.0f stores %.0f window reduction %.0f owner's words %.0f cycles" % (
             (blk[7] / max(1, sec[:, 7].sum()), blk[6] / max(1, blk[7])) + tuple(blk[k] / max(1, blk[7]) for k in range(6)))
+        blk2 = np.stack([r[c, -576:-512] for c in range(0, B, cpw)]).copy().view(np.int64).sum(axis=0)
+        if blk2[0] > 0:    # two / four lanes per recurrence wave: the middle part split, and how many passes had several owners
+            extra += "\n   of that, masks %.0f slip chain %.0f cycles; %.2f of the passes had several owners" % (
+                blk2[0] / max(1, blk[7]), (blk[1] - blk2[0]) / max(1, blk[7]), blk2[1] / max(1, sec[:, 7].sum()))
         run = np.stack([r[c, -320:-256] for c in range(0, B, cpw)]).copy().view(np.int64).sum(axis=0)
         extra += "\n   lean runs: %.2f per tile, %.2f trips and %.2f phases each (%.2f of them polling a handler mailbox), %.0f cycles inside the run per trip" % (
             run[0] / (len(sec) * tiles), run[1] / max(1, run[0]), run[7] / max(1, run[0]), run[5] / max(1, run[0]), run[6] / max(1, run[1]))
