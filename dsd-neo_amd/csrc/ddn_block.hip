@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include <stdlib.h>
+#include "ddn_bcode_dev.h"
 #include "ddn_crc_dev.h"
 #include "ddn_device.h"
 #include "ddn_nid_dev.h"
@@ -113,26 +114,11 @@ k_hamming_10_6_3(uint8_t* __restrict__ bits10, int n, uint8_t* __restrict__ errs
         errs[c] = 2;
         return;
     }
-    const int masks[4] = {0x398, 0x354, 0x2E2, 0x1E1};
-    int syn = 0;
-    for (int k = 0; k < 4; k++) {
-        syn = (syn << 1) | (__popc((unsigned)(word & masks[k])) & 1);
-    }
-    int e = 0;
-    if (syn) {
-        // syndrome -> bit index (0..3 parity bits, 4..9 data bits), -1 = uncorrectable
-        const int8_t bad_bit[16] = {-2, 0, 1, 5, 2, -1, -1, 6, 3, -1, -1, 7, 4, 8, 9, -1};
-        const int bb = bad_bit[syn];
-        if (bb < 0) {
-            e = 2;
-        } else {
-            e = 1;
-            if (bb >= 4) {
-                word ^= 1 << bb;
-            }
-            for (int i = 0; i < 6; i++) {
-                b[i] = (uint8_t)((word >> (9 - i)) & 1);
-            }
+    uint32_t fixed;
+    const int e = ddn_bcode::hamming_10_6_3_hard((uint32_t)word, &fixed);
+    if (e == 1) {
+        for (int i = 0; i < 6; i++) {
+            b[i] = (uint8_t)((fixed >> (9 - i)) & 1);
         }
     }
     errs[c] = (uint8_t)e;

@@ -5,11 +5,12 @@
 // 4 x 36 TCH behind the 12-symbol sync), the CCH decode :139-178 (descramble x^9 + x^5 + 1 seeded 0x1FF per CCH, dpmr_data.c:80-117;
 // 6 x 12 de-interleave :431-452; six Hamming(12,8) words; CRC7 over 41 bits :455-474), dpmr_extract_superframe_part() /
 // dpmr_update_superframe_part() :180-274, dpmr_play_voice_frames() :354-395; dpmr_read_dibit() :67-73 (dibit ^ 2 under -xd).
-// Hamming(12,8) uses ddn_fec3.hip's parity-check matrix and correction table, so the decode stays pinned with the generic entry.
+// Hamming(12,8) is ddn_bcode_dev.h's, the code of the generic entry (ddn_fec3.hip), so the decode stays pinned with it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "ddn_api_util.h"
+#include "ddn_bcode_dev.h"
 #include "ddn_crc_dev.h"
 #include "ddn_device.h"
 #include "ddn_fec3.h"
@@ -17,7 +18,6 @@
 #include "ddn_internal.h"
 #include "ddn_tables_ambe.h"
 #include "ddn_tables_dpmr.h"
-#include "ddn_tables_fec3.h"
 
 namespace {
 
@@ -49,7 +49,7 @@ value_of(const uint8_t* b, int n) { // MSB first
 
 // one CCH: 36 dibits -> 48 decoded bits, per-word Hamming status, CRC7 status
 __device__ void
-decode_cch(const uint8_t* dib36, const uint8_t* h128, uint8_t* b48, uint8_t* ham6, uint8_t* crc_ok) {
+decode_cch(const uint8_t* dib36, uint8_t* b48, uint8_t* ham6, uint8_t* crc_ok) {
     uint8_t m[72], s[72];
     scramble_mask(m);
     for (int i = 0; i < 36; i++) {
@@ -61,20 +61,7 @@ decode_cch(const uint8_t* dib36, const uint8_t* h128, uint8_t* b48, uint8_t* ham
         for (int j = 0; j < 12; j++) {
             word |= (uint32_t)s[j * 6 + w] << j;
         }
-        int syn = 0;
-        for (int r = 0; r < 4; r++) {
-            syn |= (__popc(word & ddn_hamming_12_8_H[r]) & 1) << (3 - r);
-        }
-        bool ok = true;
-        if (syn > 0) {
-            const uint8_t p = h128[syn];
-            if (p == 0xFF) {
-                ok = false;
-            } else {
-                word ^= 1u << p;
-            }
-        }
-        ham6[w] = ok ? 1 : 0;
+        ham6[w] = ddn_bcode::decode(ddn_bcode::HAMMING_12_8, word) ? 1 : 0;
         for (int j = 0; j < 8; j++) {
             b48[w * 8 + j] = (uint8_t)((word >> j) & 1u);
         }
@@ -86,7 +73,7 @@ decode_cch(const uint8_t* dib36, const uint8_t* h128, uint8_t* b48, uint8_t* ham
 // writes.  A slot without a whole superframe in the call's records (or past the sync list) is written as zeros, colour -1.
 __global__ __launch_bounds__(64) void
 k_dpmr_superframe(const uint8_t* __restrict__ rec, size_t stride, const int32_t* __restrict__ counts, const int32_t* __restrict__ sync_pos,
-                  const int32_t* __restrict__ n_sync, int max_syncs, int inverted, const DdnFec3Tables* __restrict__ T,
+                  const int32_t* __restrict__ n_sync, int max_syncs, int inverted,
                   uint8_t* __restrict__ bits96, uint8_t* __restrict__ ham12, uint8_t* __restrict__ crc2, int32_t* __restrict__ fields16,
                   int32_t* __restrict__ id, int32_t* __restrict__ color, uint8_t* __restrict__ valid) {
     __shared__ uint8_t d[kFrame], b[2][48], hm[2][6], cr[2];
@@ -104,7 +91,7 @@ k_dpmr_superframe(const uint8_t* __restrict__ rec, size_t stride, const int32_t*
     }
     __syncthreads();
     if (ok && t < 2) {
-        decode_cch(d + kCch[t], T->h128, b[t], hm[t], &cr[t]);
+        decode_cch(d + kCch[t], b[t], hm[t], &cr[t]);
     } else if (ok && t == 2) {
         uint8_t cc[24];
         for (int i = 0; i < 12; i++) {
@@ -291,10 +278,8 @@ ddn_dpmr_superframe_decode_batch(const uint8_t* d_records10, size_t stride_symbo
         return DDN_EINVAL;
     }
     hipStream_t st = (hipStream_t)hip_stream;
-    const DdnFec3Tables* T = nullptr;
-    DDN_LAUNCH_TRY(ddn_dev_fec3_tables(&T, st));
     hipLaunchKernelGGL(k_dpmr_superframe, dim3((unsigned)max_syncs, (unsigned)n_channels), dim3(64), 0, st, d_records10, stride_symbols,
-                       d_counts, d_sync_pos, d_n_sync, (int)max_syncs, inverted, T, d_cch_bits2x48, d_ham_ok2x6, d_crc_ok2, d_fields2x8, d_id,
+                       d_counts, d_sync_pos, d_n_sync, (int)max_syncs, inverted, d_cch_bits2x48, d_ham_ok2x6, d_crc_ok2, d_fields2x8, d_id,
                        d_color, d_valid);
     DDN_LAUNCH_TRY(hipGetLastError());
     return DDN_OK;

@@ -7,291 +7,80 @@
 // r = 1..255, Forney).  Callers: src/protocol/dmr/dmr_dburst.c:500-530 and friends, src/protocol/nxdn/*.
 //
 // All integer work, one item per lane: a code word is packed into a 32-bit register (bit j = rxBits[j]), the syndrome is
-// r parities popc(word & row mask), the correction a table lookup.  The tables are built once per device by the host with
-// the reference's own assignment order (its init loops overwrite single slots of an entry, so for the distance-6 codes
-// the survivor of colliding patterns depends on that order - reproduced, including the quirks noted at each decoder).
+// r parities popc(word & row mask), the correction a table lookup: the codes, their compile-time tables and their acceptance
+// rules are ddn_bcode_dev.h's.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cstring>
-#include <mutex>
-#include <vector>
-
+#include "ddn_bcode_dev.h"
 #include "ddn_device.h"
 #include "ddn_fec3.h"
-#include "ddn_tables_fec3.h"
 #include "ddn_tables_bptc.h"
 
 namespace {
 
-using Tables = DdnFec3Tables;
-
-int
-syn_of(uint32_t w, const uint32_t* H, int r) {
-    int s = 0;
-    for (int i = 0; i < r; i++) {
-        s |= (__builtin_popcount(w & H[i]) & 1) << (r - 1 - i);
-    }
-    return s;
-}
-
-void
-build_hamming(uint8_t* tab, int size, const uint32_t* H, int n, int r) {
-    // correctable positions = the columns of H (explicit assignments of Hamming_*_init(), fec.c:133-143,183-198,...)
-    memset(tab, 0xFF, (size_t)size);
-    for (int p = 0; p < n; p++) {
-        tab[syn_of(1u << p, H, r)] = (uint8_t)p;
-    }
-}
-
-// Golay_20_8_init / Golay_24_12_init (fec.c:437-512, 566-640): kd message bits, 12 parity bits, slot-wise assignments in
-// the reference's loop order
-void
-build_golay(uint8_t (*tab)[3], const uint32_t* H, int kd) {
-    memset(tab, 0xFF, 4096 * 3);
-    auto S = [&](uint32_t w) { return syn_of(w, H, 12); };
-    auto P = [&](int ip) { return 1 << (11 - ip); };
-    for (int i1 = 0; i1 < kd; i1++) {
-        for (int i2 = i1 + 1; i2 < kd; i2++) {
-            for (int i3 = i2 + 1; i3 < kd; i3++) {
-                const int s = S((1u << i1) | (1u << i2) | (1u << i3));
-                tab[s][0] = (uint8_t)i1, tab[s][1] = (uint8_t)i2, tab[s][2] = (uint8_t)i3;
-            }
-            const int s = S((1u << i1) | (1u << i2));
-            tab[s][0] = (uint8_t)i1, tab[s][1] = (uint8_t)i2;
-            for (int ip = 0; ip < 12; ip++) {
-                const int sp = s ^ P(ip);
-                tab[sp][0] = (uint8_t)i1, tab[sp][1] = (uint8_t)i2, tab[sp][2] = (uint8_t)(kd + ip);
-            }
-        }
-        const int s = S(1u << i1);
-        tab[s][0] = (uint8_t)i1;
-        for (int ip1 = 0; ip1 < 12; ip1++) {
-            const int s1 = s ^ P(ip1);
-            tab[s1][0] = (uint8_t)i1, tab[s1][1] = (uint8_t)(kd + ip1);
-            for (int ip2 = ip1 + 1; ip2 < 12; ip2++) {
-                const int s2 = s1 ^ P(ip2);
-                tab[s2][0] = (uint8_t)i1, tab[s2][1] = (uint8_t)(kd + ip1), tab[s2][2] = (uint8_t)(kd + ip2);
-            }
-        }
-    }
-    for (int ip1 = 0; ip1 < 12; ip1++) {
-        const int s1 = P(ip1);
-        tab[s1][0] = (uint8_t)(kd + ip1);
-        for (int ip2 = ip1 + 1; ip2 < 12; ip2++) {
-            const int s2 = s1 ^ P(ip2);
-            tab[s2][0] = (uint8_t)(kd + ip1), tab[s2][1] = (uint8_t)(kd + ip2);
-            for (int ip3 = ip2 + 1; ip3 < 12; ip3++) {
-                const int s3 = s2 ^ P(ip3);
-                tab[s3][0] = (uint8_t)(kd + ip1), tab[s3][1] = (uint8_t)(kd + ip2), tab[s3][2] = (uint8_t)(kd + ip3);
-            }
-        }
-    }
-}
-
-// QR_16_7_6_init (fec.c:744-780): 7 message bits, 9 parity bits, up to two positions
-void
-build_qr(uint8_t (*tab)[2], const uint32_t* H) {
-    memset(tab, 0xFF, 512 * 2);
-    auto S = [&](uint32_t w) { return syn_of(w, H, 9); };
-    auto P = [&](int ip) { return 1 << (8 - ip); };
-    for (int i1 = 0; i1 < 7; i1++) {
-        for (int i2 = i1 + 1; i2 < 7; i2++) {
-            const int s = S((1u << i1) | (1u << i2));
-            tab[s][0] = (uint8_t)i1, tab[s][1] = (uint8_t)i2;
-        }
-        const int s = S(1u << i1);
-        tab[s][0] = (uint8_t)i1;
-        for (int ip = 0; ip < 9; ip++) {
-            const int sp = s ^ P(ip);
-            tab[sp][0] = (uint8_t)i1, tab[sp][1] = (uint8_t)(7 + ip);
-        }
-    }
-    for (int ip1 = 0; ip1 < 9; ip1++) {
-        const int s1 = P(ip1);
-        tab[s1][0] = (uint8_t)(7 + ip1);
-        for (int ip2 = ip1 + 1; ip2 < 9; ip2++) {
-            const int s2 = s1 ^ P(ip2);
-            tab[s2][0] = (uint8_t)(7 + ip1), tab[s2][1] = (uint8_t)(7 + ip2);
-        }
-    }
-}
-
-hipError_t
-device_tables(const Tables** out, hipStream_t st) {
-    static std::mutex mu;
-    static Tables* dev_tabs[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) {
-        return e;
-    }
-    if (dev < 0 || dev >= 64) {
-        return hipErrorInvalidDevice;
-    }
-    std::lock_guard<std::mutex> lock(mu);
-    if (!dev_tabs[dev]) {
-        std::vector<Tables> h(1);
-        build_hamming(h[0].h74, 8, ddn_hamming_7_4_H, 7, 3);
-        build_hamming(h[0].h128, 16, ddn_hamming_12_8_H, 12, 4);
-        build_hamming(h[0].h139, 16, ddn_hamming_13_9_H, 13, 4);
-        build_hamming(h[0].h1511, 16, ddn_hamming_15_11_H, 15, 4);
-        build_hamming(h[0].h16114, 32, ddn_hamming_16_11_4_H, 16, 5);
-        build_golay(h[0].g208, ddn_golay_20_8_H, 8);
-        build_golay(h[0].g2412, ddn_golay_24_12_H, 12);
-        build_qr(h[0].qr, ddn_qr_16_7_6_H);
-        Tables* d = nullptr;
-        e = hipMalloc(&d, sizeof(Tables));
-        if (e != hipSuccess) {
-            return e;
-        }
-        e = hipMemcpyAsync(d, h.data(), sizeof(Tables), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            e = hipStreamSynchronize(st);
-        }
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            return e;
-        }
-        dev_tabs[dev] = d;
-    }
-    *out = dev_tabs[dev];
-    return hipSuccess;
-}
-
-template <int R>
-__device__ __forceinline__ int
-syndrome(uint32_t w, const uint32_t (&H)[R]) {
-    int s = 0;
-#pragma unroll
-    for (int i = 0; i < R; i++) {
-        s |= (__popc(w & H[i]) & 1) << (R - 1 - i);
-    }
-    return s;
-}
-
-__device__ __forceinline__ uint32_t
-pack(const uint8_t* b, int n) {
-    uint32_t w = 0;
-    for (int j = 0; j < n; j++) {
-        w |= (uint32_t)(b[j] & 1u) << j;
-    }
-    return w;
-}
+namespace bc = ddn_bcode;
 
 // ---- Hamming family -------------------------------------------------------------------------------------------------
 // One item = one call of the reference with nb code words.  Reproduced quirks: the corrected position is applied to
 // rxBits[pos] WITHOUT the code word's offset (fec.c:225, 283, 342, ...: rxBits[m_corr[s]] ^= 1), i.e. always inside the
 // first code word of the call; (12,8) keeps going after an uncorrectable word, the others stop at it (no further copies).
-template <int N, int K, int R, bool BREAKS>
+template <bool BREAKS, class C>
 __device__ __forceinline__ bool
-hamming_item(uint8_t* rx, uint8_t* dec, int nb, const uint32_t (&H)[R], const uint8_t* corr) {
+hamming_item(C c, uint8_t* bits, uint8_t* decoded, size_t i, int nb) {
+    uint8_t* rx = bits + i * C::n * nb;
+    uint8_t* dec = decoded ? decoded + i * C::k * nb : nullptr;
     bool ok = true;
     for (int ic = 0; ic < nb; ic++) {
-        const int s = syndrome<R>(pack(rx + N * ic, N), H);
-        if (s > 0) {
-            const uint8_t p = corr[s];
-            if (p == 0xFF) {
-                ok = false;
-                if (BREAKS) {
-                    break;
-                }
-            } else {
-                rx[p] ^= 1;
+        const int p = bc::position(c, bc::pack_u8(rx + C::n * ic, C::n));
+        if (p == bc::NONE) {
+            ok = false;
+            if (BREAKS) {
+                break;
             }
+        } else if (p >= 0) {
+            rx[p] ^= 1;
         }
         if (dec) {
-            for (int j = 0; j < K; j++) {
-                dec[K * ic + j] = rx[N * ic + j];
+            for (int j = 0; j < C::k; j++) {
+                dec[C::k * ic + j] = rx[C::n * ic + j];
             }
         }
     }
     return ok;
 }
 
+// one code word, one bit per byte, decoded in place: the bytes at the flipped positions change, whether accepted or not
+template <class C>
+__device__ __forceinline__ bool
+word_item(C c, uint8_t* rx) {
+    const uint32_t w0 = bc::pack_u8(rx, C::n);
+    uint32_t w = w0;
+    const bool ok = bc::decode(c, w);
+    for (uint32_t d = w ^ w0; d; d &= d - 1) {
+        rx[__ffs(d) - 1] ^= 1;
+    }
+    return ok;
+}
+
 __global__ __launch_bounds__(256) void
 k_block_code(int code, uint8_t* __restrict__ bits, size_t n_items, int nb, uint8_t* __restrict__ decoded,
-             uint8_t* __restrict__ okv, const Tables* __restrict__ T) {
+             uint8_t* __restrict__ okv) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_items) {
         return;
     }
     bool ok = true;
     switch (code) {
-        case DDN_CODE_HAMMING_7_4: {
-            uint8_t* rx = bits + i * 7;
-            const int s = syndrome<3>(pack(rx, 7), ddn_hamming_7_4_H);
-            if (s > 0) {
-                const uint8_t p = T->h74[s];
-                if (p == 0xFF) {
-                    ok = false;
-                } else {
-                    rx[p] ^= 1;
-                }
-            }
-            break;
-        }
-        case DDN_CODE_HAMMING_12_8:
-            ok = hamming_item<12, 8, 4, false>(bits + i * 12 * nb, decoded ? decoded + i * 8 * nb : nullptr, nb, ddn_hamming_12_8_H, T->h128);
-            break;
-        case DDN_CODE_HAMMING_13_9:
-            ok = hamming_item<13, 9, 4, true>(bits + i * 13 * nb, decoded ? decoded + i * 9 * nb : nullptr, nb, ddn_hamming_13_9_H, T->h139);
-            break;
-        case DDN_CODE_HAMMING_15_11:
-            ok = hamming_item<15, 11, 4, true>(bits + i * 15 * nb, decoded ? decoded + i * 11 * nb : nullptr, nb, ddn_hamming_15_11_H, T->h1511);
-            break;
-        case DDN_CODE_HAMMING_16_11_4:
-            ok = hamming_item<16, 11, 5, true>(bits + i * 16 * nb, decoded ? decoded + i * 11 * nb : nullptr, nb, ddn_hamming_16_11_4_H, T->h16114);
-            break;
-        case DDN_CODE_GOLAY_20_8: { // fec.c:514-561: flips applied even when the tally then exceeds two
-            uint8_t* rx = bits + i * 20;
-            const int s = syndrome<12>(pack(rx, 20), ddn_golay_20_8_H);
-            if (s > 0) {
-                int k = 0;
-                for (; k < 3; k++) {
-                    const uint8_t p = T->g208[s][k];
-                    if (p == 0xFF) {
-                        break;
-                    }
-                    rx[p] ^= 1;
-                }
-                ok = !(k == 0 || k > 2);
-            }
-            break;
-        }
-        case DDN_CODE_GOLAY_24_12: { // fec.c:656-690
-            uint8_t* rx = bits + i * 24;
-            const int s = syndrome<12>(pack(rx, 24), ddn_golay_24_12_H);
-            if (s > 0) {
-                int k = 0;
-                for (; k < 3; k++) {
-                    const uint8_t p = T->g2412[s][k];
-                    if (p == 0xFF) {
-                        break;
-                    }
-                    rx[p] ^= 1;
-                }
-                ok = k != 0;
-            }
-            break;
-        }
-        default: { // DDN_CODE_QR_16_7_6, fec.c:782-822
-            uint8_t* rx = bits + i * 16;
-            const int s = syndrome<9>(pack(rx, 16), ddn_qr_16_7_6_H);
-            if (s > 0) {
-                int k = 0;
-                for (; k < 2; k++) {
-                    const uint8_t p = T->qr[s][k];
-                    if (p == 0xFF) {
-                        break;
-                    }
-                    rx[p] ^= 1;
-                }
-                ok = k != 0;
-            }
-            break;
-        }
+        case DDN_CODE_HAMMING_7_4: ok = word_item(bc::HAMMING_7_4, bits + i * 7); break;
+        case DDN_CODE_HAMMING_12_8: ok = hamming_item<false>(bc::HAMMING_12_8, bits, decoded, i, nb); break;
+        case DDN_CODE_HAMMING_13_9: ok = hamming_item<true>(bc::HAMMING_13_9, bits, decoded, i, nb); break;
+        case DDN_CODE_HAMMING_15_11: ok = hamming_item<true>(bc::HAMMING_15_11, bits, decoded, i, nb); break;
+        case DDN_CODE_HAMMING_16_11_4: ok = hamming_item<true>(bc::HAMMING_16_11_4, bits, decoded, i, nb); break;
+        case DDN_CODE_GOLAY_20_8: ok = word_item(bc::GOLAY_20_8, bits + i * 20); break;
+        case DDN_CODE_GOLAY_24_12: ok = word_item(bc::GOLAY_24_12, bits + i * 24); break;
+        default: ok = word_item(bc::QR_16_7_6, bits + i * 16); break; // DDN_CODE_QR_16_7_6
     }
     if (okv) {
         okv[i] = ok ? 1 : 0;
@@ -304,7 +93,7 @@ k_block_code(int code, uint8_t* __restrict__ bits, size_t n_items, int nb, uint8
 // column 0 the reference reads an uninitialised array - zeros here); Hamming(15,11) is perfect and never fails.
 __global__ __launch_bounds__(128) void
 k_bptc_196x96(const uint8_t* __restrict__ in, int deinterleave, size_t n, uint8_t* __restrict__ out96,
-              uint8_t* __restrict__ r3, uint32_t* __restrict__ errs, const Tables* __restrict__ T) {
+              uint8_t* __restrict__ r3, uint32_t* __restrict__ errs) {
     const size_t i = (size_t)blockIdx.x * 128 + threadIdx.x;
     if (i >= n) {
         return;
@@ -322,17 +111,18 @@ k_bptc_196x96(const uint8_t* __restrict__ in, int deinterleave, size_t n, uint8_
         row[r] = w;
     }
     uint32_t bad = 0;
+    // (the tables are constants the compiler sees through: left to itself it lays both passes out flat and wants 210 registers, two
+    // waves per SIMD; with these two loops kept it stays at eight)
+#pragma nounroll
     for (int pass = 0; pass < 2; pass++) {
         uint32_t e = 0;
+#pragma nounroll
         for (int r = 0; r < 9; r++) { // rows 0..8 only (bptc.c:76)
-            const int s = syndrome<4>(row[r], ddn_hamming_15_11_H);
-            if (s > 0) {
-                const uint8_t p = T->h1511[s];
-                if (p == 0xFF) {
-                    e++;
-                } else if (p < 11) { // only the eleven information bits are written back (bptc.c:84-86)
-                    row[r] ^= 1u << p;
-                }
+            const int p = bc::position(bc::HAMMING_15_11, row[r]);
+            if (p == bc::NONE) {
+                e++;
+            } else if (p >= 0 && p < 11) { // only the eleven information bits are written back (bptc.c:84-86)
+                row[r] ^= 1u << p;
             }
         }
         uint32_t prev = 0; // the nine corrected bits of the previous column
@@ -341,17 +131,8 @@ k_bptc_196x96(const uint8_t* __restrict__ in, int deinterleave, size_t n, uint8_
             for (int r = 0; r < 13; r++) {
                 col |= ((row[r] >> c) & 1u) << r;
             }
-            const int s = syndrome<4>(col, ddn_hamming_13_9_H);
-            bool okc = true;
-            if (s > 0) {
-                const uint8_t p = T->h139[s];
-                if (p == 0xFF) {
-                    okc = false;
-                    e++;
-                } else {
-                    col ^= 1u << p;
-                }
-            }
+            const bool okc = bc::decode(bc::HAMMING_13_9, col);
+            e += okc ? 0 : 1;
             const uint32_t nine = okc ? (col & 0x1FFu) : prev;
             prev = nine;
             for (int r = 0; r < 9; r++) {
@@ -525,13 +306,8 @@ ddn_dev_block_code(int code, uint8_t* bits, size_t n_items, int nb, uint8_t* dec
     if (n_items == 0) {
         return hipSuccess;
     }
-    const Tables* T = nullptr;
-    hipError_t e = device_tables(&T, st);
-    if (e != hipSuccess) {
-        return e;
-    }
     hipLaunchKernelGGL(k_block_code, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st, code, bits, n_items, nb,
-                       decoded, ok, T);
+                       decoded, ok);
     return hipGetLastError();
 }
 
@@ -541,13 +317,8 @@ ddn_dev_bptc_196x96(const uint8_t* in, int deinterleave, size_t n, uint8_t* out9
     if (n == 0) {
         return hipSuccess;
     }
-    const Tables* T = nullptr;
-    hipError_t e = device_tables(&T, st);
-    if (e != hipSuccess) {
-        return e;
-    }
     hipLaunchKernelGGL(k_bptc_196x96, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, in, deinterleave, n, out96, r3,
-                       errs, T);
+                       errs);
     return hipGetLastError();
 }
 
@@ -560,8 +331,7 @@ ddn_dev_bptc_196x96(const uint8_t* in, int deinterleave, size_t n, uint8_t* out9
 __constant__ uint8_t c_bptc_rc_perm[32] = DDN_BPTC_RC_PERM_INIT;
 
 __global__ __launch_bounds__(128) void
-k_bptc_128x77(const uint8_t* __restrict__ in, size_t n, uint8_t* __restrict__ out77, uint32_t* __restrict__ errs,
-              const Tables* __restrict__ T) {
+k_bptc_128x77(const uint8_t* __restrict__ in, size_t n, uint8_t* __restrict__ out77, uint32_t* __restrict__ errs) {
     const size_t i = (size_t)blockIdx.x * 128 + threadIdx.x;
     if (i >= n) {
         return;
@@ -577,17 +347,7 @@ k_bptc_128x77(const uint8_t* __restrict__ in, size_t n, uint8_t* __restrict__ ou
     }
     for (int r = 0; r < 7; r++) {
         uint32_t w = row[r];
-        const int s = syndrome<5>(w, ddn_hamming_16_11_4_H);
-        bool ok = true;
-        if (s > 0) {
-            const uint8_t p = T->h16114[s];
-            if (p == 0xFF) {
-                ok = false;
-            } else {
-                w ^= 1u << p;
-            }
-        }
-        if (ok) {
+        if (bc::decode(bc::HAMMING_16_11_4, w)) {
             line = w & 0x7FFu;
         } else {
             bad++;
@@ -617,8 +377,7 @@ k_bptc_128x77(const uint8_t* __restrict__ in, size_t n, uint8_t* __restrict__ ou
 }
 
 __global__ __launch_bounds__(128) void
-k_bptc_16x2(const uint8_t* __restrict__ in, size_t n, int parity_odd, uint8_t* __restrict__ out32, uint32_t* __restrict__ errs,
-            const Tables* __restrict__ T) {
+k_bptc_16x2(const uint8_t* __restrict__ in, size_t n, int parity_odd, uint8_t* __restrict__ out32, uint32_t* __restrict__ errs) {
     const size_t i = (size_t)blockIdx.x * 128 + threadIdx.x;
     if (i >= n) {
         return;
@@ -628,14 +387,11 @@ k_bptc_16x2(const uint8_t* __restrict__ in, size_t n, int parity_odd, uint8_t* _
         m |= (uint32_t)(in[i * 32 + j] & 1u) << c_bptc_rc_perm[j];
     }
     uint32_t bad = 0;
-    const int s = syndrome<5>(m & 0xFFFFu, ddn_hamming_16_11_4_H);
-    if (s > 0) {
-        const uint8_t p = T->h16114[s];
-        if (p == 0xFF) {
-            bad = 1;
-        } else if (p < 11) { // only the eleven data bits are copied back (bptc.c:311-313)
-            m ^= 1u << p;
-        }
+    const int p = bc::position(bc::HAMMING_16_11_4, m & 0xFFFFu);
+    if (p == bc::NONE) {
+        bad = 1;
+    } else if (p >= 0 && p < 11) { // only the eleven data bits are copied back (bptc.c:311-313)
+        m ^= 1u << p;
     }
     for (int j = 0; j < 32; j++) {
         out32[i * 32 + j] = (uint8_t)((m >> j) & 1u);
@@ -652,12 +408,7 @@ ddn_dev_bptc_128x77(const uint8_t* in, size_t n, uint8_t* out77, uint32_t* errs,
     if (n == 0) {
         return hipSuccess;
     }
-    const Tables* T = nullptr;
-    hipError_t e = device_tables(&T, st);
-    if (e != hipSuccess) {
-        return e;
-    }
-    hipLaunchKernelGGL(k_bptc_128x77, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, in, n, out77, errs, T);
+    hipLaunchKernelGGL(k_bptc_128x77, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, in, n, out77, errs);
     return hipGetLastError();
 }
 
@@ -666,12 +417,7 @@ ddn_dev_bptc_16x2(const uint8_t* in, size_t n, int parity_odd, uint8_t* out32, u
     if (n == 0) {
         return hipSuccess;
     }
-    const Tables* T = nullptr;
-    hipError_t e = device_tables(&T, st);
-    if (e != hipSuccess) {
-        return e;
-    }
-    hipLaunchKernelGGL(k_bptc_16x2, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, in, n, parity_odd, out32, errs, T);
+    hipLaunchKernelGGL(k_bptc_16x2, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, in, n, parity_odd, out32, errs);
     return hipGetLastError();
 }
 
@@ -742,9 +488,4 @@ ddn_dev_rs_12_9(uint8_t* cw, size_t n, uint8_t* result, uint8_t* found, uint8_t*
     }
     hipLaunchKernelGGL(k_rs_12_9, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, cw, n, result, found, syn_out);
     return hipGetLastError();
-}
-
-extern "C" hipError_t
-ddn_dev_fec3_tables(const DdnFec3Tables** out, hipStream_t st) {
-    return device_tables(out, st);
 }

@@ -17,14 +17,13 @@
 //   NXDN  nxdn_frame() (src/protocol/nxdn/nxdn_frame.c:181-233,592-640): 8 LICH dibits de-scrambled (PN9 seed 228), parity and
 //         profile table; accepted -> 174 more, rejected -> the handler returns and lastsynctype is cleared
 //
-// Code tables (syndrome -> positions to flip) are ddn_fec3.hip's per-device ones, built in the reference's init-loop order.
+// The three codes (TACT Hamming(7,4), slot type Golay(20,8), EMB QR(16,7,6)) and their tables are ddn_bcode_dev.h's.
 #ifndef DDN_FSK4H_DEV_H
 #define DDN_FSK4H_DEV_H
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "ddn_fec3.h"
-#include "ddn_tables_fec3.h"
+#include "ddn_bcode_dev.h"
 
 namespace ddn_fsk4h {
 
@@ -38,71 +37,11 @@ enum {
     F_PENDING, F_REDB, F_STEREO, F_NEV, F_COUNT = 32
 };
 
-template <int R>
-__device__ __forceinline__ int
-syndrome(uint32_t w, const uint32_t (&H)[R]) {
-    int s = 0;
-#pragma unroll
-    for (int i = 0; i < R; i++) {
-        s |= (__popc(w & H[i]) & 1) << (R - 1 - i);
-    }
-    return s;
-}
-
-// Hamming_7_4_decode (fec.c:145-170) on a word with bit j = rxBits[j]; returns ok, *w corrected
-__device__ __forceinline__ bool
-hamming_7_4(uint32_t& w, const DdnFec3Tables* T) {
-    const int s = syndrome<3>(w, ddn_hamming_7_4_H);
-    if (s > 0) {
-        const uint8_t p = T->h74[s];
-        if (p == 0xFF) {
-            return false;
-        }
-        w ^= 1u << p;
-    }
-    return true;
-}
-// Golay_20_8_decode (fec.c:514-561): up to two flips accepted (the flips of a three-position entry are applied, then refused)
-__device__ __forceinline__ bool
-golay_20_8(uint32_t& w, const DdnFec3Tables* T) {
-    const int s = syndrome<12>(w, ddn_golay_20_8_H);
-    if (s > 0) {
-        int k = 0;
-        for (; k < 3; k++) {
-            const uint8_t p = T->g208[s][k];
-            if (p == 0xFF) {
-                break;
-            }
-            w ^= 1u << p;
-        }
-        return !(k == 0 || k > 2);
-    }
-    return true;
-}
-// QR_16_7_6_decode (fec.c:782-822)
-__device__ __forceinline__ bool
-qr_16_7_6(uint32_t& w, const DdnFec3Tables* T) {
-    const int s = syndrome<9>(w, ddn_qr_16_7_6_H);
-    if (s > 0) {
-        int k = 0;
-        for (; k < 2; k++) {
-            const uint8_t p = T->qr[s][k];
-            if (p == 0xFF) {
-                break;
-            }
-            w ^= 1u << p;
-        }
-        return k != 0;
-    }
-    return true;
-}
-
 // The handler context of one lane: hs = its words in LDS (stride = lanes), pay = its burst dibits in LDS (stride = lanes)
 struct Ctx {
     int* hs;
     uint8_t* pay;
     int stride;
-    const DdnFec3Tables* T;
     int32_t* events; // this channel's event rows, or nullptr
     int max_events;
     __device__ __forceinline__ int& f(int field) const { return hs[field * stride]; }
@@ -233,7 +172,7 @@ tact_decode(const Ctx& x, int& slot_out) { // CACH dibits 0..11 de-interleaved, 
         }
     }
     uint32_t t = cach & 0x7Fu;
-    if (!hamming_7_4(t, x.T)) {
+    if (!ddn_bcode::decode(ddn_bcode::HAMMING_7_4, t)) {
         return false;
     }
     slot_out = (int)((t >> 1) & 1u);
@@ -261,7 +200,7 @@ data_slot_type(const Ctx& x, int pos) {
         st |= (uint32_t)((b >> 1) & 1) << (10 + 2 * i);
         st |= (uint32_t)(b & 1) << (11 + 2 * i);
     }
-    if (!golay_20_8(st, x.T)) {
+    if (!ddn_bcode::decode(ddn_bcode::GOLAY_20_8, st)) {
         x.ev(pos, EV_DMR_DATA, 0, -1, -1);
         return false;
     }
@@ -372,7 +311,7 @@ bs_burst_done(const Ctx& x, int pos) {
                 emb |= (uint32_t)(b & 1) << (9 + 2 * i);
             }
             int cc = 25;
-            int emb_ok = qr_16_7_6(emb, x.T) ? 1 : 0;
+            int emb_ok = ddn_bcode::decode(ddn_bcode::QR_16_7_6, emb) ? 1 : 0;
             bool ended = false;
             if (emb_ok) {
                 x.f(F_EMBERR0 + slot) = 0;

@@ -12,42 +12,19 @@
 
 #include <hip/hip_runtime.h>
 
-#include <mutex>
 #include <stdint.h>
 
+#include "ddn_bcode_dev.h"
 #include "ddn_device.h"
 
 namespace {
-__device__ __forceinline__ uint32_t
-golay_syndrome11(uint32_t cw) {
-    cw &= 0x7fffffu;
-#pragma unroll
-    for (int i = 0; i < 12; i++) {
-        cw = (cw & 1u) ? ((cw ^ 0xAE3u) >> 1) : (cw >> 1);
-    }
-    return cw;
-}
+using Golay23 = ddn_bcode::Golay23<ddn_bcode::Golay23Lsb>; // the syndrome -> error pattern table
 } // namespace
-
-// builds the syndrome -> error pattern table (every pattern of weight <= 3 over 23 bits: 1+23+253+1771 = 2048)
-__global__ void
-k_golay_table(uint32_t* __restrict__ tab) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x; // 0 .. 23*23*23-1, decoded as (a, b, c) with a <= b <= c
-    if (idx == 0) {
-        tab[0] = 0;
-    }
-    const int a = idx / 529, b = (idx / 23) % 23, c = idx % 23;
-    if (a >= 23 || a > b || b > c) {
-        return;
-    }
-    const uint32_t e = (1u << a) | (1u << b) | (1u << c); // equal indices collapse to lower weights
-    tab[golay_syndrome11(e)] = e;
-}
 
 __global__ __launch_bounds__(256) void
 k_golay24(uint8_t* __restrict__ data, const uint8_t* __restrict__ parity, int len, int n,
-          const uint32_t* __restrict__ tab_g, uint8_t* __restrict__ status, int32_t* __restrict__ fixed, DdnSel sel) {
-    const uint32_t* tab = tab_g; // (read in place - 8 KB, it stays in the L1: single-wave workgroups, no LDS; see DDN_WG)
+          uint8_t* __restrict__ status, int32_t* __restrict__ fixed, DdnSel sel) {
+    const uint32_t* tab = Golay23::v.e; // (read in place - 8 KB, it stays in the L1: single-wave workgroups, no LDS; see DDN_WG)
     auto one = [&](long i) {
     uint8_t* d = data + (size_t)i * len;
     const uint8_t* p = parity + (size_t)i * 12;
@@ -67,7 +44,7 @@ k_golay24(uint8_t* __restrict__ data, const uint8_t* __restrict__ parity, int le
     if (valid) {
         const uint32_t pbit = cw & 0x800000u;
         uint32_t w23 = cw & 0x7fffffu;
-        const uint32_t e = tab[golay_syndrome11(w23)];
+        const uint32_t e = tab[ddn_bcode::Golay23Lsb::syndrome(w23)];
         if (e) {
             const int wt = __popc(e);
             bool fits = false;
@@ -114,7 +91,7 @@ __device__ __forceinline__ int
 golay_hard_word(uint32_t cw, const uint32_t* tab, uint32_t* out, int* fx) {
     const uint32_t pbit = cw & 0x800000u;
     uint32_t w23 = cw & 0x7fffffu;
-    const uint32_t e = tab[golay_syndrome11(w23)];
+    const uint32_t e = tab[ddn_bcode::Golay23Lsb::syndrome(w23)];
     *fx = 0;
     if (e) {
         const int wt = __popc(e);
@@ -151,11 +128,11 @@ golay_encode_word(uint32_t d12) {
 template <int L>
 __global__ __launch_bounds__(256) void
 k_golay24_soft(uint8_t* __restrict__ data, const uint8_t* __restrict__ parity, const int32_t* __restrict__ reliab, int n,
-               const uint32_t* __restrict__ tab_g, uint8_t* __restrict__ status, int32_t* __restrict__ fixed) {
+               uint8_t* __restrict__ status, int32_t* __restrict__ fixed) {
     constexpr int N = L + 12, SH = 12 - L;
     __shared__ uint32_t tab[2048];
     for (int i = threadIdx.x; i < 2048; i += 256) {
-        tab[i] = tab_g[i];
+        tab[i] = Golay23::v.e[i];
     }
     __syncthreads();
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -286,30 +263,6 @@ k_hamming_10_6_3_soft(const uint8_t* __restrict__ bits, const int32_t* __restric
         rel[k] = clamp255d(rp[k]);
         key[k] = rel[k] * 64 + k;
     }
-    // hamming_10_6_3_decode on a word: 0 valid, 1 corrected (data bits only are rewritten), 2 uncorrectable
-    auto hard = [&](uint32_t w, uint32_t* fixed_w) -> int {
-        const uint32_t m[4] = {0x398u, 0x354u, 0x2E2u, 0x1E1u};
-        int syn = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            syn = (syn << 1) | (__popc(w & m[k]) & 1);
-        }
-        *fixed_w = w;
-        if (syn == 0) {
-            return 0;
-        }
-        // syndrome -> flipped word bit (4..9 = data bits), -1 = two or more errors; 0..3 = a parity bit
-        // -1 encoded as 15 in a packed nibble table: {-, 0, 1, 5, 2, x, x, 6, 3, x, x, 7, 4, 8, 9, x}
-        const uint32_t nib = (uint32_t)((0xF9847FF36FF2510Full >> (4 * syn)) & 15u);
-        const int bb = (nib == 15u) ? -1 : (int)nib;
-        if (bb < 0) {
-            return 2;
-        }
-        if (bb >= 4) {
-            *fixed_w = w ^ (1u << bb);
-        }
-        return 1;
-    };
     auto encode = [&](uint32_t w) -> uint32_t {
         const uint32_t d0 = (w >> 9) & 1, d1 = (w >> 8) & 1, d2 = (w >> 7) & 1, d3 = (w >> 6) & 1, d4 = (w >> 5) & 1,
                        d5 = (w >> 4) & 1;
@@ -332,7 +285,7 @@ k_hamming_10_6_3_soft(const uint8_t* __restrict__ bits, const int32_t* __restric
         uint32_t best = 0, hardw = 0;
         {
             uint32_t fw;
-            const int r = hard(orig, &fw);
+            const int r = ddn_bcode::hamming_10_6_3_hard(orig, &fw);
             if (r == 0 || r == 1) {
                 hardw = encode(fw);
                 hard_valid = true;
@@ -371,7 +324,7 @@ k_hamming_10_6_3_soft(const uint8_t* __restrict__ bits, const int32_t* __restric
                 x ^= (mask & (1 << q)) ? flip[q] : 0u;
             }
             uint32_t fw;
-            if (hard(orig ^ x, &fw) != 0) {
+            if (ddn_bcode::hamming_10_6_3_hard(orig ^ x, &fw) != 0) {
                 continue;
             }
             const uint32_t c = orig ^ x;
@@ -408,58 +361,17 @@ k_hamming_10_6_3_soft(const uint8_t* __restrict__ bits, const int32_t* __restric
     status[i] = (uint8_t)rc;
 }
 
-// syndrome -> error pattern table, built once per DEVICE (immutable afterwards): the pointer is device memory, so a
-// process that moves to another GPU with hipSetDevice() must not reuse the first device's table
-static hipError_t
-golay_table(uint32_t** out, hipStream_t st) {
-    static std::mutex mu;
-    static uint32_t* tabs[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) {
-        return e;
-    }
-    if (dev < 0 || dev >= 64) {
-        return hipErrorInvalidDevice;
-    }
-    std::lock_guard<std::mutex> lock(mu);
-    if (!tabs[dev]) {
-        uint32_t* t = nullptr;
-        e = hipMalloc(&t, 2048 * sizeof(uint32_t));
-        if (e != hipSuccess) {
-            return e;
-        }
-        hipLaunchKernelGGL(k_golay_table, dim3((23 * 23 * 23 + 255) / 256), dim3(256), 0, st, t);
-        e = hipGetLastError();
-        if (e == hipSuccess) {
-            e = hipStreamSynchronize(st);
-        }
-        if (e != hipSuccess) {
-            (void)hipFree(t);
-            return e;
-        }
-        tabs[dev] = t;
-    }
-    *out = tabs[dev];
-    return hipSuccess;
-}
-
 extern "C" hipError_t
 ddn_dev_golay24_soft(uint8_t* data, const uint8_t* parity, const int32_t* reliab, int len, int n, uint8_t* status,
                      int32_t* fixed, hipStream_t st) {
     if (n <= 0) {
         return hipSuccess;
     }
-    uint32_t* tab = nullptr;
-    hipError_t e = golay_table(&tab, st);
-    if (e != hipSuccess) {
-        return e;
-    }
     const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
     if (len == 6) {
-        hipLaunchKernelGGL((k_golay24_soft<6>), grid, blk, 0, st, data, parity, reliab, n, (const uint32_t*)tab, status, fixed);
+        hipLaunchKernelGGL((k_golay24_soft<6>), grid, blk, 0, st, data, parity, reliab, n, status, fixed);
     } else {
-        hipLaunchKernelGGL((k_golay24_soft<12>), grid, blk, 0, st, data, parity, reliab, n, (const uint32_t*)tab, status, fixed);
+        hipLaunchKernelGGL((k_golay24_soft<12>), grid, blk, 0, st, data, parity, reliab, n, status, fixed);
     }
     return hipGetLastError();
 }
@@ -480,13 +392,8 @@ ddn_dev_golay24(uint8_t* data, const uint8_t* parity, int len, int n, uint8_t* s
     if (n <= 0) {
         return hipSuccess;
     }
-    uint32_t* tab = nullptr;
-    hipError_t e0 = golay_table(&tab, st);
-    if (e0 != hipSuccess) {
-        return e0;
-    }
     const DdnSel sel = ddn_sel_for(len == 6 ? 36 : 12);
     hipLaunchKernelGGL(k_golay24, dim3(ddn_sel_grid(&sel, ((unsigned long)n + DDN_WG - 1) / DDN_WG)), dim3(DDN_WG), 0, st, data, parity, len, n,
-                       (const uint32_t*)tab, status, fixed, sel);
+                       status, fixed, sel);
     return hipGetLastError();
 }

@@ -25,10 +25,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ddn_bcode_dev.h"
 #include "ddn_crc_dev.h"
 #include "ddn_expf.h"
 #include "ddn_fec3.h"
-#include "ddn_tables_fec3.h"
 
 namespace {
 
@@ -129,7 +129,7 @@ k_m17_lsf_finish(const uint8_t* __restrict__ dec, int dec_stride, const uint32_t
 __global__ __launch_bounds__(64) void
 k_m17_str_bits(const uint8_t* __restrict__ rec, size_t stride, const int32_t* __restrict__ counts, const int32_t* __restrict__ sync_pos,
                const uint8_t* __restrict__ sync_pat, const int32_t* __restrict__ n_sync, int max_syncs, int lmax,
-               const DdnFec3Tables* __restrict__ T, uint8_t* __restrict__ sym296, int32_t* __restrict__ slot_sync,
+               uint8_t* __restrict__ sym296, int32_t* __restrict__ slot_sync,
                uint8_t* __restrict__ slot_lich6, uint8_t* __restrict__ slot_cnt, uint8_t* __restrict__ slot_ok) {
     __shared__ uint8_t bits[368]; // de-randomised, de-interleaved
     __shared__ uint32_t word[4];
@@ -160,23 +160,7 @@ k_m17_str_bits(const uint8_t* __restrict__ rec, size_t stride, const int32_t* __
         for (int q = 0; q < 24; q++) {
             w |= (uint32_t)bits[24 * lane + q] << q;
         }
-        int s = 0;
-#pragma unroll
-        for (int i = 0; i < 12; i++) {
-            s |= (__popc(w & ddn_golay_24_12_H[i]) & 1) << (11 - i);
-        }
-        bool ok = true;
-        if (s > 0) {
-            int k = 0;
-            for (; k < 3; k++) {
-                const uint8_t p = T->g2412[s][k];
-                if (p == 0xFF) {
-                    break;
-                }
-                w ^= 1u << p;
-            }
-            ok = k != 0;
-        }
+        const bool ok = ddn_bcode::decode(ddn_bcode::GOLAY_24_12, w);
         word[lane] = w;
         werr[lane] = ok ? 0 : 1;
     }
@@ -323,7 +307,7 @@ k_ysf_fich_cost(const uint8_t* __restrict__ rec, size_t stride, const int32_t* _
 
 __global__ void
 k_ysf_fich_finish(const uint8_t* __restrict__ dec, int dec_stride, const uint32_t* __restrict__ cost, const int32_t* __restrict__ slot_sync,
-                  int n_channels, int lmax, int max_syncs, const DdnFec3Tables* __restrict__ T, uint8_t* __restrict__ fich4,
+                  int n_channels, int lmax, int max_syncs, uint8_t* __restrict__ fich4,
                   uint8_t* __restrict__ status, uint32_t* __restrict__ v_error) {
     const int slot = blockIdx.x * blockDim.x + threadIdx.x;
     if (slot >= n_channels * lmax) {
@@ -343,22 +327,7 @@ k_ysf_fich_finish(const uint8_t* __restrict__ dec, int dec_stride, const uint32_
             const int b = 8 + 24 * w4 + q;
             w |= (uint32_t)((by[b >> 3] >> (7 - (b & 7))) & 1) << q;
         }
-        int s = 0;
-#pragma unroll
-        for (int i = 0; i < 12; i++) {
-            s |= (__popc(w & ddn_golay_24_12_H[i]) & 1) << (11 - i);
-        }
-        if (s > 0) { // Golay_24_12_decode, src/fec/fec.c:656-690
-            int kk = 0;
-            for (; kk < 3; kk++) {
-                const uint8_t p = T->g2412[s][kk];
-                if (p == 0xFF) {
-                    break;
-                }
-                w ^= 1u << p;
-            }
-            bad = bad || kk == 0;
-        }
+        bad = !ddn_bcode::decode(ddn_bcode::GOLAY_24_12, w) || bad; // Golay_24_12_decode, src/fec/fec.c:656-690
         for (int q = 0; q < 12; q++) {
             fich = (fich << 1) | ((w >> q) & 1u);
         }
@@ -739,14 +708,9 @@ ddn_dev_ysf_fich_cost(const uint8_t* rec, size_t stride, const int32_t* counts, 
 extern "C" hipError_t
 ddn_dev_ysf_fich_finish(const uint8_t* dec, int dec_stride, const uint32_t* cost, const int32_t* slot_sync, int n_channels, int lmax,
                         int max_syncs, uint8_t* fich4, uint8_t* status, uint32_t* v_error, hipStream_t st) {
-    const DdnFec3Tables* T = nullptr;
-    const hipError_t e = ddn_dev_fec3_tables(&T, st);
-    if (e != hipSuccess) {
-        return e;
-    }
     const int n = n_channels * lmax;
     hipLaunchKernelGGL(k_ysf_fich_finish, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, dec, dec_stride, cost, slot_sync, n_channels,
-                       lmax, max_syncs, T, fich4, status, v_error);
+                       lmax, max_syncs, fich4, status, v_error);
     return hipGetLastError();
 }
 
@@ -754,13 +718,8 @@ extern "C" hipError_t
 ddn_dev_m17_str_bits(const uint8_t* rec, size_t stride, const int32_t* counts, const int32_t* sync_pos, const uint8_t* sync_pat,
                      const int32_t* n_sync, int n_channels, int max_syncs, int lmax, uint8_t* sym296, int32_t* slot_sync, uint8_t* slot_lich6,
                      uint8_t* slot_cnt, uint8_t* slot_ok, hipStream_t st) {
-    const DdnFec3Tables* T = nullptr;
-    const hipError_t e = ddn_dev_fec3_tables(&T, st);
-    if (e != hipSuccess) {
-        return e;
-    }
     hipLaunchKernelGGL(k_m17_str_bits, dim3((unsigned)n_channels, (unsigned)lmax), dim3(64), 0, st, rec, stride, counts, sync_pos, sync_pat,
-                       n_sync, max_syncs, lmax, T, sym296, slot_sync, slot_lich6, slot_cnt, slot_ok);
+                       n_sync, max_syncs, lmax, sym296, slot_sync, slot_lich6, slot_cnt, slot_ok);
     return hipGetLastError();
 }
 

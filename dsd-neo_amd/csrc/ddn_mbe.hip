@@ -8,8 +8,8 @@
 //
 // Three kernels, split by what is actually sequential:
 //   k_mbe_frame_decode  frames are independent: one lane per frame, 64 frames staged coalesced through LDS, Golay(23,12)
-//                       by a 2048-entry syndrome -> pattern table in LDS (the code is perfect), Hamming(15,11) by its
-//                       parity-check column, the PN sequence as four 23-bit and three 15-bit masks.  HBM-bound:
+//                       by ddn_bcode_dev.h's 2048-entry syndrome -> pattern constant (the code is perfect), Hamming(15,11) by
+//                       its parity-check column, the PN sequence as four 23-bit and three 15-bit masks.  HBM-bound:
 //                       184 B in + 108 B out per IMBE frame.
 //   k_mbe_params        a talk path's frames depend on each other only through the parameter history (log-magnitude
 //                       prediction, phase track, repeat counter): one wavefront per talk path walks its frames in
@@ -22,9 +22,9 @@
 //                       640 B of PCM per frame written coalesced.
 
 #include <hip/hip_runtime.h>
-#include <mutex>
 #include <stdint.h>
 
+#include "ddn_bcode_dev.h"
 #include "ddn_device.h"
 #include "ddn_mbe.h"
 #include "ddn_mbe_dev.h"
@@ -33,70 +33,25 @@
 namespace {
 
 // ---- frame FEC ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t
-golay_syndrome(uint32_t w) {
-#pragma unroll
-    for (int i = 22; i >= 11; i--) {
-        if ((w >> i) & 1u) {
-            w ^= 0xC75u << (i - 11);
-        }
-    }
-    return w & 0x7FFu;
-}
-
-__device__ __forceinline__ void
-golay_table_lds(uint32_t* tab, int tid, int nthreads) {
-    for (int idx = tid; idx < 23 * 23 * 23; idx += nthreads) {
-        const int a = idx / 529, b = (idx / 23) % 23, c = idx % 23;
-        if (a <= b && b <= c) {
-            const uint32_t e = (1u << a) | (1u << b) | (1u << c);
-            tab[golay_syndrome(e)] = e;
-        }
-    }
-    if (tid == 0) {
-        tab[0] = 0;
-    }
-}
-
-// The syndrome -> pattern table once per device in global memory (8 KB): a decode block copies it into LDS instead of walking the
-// 23^3 patterns itself (that walk was most of a block's work: 190 iterations per lane against the 64 frames' few hundred
-// instructions).
-__device__ uint32_t g_golay_tab[2048];
-
-__global__ __launch_bounds__(256) void
-k_golay_tab_init() {
-    __shared__ uint32_t tab[2048];
-    for (int i = threadIdx.x; i < 2048; i += 256) {
-        tab[i] = 0;
-    }
-    __syncthreads();
-    golay_table_lds(tab, threadIdx.x, 256);
-    __syncthreads();
-    for (int i = threadIdx.x; i < 2048; i += 256) {
-        g_golay_tab[i] = tab[i];
-    }
-}
+using Golay23 = ddn_bcode::Golay23<ddn_bcode::Golay23Msb>; // syndrome -> error pattern, 8 KB
 
 // corrects the 12 data bits (22..11) of a 23-bit word, parity bits stay as received (mbe_golay2312)
 __device__ __forceinline__ uint32_t
 golay_fix(uint32_t w, const uint32_t* tab, int& errs) {
-    const uint32_t e = tab[golay_syndrome(w)] & 0x7FF800u;
+    const uint32_t e = tab[ddn_bcode::Golay23Msb::syndrome(w)] & 0x7FF800u;
     errs = __popc(e);
     return w ^ e;
 }
 
 __device__ __forceinline__ uint32_t
 hamming_fix(uint32_t w, int& errs) {
-    const uint32_t m0 = 0x7f08, m1 = 0x78e4, m2 = 0x66d2, m3 = 0x55b1;
-    const uint32_t syn = ((__popc(w & m0) & 1) << 3) | ((__popc(w & m1) & 1) << 2) | ((__popc(w & m2) & 1) << 1)
-                         | (__popc(w & m3) & 1);
+    const uint32_t syn = (uint32_t)ddn_bcode::syndrome(ddn_bcode::MBE_HAMMING_15_11, w);
     errs = 0;
     if (syn) {
         errs = 1;
 #pragma unroll
         for (int p = 0; p < 15; p++) {
-            const uint32_t col = (((m0 >> p) & 1u) << 3) | (((m1 >> p) & 1u) << 2) | (((m2 >> p) & 1u) << 1) | ((m3 >> p) & 1u);
-            if (col == syn) {
+            if ((uint32_t)ddn_bcode::syndrome(ddn_bcode::MBE_HAMMING_15_11, 1u << p) == syn) { // column p
                 w ^= 1u << p;
             }
         }
@@ -118,7 +73,7 @@ k_mbe_frame_decode(const uint8_t* __restrict__ frames, const uint8_t* __restrict
     constexpr int FPW = DDN_MBE_FRAMES_PER_WG;
     __shared__ uint8_t stage[FPW * FB];
     __shared__ uint8_t outb[FPW * OB];
-    const uint32_t* tab = g_golay_tab;
+    const uint32_t* tab = Golay23::v.e;
     const int lane = threadIdx.x;
     const size_t f0 = (size_t)blockIdx.x * FPW;
     const size_t nf = (n - f0) < (size_t)FPW ? (n - f0) : (size_t)FPW;
@@ -840,28 +795,6 @@ ddn_dev_mbe_frame_decode(int codec, const uint8_t* frames, const uint8_t* soft, 
                          hipStream_t st) {
     if (n == 0) {
         return hipSuccess;
-    }
-    { // the Golay table of this device, built at the first decode
-        static std::mutex mu;
-        static bool up[64] = {false};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) {
-            return hipErrorInvalidDevice;
-        }
-        std::lock_guard<std::mutex> lock(mu);
-        if (dev < 0 || dev >= 64 || !up[dev]) {
-            hipLaunchKernelGGL(k_golay_tab_init, dim3(1), dim3(256), 0, st);
-            hipError_t e = hipGetLastError();
-            if (e == hipSuccess) {
-                e = hipStreamSynchronize(st); // other streams' decodes may follow at once
-            }
-            if (e != hipSuccess) {
-                return e;
-            }
-            if (dev >= 0 && dev < 64) {
-                up[dev] = true;
-            }
-        }
     }
     const dim3 grid((unsigned)((n + DDN_MBE_FRAMES_PER_WG - 1) / DDN_MBE_FRAMES_PER_WG)), blk(64);
     if (codec == DDN_MBE_IMBE_7200X4400) {

@@ -223,7 +223,7 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
           uint8_t* __restrict__ rec, uint8_t* __restrict__ flags, uint8_t* __restrict__ pay, int32_t* __restrict__ counts,
           size_t max_sym, const int32_t* __restrict__ lock4, int32_t* __restrict__ sync_pos, uint8_t* __restrict__ sync_pat,
           uint8_t* __restrict__ pre, uint8_t* __restrict__ pre_rel, int32_t* __restrict__ n_sync, int max_sync,
-          int32_t* __restrict__ hwords, uint8_t* __restrict__ hpay_store, const DdnFec3Tables* __restrict__ htab,
+          int32_t* __restrict__ hwords, uint8_t* __restrict__ hpay_store,
           int32_t* __restrict__ events, int32_t* __restrict__ n_events) {
     using LdsT = Lds4<CPW, Fsk4Cfg<PROTO>::short_sym>;
     constexpr int TSW = LdsT::TSW, RMASKW = LdsT::RMASKW, QCAPW = LdsT::QCAPW;
@@ -473,7 +473,6 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
         x.hs = &LH.hs[0][ln];
         x.pay = &LH.pay[0][ln];
         x.stride = CPW;
-        x.T = htab;
         x.events = events ? events + (size_t)ch * cfg_max_events * 4 : nullptr;
         x.max_events = cfg_max_events;
         return x;
@@ -2006,7 +2005,7 @@ launch(const float* raw, const float* filt, const float* prev_tail, float* fstal
        int n_channels, const DdnFsk4Config* cfg, DdnFsk4State* state, float* lbuf_store, float* shist_store,
        uint8_t* phist_store, uint8_t* rhist_store, uint8_t* rec, uint8_t* flags, uint8_t* pay, int32_t* counts,
        size_t max_sym, const int32_t* lock4, int32_t* sync_pos, uint8_t* sync_pat, uint8_t* pre, uint8_t* pre_rel,
-       int32_t* n_sync, int max_sync, int32_t* hwords, uint8_t* hpay, const DdnFec3Tables* htab, int32_t* events,
+       int32_t* n_sync, int max_sync, int32_t* hwords, uint8_t* hpay, int32_t* events,
        int32_t* n_events, hipStream_t st) {
     using LdsT = Lds4<CPW, Fsk4Cfg<PROTO>::short_sym>;
     const size_t shmem = HM ? (((sizeof(LdsT) + 15) & ~(size_t)15) + sizeof(Lds4H<CPW>)) : sizeof(LdsT);
@@ -2026,7 +2025,7 @@ launch(const float* raw, const float* filt, const float* prev_tail, float* fstal
     hipLaunchKernelGGL((k_fsk4_rx<CPW, MAXW, PROTO, HM>), dim3((unsigned)((n_channels + CPW - 1) / CPW)), dim3(128), shmem, st,
                        raw, filt, prev_tail, fstale, taps, n, stride, n_channels, cfg, state, lbuf_store, shist_store,
                        phist_store, rhist_store, rec, flags, pay, counts, max_sym, lock4, sync_pos, sync_pat, pre, pre_rel,
-                       n_sync, max_sync, hwords, hpay, htab, events, n_events);
+                       n_sync, max_sync, hwords, hpay, events, n_events);
     return hipGetLastError();
 }
 } // namespace
@@ -2047,22 +2046,15 @@ ddn_dev_fsk4_rx(const float* raw, const float* filt, const float* prev_tail, flo
     if ((protocol == 4 || protocol == 5 || protocol == 6 || protocol == 7 || protocol == 8) && handlers) {
         return hipErrorInvalidValue; // M17 / YSF / dPMR / D-STAR / EDACS frames are fixed counts: no handler family
     }
-    const DdnFec3Tables* htab = nullptr;
-    if (handlers) {
-        if (!hwords || !hpay) {
-            return hipErrorInvalidValue;
-        }
-        const hipError_t e = ddn_dev_fec3_tables(&htab, st);
-        if (e != hipSuccess) {
-            return e;
-        }
+    if (handlers && (!hwords || !hpay)) {
+        return hipErrorInvalidValue;
     }
     // MAXW: the longest whole symbol the straight pass takes (samples per symbol + one slip sample); 12 covers 4800 baud at
     // 48 ksps, 22 covers 2400 baud
     const int sps = cfg_sps > 0 ? cfg_sps : 64;
 #define DDN_RX4_ARGS                                                                                                       \
     raw, filt, prev_tail, fstale, taps, n, stride, n_channels, cfg, state, lbuf_store, shist_store, phist_store, rhist_store, rec,  \
-        flags, pay, counts, max_sym, lock4, sync_pos, sync_pat, pre, pre_rel, n_sync, max_sync, hwords, hpay, htab, events,     \
+        flags, pay, counts, max_sym, lock4, sync_pos, sync_pat, pre, pre_rel, n_sync, max_sync, hwords, hpay, events,           \
         n_events, st
 #define DDN_RX4_GO(CPW_, MAXW_)                                                                                            \
     do {                                                                                                                   \
