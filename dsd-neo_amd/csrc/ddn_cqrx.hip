@@ -24,10 +24,9 @@
 #include "ddn_p25h_dev.h"
 
 namespace {
-using ddn_p25h::Scratch;
+using namespace ddn_p25h; // the handlers' decoders (ddn_p25h_dev.h) and decision rules (ddn_p25h_rules.h)
 
 constexpr int MSZ = 1024, SSZ = 128;
-enum { PH_IDLE = 0, PH_NID = 1, PH_BODY = 2, PH_TSBK = 3, PH_MPDU = 4 };
 
 struct Lds {
     // (round 6) the 1024-deep extrema rings stay where the carried state keeps them, in HBM (one slot read - a slot ahead, so off the
@@ -195,12 +194,6 @@ cq_digitize(float sym, float center, int map_idx, int negative, const float leve
     rel8 = clamp255(a1 < a0 ? a1 : a0);
 }
 
-// the half-rate decoder's short cut as a call: inlined, its registers are allocated on top of the per-symbol path's (capped below)
-__device__ __noinline__ bool
-cq_hard_path(const ddn_p25h::Scratch& sc, int lane, uint32_t* by) {
-    return ddn_p25h::half_rate_hard_path_wave(sc, lane, by);
-}
-
 // (round 6) three wavefronts per SIMD: left to itself the kernel compiled to 256 + registers (the handlers' decoders, inlined) - ONE
 // wavefront per SIMD, four channels per CU, 4096 channels in four rounds (29 ms per 4096 x 4800 symbols).  The per-symbol path needs a
 // fraction of that.  Capped at 168 registers twelve channels are resident per CU (the chain objects at 4096 channels: P25 CQPSK 72.6
@@ -308,15 +301,15 @@ k_cq_rx(const float* __restrict__ symbols, const int32_t* __restrict__ counts_in
         s_min = -15000.0f;
         h_nac = 0; // engine.c:1889; p2_cc stays
     };
-    auto push_event = [&](int pos, int kind, int a, int b, int p0, int p1, int p2, int p3) {
+    auto push_event = [&](int pos, const Event& ev) {
         if (lane == 0 && events && nev < cfg.max_events) {
             int32_t* e = events + ((size_t)ch * cfg.max_events + nev) * 4;
             e[0] = pos;
-            e[1] = kind;
-            e[2] = a;
-            e[3] = b;
+            e[1] = ev.kind;
+            e[2] = ev.a;
+            e[3] = ev.b;
             if (event_data) {
-                *reinterpret_cast<int4*>(event_data + ((size_t)ch * cfg.max_events + nev) * 4) = make_int4(p0, p1, p2, p3);
+                *reinterpret_cast<int4*>(event_data + ((size_t)ch * cfg.max_events + nev) * 4) = make_int4(ev.d0, ev.d1, ev.d2, ev.d3);
             }
         }
         nev++;
@@ -325,7 +318,7 @@ k_cq_rx(const float* __restrict__ symbols, const int32_t* __restrict__ counts_in
     auto block_take = [&](int l0, int l1) {
         if ((h_skip / 36) == 0) {
             if (h_k < 98 && lane == 0) {
-                L.sc.d[ddn_p25h::deinterleave98(h_k)] = (int32_t)((uint32_t)(uint16_t)(int16_t)l0 | ((uint32_t)(uint16_t)(int16_t)l1 << 16));
+                L.sc.d[deinterleave98(h_k)] = (int32_t)((uint32_t)(uint16_t)(int16_t)l0 | ((uint32_t)(uint16_t)(int16_t)l1 << 16));
             }
             h_k++;
         } else {
@@ -333,34 +326,10 @@ k_cq_rx(const float* __restrict__ symbols, const int32_t* __restrict__ counts_in
         }
         h_skip++;
     };
-    // tsbk_decode_repetition_bytes(): list-8, the first CRC16-clean candidate, else the best one
-    auto half_rate_select = [&](uint32_t by[3], int& crc_ok) -> int {
+    // the block's decode; its short cut as a call keeps the registers off the per-symbol path (capped above); cfg.dbg bit 1: no short cut
+    auto half_rate_select = [&](uint32_t by[3], int& crc_ok) {
         wave_sync();
-        // a clean block's best path is its hard dibits' walk through the trellis (ddn_p25h_dev.h); cfg.dbg bit 1 switches the short
-        // cut off (A/B for the tests)
-        if ((cfg.dbg & 1) || !cq_hard_path(L.sc, lane, by)) {
-            ddn_p25h::half_rate_best_wave(L.sc, lane, by);
-        }
-        crc_ok = ddn_p25h::crc16_ok_wave(L.sc, by, lane);
-        int sel = 0;
-        if (!crc_ok) {
-            wave_sync();
-            ddn_p25h::half_rate_list_wave(L.sc, lane);
-            wave_sync();
-            const int nout = L.sc.n_out;
-            for (int q = 0; q < nout; q++) {
-                const uint32_t cw[3] = {L.sc.outl[q][0], L.sc.outl[q][1], L.sc.outl[q][2]};
-                if (ddn_p25h::crc16_ok(cw)) {
-                    sel = q;
-                    crc_ok = 1;
-                    break;
-                }
-            }
-            by[0] = L.sc.outl[sel][0];
-            by[1] = L.sc.outl[sel][1];
-            by[2] = L.sc.outl[sel][2];
-        }
-        return sel;
+        return half_rate_select_wave<true>(L.sc, lane, !(cfg.dbg & 1), by, crc_ok);
     };
     // one in-frame symbol through the P25 Phase 1 handlers (ddn_p25h_dev.h lists their source lines); false = the handler has returned
     auto handler_symbol = [&](int pos, int d, int l0, int l1) -> bool {
@@ -380,31 +349,25 @@ k_cq_rx(const float* __restrict__ symbols, const int32_t* __restrict__ counts_in
             wave_sync();
             const uint64_t w = __ballot(lane < 63 && L.sc.nb[lane] != 0);
             const int par = L.sc.nb[63], prel = L.sc.nr[63];
-            const int observed = (h_nac > 0 && h_nac < 0xFFF) ? h_nac : ((h_p2cc > 0 && h_p2cc < 0xFFF) ? h_p2cc : 0);
             const ddn_nid::Gf gf = {L.sc.ex, L.sc.lg};
             const ddn_nid::Work wk = {L.sc.work + lane, L.sc.work + 23 * 64 + lane, L.sc.work + 47 * 64 + lane, L.sc.work + 71 * 64 + lane};
-            const ddn_nid::NidRes r = ddn_nid::nid_decode_wave(gf, wk, w, L.sc.nr, par, prel, observed, cfg.nid_threshold, L.sc.masks, lane);
+            const ddn_nid::NidRes r = ddn_nid::nid_decode_wave(gf, wk, w, L.sc.nr, par, prel, observed_nac(h_nac, h_p2cc), cfg.nid_threshold, L.sc.masks, lane);
             wave_sync();
-            int duid = 0xFF;
-            if (r.status > 0) {
-                const bool valid = r.nac != 0 && r.nac != 0xFFF;
-                if (r.nac != h_nac && valid) {
-                    h_nac = r.nac;
-                    h_p2cc = r.nac;
-                }
-                duid = r.duid;
-            }
-            push_event(pos, ddn_p25h::EV_NID, r.status, (r.nac & 0xFFFF) | (duid << 16), r.status, r.nac, r.duid, r.errs);
-            if (duid == 0x7 || duid == 0xC) {
-                h_phase = (duid == 0x7) ? PH_TSBK : PH_MPDU;
-                h_block = 0;
-                h_end = 3;
-                h_skip = 36 - 14;
+            const NidOutcome no = nid_outcome(r.status, r.nac, r.duid, r.errs, h_nac, h_p2cc);
+            h_nac = no.nac;
+            h_p2cc = no.p2cc;
+            push_event(pos, no.ev);
+            const BlockPhase bp = block_phase_start(no.duid);
+            if (bp.phase != PH_IDLE) {
+                h_phase = bp.phase;
+                h_block = bp.block;
+                h_end = bp.end;
+                h_skip = bp.skipdibit;
                 h_idx = 0;
                 h_k = 0;
                 return true;
             }
-            h_left = duid == 0x0 ? 339 : ((duid == 0x5 || duid == 0xA) ? 807 : (duid == 0x3 ? 15 : (duid == 0xF ? 159 : 0)));
+            h_left = body_symbols(no.duid);
             if (h_left <= 0) {
                 h_phase = PH_IDLE;
                 return false;
@@ -421,19 +384,18 @@ k_cq_rx(const float* __restrict__ symbols, const int32_t* __restrict__ counts_in
         }
         if (h_phase == PH_TSBK) {
             block_take(l0, l1);
-            if (++h_idx < 101) {
+            if (++h_idx < TSBK_SYMBOLS) {
                 return true;
             }
             uint32_t by[3];
             int crc_ok;
             const int sel = half_rate_select(by, crc_ok);
-            const int last = (int)((by[0] >> 7) & 1u);
-            push_event(pos, ddn_p25h::EV_TSBK, h_block, crc_ok | (int)(((by[0] >> 8) & 0xFF) << 8) | (((last << 8) | sel) << 16), (int)by[0],
-                       (int)by[1], (int)by[2], (crc_ok & 1) | ((sel & 0xFF) << 8) | (h_block << 16));
+            const TsbkOutcome to = tsbk_outcome(by[0], by[1], by[2], crc_ok, sel, h_block);
+            push_event(pos, to.ev);
             h_block++;
             h_idx = 0;
             h_k = 0;
-            if (last || h_block >= 3) {
+            if (to.last) {
                 h_phase = PH_IDLE;
                 return false;
             }
@@ -449,15 +411,9 @@ k_cq_rx(const float* __restrict__ symbols, const int32_t* __restrict__ counts_in
                 uint32_t by[3];
                 int crc_ok;
                 const int sel = half_rate_select(by, crc_ok);
-                if (crc_ok) {
-                    const int sap = (int)((by[0] >> 8) & 0x3F), blks = (int)((by[1] >> 16) & 0x7F);
-                    h_end = blks + 1;
-                    if ((sap == 61 || sap == 63) && blks > 10) {
-                        h_end = 4;
-                    }
-                }
-                push_event(pos, ddn_p25h::EV_MPDU, crc_ok, (h_end & 0xFFFF) | (int)((by[0] & 0xFF) << 16), (int)by[0], (int)by[1], (int)by[2],
-                           (crc_ok & 1) | ((sel & 0xFF) << 8));
+                const HeaderOutcome ho = header_outcome(by[0], by[1], by[2], crc_ok, sel, h_end);
+                h_end = ho.end;
+                push_event(pos, ho.ev);
             }
             h_block++;
             h_idx = 0;

@@ -15,7 +15,9 @@
 // LLR is non-zero and the hard dibits walk the trellis from state 0, that walk IS the best path and the list decoder's first
 // candidate (its metric is 0 and every other path's is positive), so the 49-step add-compare-select chain is not run; when its
 // bytes pass the CRC16 the CRC scan stops at it.  Otherwise the best path proper (half_rate_best_wave), and when that fails its
-// CRC the list-8 decoder (half_rate_list_wave: one lane per (state, rank), as ddn_trellis.hip's k_p25_half_rate_list).
+// CRC the list-8 decoder (half_rate_list_wave: one lane per (state, rank), as ddn_trellis.hip's k_p25_half_rate_list); the
+// sequence is half_rate_select_wave().  What a decision then means - NAC, DUID lengths, block ends, event words - is integer
+// rules that both loops share and the CPU tests run: ddn_p25h_rules.h.
 #ifndef DDN_P25H_DEV_H
 #define DDN_P25H_DEV_H
 #include <hip/hip_runtime.h>
@@ -24,13 +26,12 @@
 #include "ddn_crc_dev.h"
 #include "ddn_device.h"
 #include "ddn_nid_dev.h"
+#include "ddn_p25h_rules.h"
 #include "ddn_slicer_dev.h"
 
 namespace ddn_p25h {
 
 constexpr int HN = 104; // in-frame history ring, symbols per channel (a phase is at most 101)
-enum { PH_IDLE = 0, PH_NID = 1, PH_TSBK = 3, PH_MPDU = 4 };
-enum { EV_NID = 1, EV_TSBK = 2, EV_MPDU = 3 };
 
 struct Scratch { // one decision at a time
     uint8_t ex[128], lg[64];
@@ -45,53 +46,11 @@ struct Scratch { // one decision at a time
             uint2 back[49][4];       // as bytes [49][4][8]
             uint16_t ct[49][4][4];   // branch costs [step][state][predecessor]
             alignas(16) uint32_t mb[2][32]; // survivor metrics [step parity][state * 8 + rank]
-            uint4 cand[32];
-            uint8_t cvalid[32];
             uint32_t outl[8][4]; // the merged candidate list {bytes 0-3, 4-7, 8-11, metric}
             int n_out;
         };
     };
 };
-
-__device__ __forceinline__ int
-deinterleave98(int i) { // as ddn_trellis.hip: 49 dibit pairs dealt to 4 lanes round-robin
-    const int pair_rx = i >> 1;
-    int lane, k;
-    if (pair_rx < 13) {
-        lane = 0;
-        k = pair_rx;
-    } else {
-        lane = 1 + (pair_rx - 13) / 12;
-        k = (pair_rx - 13) % 12;
-    }
-    return 2 * (lane + 4 * k) + (i & 1);
-}
-
-// trellis output for (state << 2) | next state, src/protocol/p25/p25_12.c:19:
-// {2, 12, 1, 15, 14, 0, 13, 3, 9, 7, 10, 4, 5, 11, 6, 8} packed 4 bits each
-constexpr uint64_t HALF_RATE_NIBBLES = 0x86B5'4A79'3D0E'F1C2ull;
-__host__ __device__ constexpr int
-half_rate_nibble(int idx) {
-    return (int)((HALF_RATE_NIBBLES >> (4 * idx)) & 15u);
-}
-// the table read the other way: (state << 2) | next state of the one branch that emits a nibble, packed 4 bits each
-__host__ __device__ constexpr uint64_t
-half_rate_branches_by_nibble() {
-    uint64_t inv = 0;
-    for (int idx = 0; idx < 16; idx++) {
-        inv |= (uint64_t)idx << (4 * half_rate_nibble(idx));
-    }
-    return inv;
-}
-__host__ __device__ constexpr bool
-half_rate_nibbles_distinct() {
-    unsigned seen = 0;
-    for (int idx = 0; idx < 16; idx++) {
-        seen |= 1u << half_rate_nibble(idx);
-    }
-    return seen == 0xFFFFu;
-}
-static_assert(half_rate_nibbles_distinct(), "half_rate_hard_path_wave: one branch per nibble, or the look-up is not a function");
 
 __device__ __forceinline__ int
 crc16_ok(const uint32_t w[3]) { // p25_crc.c:18-36 over bytes 0..9 of the 12 (big-endian in the words' byte order below)
@@ -244,28 +203,6 @@ half_rate_list_wave(Scratch& sc, int lane) {
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// skipdibit bookkeeping of tsbk_read_repetition_samples() / p25_mpdu_read_repetition() in closed form.  The counter starts a
-// block at sk0 (1..36); a symbol read with the counter at 36 is a status symbol and restarts it, so status symbols sit at
-// i0 = 36 - sk0 and every 36 after.
-__device__ __forceinline__ bool
-block_is_status(int sk0, int i, int& data_index) {
-    const int i0 = 36 - sk0;
-    const int before = (i <= i0) ? 0 : ((i - 1 - i0) / 36 + 1); // status symbols among 0 .. i - 1
-    data_index = i - before;
-    return i >= i0 && ((i - i0) % 36) == 0;
-}
-__device__ __forceinline__ int
-block_counter_after(int sk0, int n_sym, int& n_data) { // the counter after n_sym symbols, and how many of them were data
-    const int i0 = 36 - sk0;
-    if (n_sym <= i0) {
-        n_data = n_sym;
-        return sk0 + n_sym;
-    }
-    const int n_status = (n_sym - 1 - i0) / 36 + 1;
-    n_data = n_sym - n_status;
-    return n_sym - (i0 + 36 * (n_status - 1));
 }
 
 // XOR over the wavefront: four DPP steps inside each row of 16 lanes, then the four rows through scalar reads
@@ -455,30 +392,44 @@ half_rate_hard_path_wave(const Scratch& sc, int lane, uint32_t by[3]) {
     return true;
 }
 
-// symbols p25_mpdu_read_repetition() consumes for one repetition starting with the counter at sk0 (98 data dibits, <= 101 reads)
-__device__ __forceinline__ int
-mpdu_block_symbols(int sk0, int& sk_after) {
-    int sk = sk0, k = 0, i = 0;
-    for (; i < 101; i++) {
-        if ((sk / 36) == 0) {
-            k++;
-        } else {
-            sk = 0;
-        }
-        sk++;
-        if (k == 98) {
-            i++;
-            break;
-        }
-    }
-    sk_after = sk;
-    return i;
+// the short cut as a call, for a kernel whose own path must not be allocated on top of its registers (ddn_cqrx.hip)
+__device__ inline __noinline__ bool
+half_rate_hard_path_call(const Scratch& sc, int lane, uint32_t* by) {
+    return half_rate_hard_path_wave(sc, lane, by);
 }
-
-struct Verdict {
-    int ext;  // symbols the handler reads next (0 = it has returned)
-    int more; // another decision falls due when those are read
-};
+// tsbk_decode_repetition_bytes() / p25_mpdu_decode_r12_block(block 0), LLR pairs in sc.d (written and fenced by the caller): list-8
+// decode, the first CRC16-clean candidate, else the best one -> its index, by[] and crc_ok the same in every lane.  The list's first
+// candidate is the plain best path, so the list proper only runs when that fails its CRC; and the best path of a clean block is its
+// hard dibits' walk, found without the decoder (quick = false switches that off: A/B for the tests).  Fences only, no barrier: the
+// C4FM loop's handler wave is one wave of several.  stamp(1) / stamp(2): after the decode / its CRC, ddn_rx.hip's timing experiments.
+struct NoStamp { __device__ void operator()(int) const {} };
+template <bool HARD_CALL = false, class Stamp = NoStamp>
+__device__ __forceinline__ int
+half_rate_select_wave(Scratch& sc, int lane, bool quick, uint32_t by[3], int& crc_ok, Stamp stamp = Stamp()) {
+    if (!(quick && (HARD_CALL ? half_rate_hard_path_call(sc, lane, by) : half_rate_hard_path_wave(sc, lane, by)))) {
+        half_rate_best_wave(sc, lane, by);
+    }
+    stamp(1);
+    crc_ok = crc16_ok_wave(sc, by, lane);
+    stamp(2);
+    int sel = 0;
+    if (!crc_ok) {
+        half_rate_list_wave(sc, lane);
+        const int nout = sc.n_out;
+        for (int q = 0; q < nout; q++) {
+            const uint32_t cw[3] = {sc.outl[q][0], sc.outl[q][1], sc.outl[q][2]};
+            if (crc16_ok(cw)) {
+                sel = q;
+                crc_ok = 1;
+                break;
+            }
+        }
+        by[0] = sc.outl[sel][0];
+        by[1] = sc.outl[sel][1];
+        by[2] = sc.outl[sel][2];
+    }
+    return sel;
+}
 
 } // namespace ddn_p25h
 #endif

@@ -943,6 +943,7 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
             phase = PH_NID;
         }
         int ext = 0, more = 0;
+        bool early = false; // the verdict went out ahead of the decode
         // cfg.dbg bit 2147483648 (A/B for the tests): every trellis block through half_rate_best_wave(), every verdict after its decode
         const bool quick = ((unsigned)cfg.dbg & 2147483648u) == 0;
         auto answer = [&](int ext_now, int more_now) { // the verdict to the waiting lane (once per request)
@@ -956,8 +957,7 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                 __hip_atomic_store(&H.rsp_seq[c], seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         };
-        int ev_kind = 0, ev_a = 0, ev_b = 0;
-        int32_t pay0 = 0, pay1 = 0, pay2 = 0, pay3 = 0; // what the decision decoded (cfg.event_data)
+        Event ev = {0, 0, 0, 0, 0, 0, 0}; // the decision and what it decoded (cfg.event_data), ddn_p25h_rules.h
         auto slice_at = [&](int i, int& d, int& relb, int& l0, int& l1) {
             int slot = hw - nsym + i; // hw = the ring slot after the phase's last symbol
             slot += slot < 0 ? HN : 0;
@@ -1022,36 +1022,26 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
             dbg_stamp(0);
             const uint64_t w = __ballot(lane < 63 && sc.nb[lane] != 0);
             const int par = sc.nb[63], prel = sc.nr[63];
-            const int observed = (nac > 0 && nac < 0xFFF) ? nac : ((p2cc > 0 && p2cc < 0xFFF) ? p2cc : 0);
             const ddn_nid::Gf gf = {sc.ex, sc.lg};
             const ddn_nid::Work wk = {sc.work + lane, sc.work + 23 * 64 + lane, sc.work + 47 * 64 + lane, sc.work + 71 * 64 + lane};
-            r = ddn_nid::nid_decode_wave(gf, wk, w, sc.nr, par, prel, observed, cfg.nid_threshold, sc.masks, lane);
+            r = ddn_nid::nid_decode_wave(gf, wk, w, sc.nr, par, prel, observed_nac(nac, p2cc), cfg.nid_threshold, sc.masks, lane);
             }
             dbg_stamp(1);
-            int duid = 0xFF;
-            if (r.status > 0) { // p25p1_handle_nid_decode_success(): NAC / DUID updates
-                const bool valid = r.nac != 0 && r.nac != 0xFFF;
-                if (r.nac != nac && valid) {
-                    nac = r.nac;
-                    p2cc = r.nac;
-                }
-                duid = r.duid;
-            }
-            ev_kind = EV_NID;
-            ev_a = r.status;
-            ev_b = (r.nac & 0xFFFF) | (duid << 16);
-            pay0 = r.status, pay1 = r.nac, pay2 = r.duid, pay3 = r.errs;
-            phase = PH_IDLE;
-            if (duid == 0x7 || duid == 0xC) {
-                phase = (duid == 0x7) ? PH_TSBK : PH_MPDU;
-                block = 0;
-                end = 3; // TSBK_MAX_BLOCKS; p25_mpdu_context_init()
-                sk0 = 36 - 14;
+            const NidOutcome no = nid_outcome(r.status, r.nac, r.duid, r.errs, nac, p2cc);
+            nac = no.nac;
+            p2cc = no.p2cc;
+            ev = no.ev;
+            const BlockPhase bp = block_phase_start(no.duid);
+            phase = bp.phase;
+            if (phase != PH_IDLE) {
+                block = bp.block;
+                end = bp.end;
+                sk0 = bp.skipdibit;
                 int ska;
-                ext = (duid == 0x7) ? 101 : mpdu_block_symbols(sk0, ska);
+                ext = (phase == PH_TSBK) ? TSBK_SYMBOLS : mpdu_block_symbols(sk0, ska);
                 more = 1;
             } else {
-                ext = duid == 0x0 ? 339 : ((duid == 0x5 || duid == 0xA) ? 807 : (duid == 0x3 ? 15 : (duid == 0xF ? 159 : 0)));
+                ext = body_symbols(no.duid);
             }
         } else if (phase == PH_TSBK || (phase == PH_MPDU && block == 0)) {
             // the block's data dibits, de-interleaved LLR pairs (lo 16 bits = the dibit's first bit)
@@ -1075,64 +1065,30 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
             // (sc.d; the release fence of answer() has those reads done), and nothing below reads the ring or the request words
             // again - the lane may overwrite both as soon as it goes on.  Its next request is picked up after this one's event is
             // written (one decision at a time), so the channel's events keep their order.
-            if (quick && phase == PH_TSBK && block >= 2) {
+            early = quick && phase == PH_TSBK && tsbk_block_ends(block);
+            if (early) {
                 answer(0, 0);
             }
-            // tsbk_decode_repetition_bytes(): list-8 decode, the first CRC16-clean candidate, else the best one.  The list's
-            // first candidate is the plain best path (ddn_p25h_dev.h), so the list proper is only run when that fails its CRC;
-            // and the best path of a clean block is its hard dibits' walk through the trellis, found without the decoder.
             dbg_stamp(0);
             uint32_t by[3];
-            if (!(quick && half_rate_hard_path_wave(sc, lane, by))) {
-                half_rate_best_wave(sc, lane, by);
-            }
-            dbg_stamp(1);
-            int crc_ok = crc16_ok_wave(sc, by, lane), sel = 0;
-            dbg_stamp(2);
-            if (!crc_ok) {
-                dbg_path = 1;
-                half_rate_list_wave(sc, lane);
-                const int nout = sc.n_out;
-                for (int q = 0; q < nout; q++) {
-                    const uint32_t cw[3] = {sc.outl[q][0], sc.outl[q][1], sc.outl[q][2]};
-                    if (crc16_ok(cw)) {
-                        sel = q;
-                        crc_ok = 1;
-                        break;
-                    }
-                }
-                by[0] = sc.outl[sel][0];
-                by[1] = sc.outl[sel][1];
-                by[2] = sc.outl[sel][2];
-            }
-            const int byte0 = by[0] & 0xFF;
-            pay0 = (int32_t)by[0], pay1 = (int32_t)by[1], pay2 = (int32_t)by[2];
-            pay3 = (crc_ok & 1) | ((sel & 0xFF) << 8) | ((phase == PH_TSBK ? block : 0) << 16);
+            int crc_ok;
+            const int sel = half_rate_select_wave(sc, lane, quick, by, crc_ok, dbg_stamp);
+            dbg_path = (!crc_ok || sel > 0) ? 1 : 0; // the list decoder ran: its first candidate is the path that failed
             sk0 = sk_after;
             if (phase == PH_TSBK) {
-                const int last = (byte0 >> 7) & 1;
-                ev_kind = EV_TSBK;
-                ev_a = block;
-                ev_b = crc_ok | (((by[0] >> 8) & 0xFF) << 8) | (((last << 8) | sel) << 16); // bits 8..15: byte 1 of the block
+                const TsbkOutcome to = tsbk_outcome(by[0], by[1], by[2], crc_ok, sel, block);
+                ev = to.ev;
                 block++;
-                if (last || block >= 3) {
+                if (to.last) {
                     phase = PH_IDLE;
                 } else {
-                    ext = 101;
+                    ext = TSBK_SYMBOLS;
                     more = 1;
                 }
             } else {
-                // p25_mpdu_update_header_from_first_block(): aggressive_framesync = 1 keeps the defaults on a bad header CRC
-                if (crc_ok) {
-                    const int sap = (by[0] >> 8) & 0x3F, blks = (by[1] >> 16) & 0x7F;
-                    end = blks + 1;
-                    if ((sap == 61 || sap == 63) && blks > 10) {
-                        end = 4;
-                    }
-                }
-                ev_kind = EV_MPDU;
-                ev_a = crc_ok;
-                ev_b = (end & 0xFFFF) | (byte0 << 16);
+                const HeaderOutcome ho = header_outcome(by[0], by[1], by[2], crc_ok, sel, end);
+                ev = ho.ev;
+                end = ho.end;
                 block = 1;
                 // the remaining repetitions are read without a decision: their symbol counts follow from the status counter
                 int total = 0;
@@ -1157,22 +1113,22 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
             hs.p2_cc = p2cc;
             h_served = seq;
         }
-        if (!(quick && ev_kind == EV_TSBK && ev_a >= 2)) { // (a TSDU's third block: answered above, ahead of its decode)
+        if (!early) { // (a TSDU's third block: answered above, ahead of its decode)
             answer(ext, more);
         }
 #if DDN_RX_CYCLES
         dbg_free = (int)clock64();
 #endif
         if (lane == c) {
-            if (ev_kind) {
+            if (ev.kind) {
                 if (nev < cfg.max_events && gch < n_channels) {
                     int32_t* e = events + ((size_t)gch * cfg.max_events + nev) * 4;
                     e[0] = o_dec;
-                    e[1] = ev_kind;
-                    e[2] = ev_a;
-                    e[3] = ev_b;
+                    e[1] = ev.kind;
+                    e[2] = ev.a;
+                    e[3] = ev.b;
                     if (cfg.event_data) {
-                        *reinterpret_cast<int4*>(cfg.event_data + ((size_t)gch * cfg.max_events + nev) * 4) = make_int4(pay0, pay1, pay2, pay3);
+                        *reinterpret_cast<int4*>(cfg.event_data + ((size_t)gch * cfg.max_events + nev) * 4) = make_int4(ev.d0, ev.d1, ev.d2, ev.d3);
                     }
                     if (cfg.dbg & 65536) {
                         e[2] = dbg_path;

@@ -22,32 +22,17 @@
 
 #include "ddn_crc_dev.h"
 #include "ddn_device.h"
+#include "ddn_p25h_rules.h"
 
 namespace {
 
-__constant__ uint8_t c_half_rate_nibble[16] = {2, 12, 1, 15, 14, 0, 13, 3, 9, 7, 10, 4, 5, 11, 6, 8};
 __constant__ uint8_t c_r34_point_to_nibble[16] = {2, 10, 7, 15, 14, 6, 11, 3, 13, 5, 8, 0, 1, 9, 4, 12};
 __constant__ uint8_t c_r34_nibble_to_point[16] = {11, 12, 0, 7, 14, 9, 5, 2, 10, 13, 1, 6, 15, 8, 4, 3};
 __constant__ uint8_t c_r34_fsm[64] = {0, 8,  4, 12, 2, 10, 6, 14, 4, 12, 2, 10, 6, 14, 0, 8, 1, 9,  5, 13, 3, 11,
                                       7, 15, 5, 13, 3, 11, 7, 15, 1, 9,  3, 11, 7, 15, 1, 9, 5, 13, 7, 15, 1, 9,
                                       5, 13, 3, 11, 2, 10, 6, 14, 0, 8,  4, 12, 6, 14, 0, 8, 4, 12, 2, 10};
 
-// position of received dibit i inside the de-interleaved block: 49 dibit pairs dealt to 4 lanes round-robin
-__device__ __forceinline__ int
-deinterleave98(int i) {
-    // received order: lane 0 pairs (0,4,8,...,48) [13 pairs], lane 1 (1,5,...,45) [12], lane 2 [12], lane 3 [12]
-    const int pair_rx = i >> 1;
-    int lane, k;
-    if (pair_rx < 13) {
-        lane = 0;
-        k = pair_rx;
-    } else {
-        lane = 1 + (pair_rx - 13) / 12;
-        k = (pair_rx - 13) % 12;
-    }
-    return 2 * (lane + 4 * k) + (i & 1);
-}
-
+using ddn_p25h::deinterleave98; // and the half-rate trellis outputs, half_rate_nibble(): stated once, ddn_p25h_rules.h
 } // namespace
 
 // ------------------------------------------------------------------------------------------------------
@@ -74,7 +59,7 @@ k_p25_half_rate(const int16_t* __restrict__ llr, int n, uint8_t* __restrict__ ou
     uint8_t e[4];
 #pragma unroll
     for (int ps = 0; ps < 4; ps++) {
-        e[ps] = c_half_rate_nibble[(ps << 2) | ns];
+        e[ps] = (uint8_t)ddn_p25h::half_rate_nibble((ps << 2) | ns);
     }
     for (int t = 0; t < 49; t++) {
         const int32_t p0 = live ? d[c][2 * t] : 0, p1 = live ? d[c][2 * t + 1] : 0;
@@ -473,7 +458,7 @@ k_p25_half_rate_list(const int16_t* __restrict__ llr, int n, int max_cand, uint3
     uint8_t e[4];
 #pragma unroll
     for (int ps = 0; ps < 4; ps++) {
-        e[ps] = c_half_rate_nibble[(ps << 2) | ns];
+        e[ps] = (uint8_t)ddn_p25h::half_rate_nibble((ps << 2) | ns);
     }
     for (int t = 0; t < 49; t++) {
         const int32_t p0 = live ? d[c][2 * t] : 0, p1 = live ? d[c][2 * t + 1] : 0;

@@ -304,6 +304,7 @@ long orc_cqrx_run(orc_cqrx* r, const float* sym, long n, int* rec4, uint8_t* fla
 size_t orc_cqrx_sizeof(void);
 size_t orc_cqrx_slicer_offset(void);
 void orc_cqrx_get_state(const orc_cqrx* r, float out8[8]);
+void orc_cqrx_get_handler(const orc_cqrx* r, int out8[8]); /* h.{phase, block, end, skipdibit, nac, p2_cc, idx, k} */
 void orc_cqrx_prime(orc_cqrx* r, float center, float min, float max);
 int orc_cq_reliability(float sym_c, double snr_db);
 void orc_cq_digitize(const orc_slicer* s, float sym, int map_idx, int negative, double snr_db, int rec4[4]);

@@ -523,6 +523,12 @@ orc_cqrx_get_state(const orc_cqrx* r, float out8[8]) {
     out8[7] = (float)r->sl.midx;
 }
 
+void
+orc_cqrx_get_handler(const orc_cqrx* r, int out8[8]) { /* the P25 Phase 1 handler's words between two symbols */
+    const int v[8] = {r->h.phase, r->h.block, r->h.end, r->h.skipdibit, r->h.nac, r->h.p2_cc, r->h.idx, r->h.k};
+    memcpy(out8, v, sizeof(v));
+}
+
 /* Test hook for the reference's frame-sync known answers (tests/test_oracle_framesync_kat.py): the slicer's centre / min / max as
  * those tests set them, the extrema average holding min / max alone. */
 void

@@ -99,11 +99,16 @@ def mpdu_block_symbols(sk0):
     return i
 
 
+def block_data_symbols(sk0, n_sym):
+    """which of a block's n_sym symbols are data dibits, its status counter starting at sk0 (ddn_p25h_rules.h, block_is_status)"""
+    i0 = 36 - sk0
+    return [s for s in range(n_sym) if not (s >= i0 and (s - i0) % 36 == 0)]
+
+
 def classify_block(llr_pairs_rx, sk0):
     """llr_pairs_rx int [n_sym][2]: the LLRs of a block's symbols as received (status symbols included), sk0 its status counter ->
     (is_path, has_zero, bytes12 of the hard path or None)"""
-    i0 = 36 - sk0
-    data = [s for s in range(len(llr_pairs_rx)) if not (s >= i0 and (s - i0) % 36 == 0)][:98]
+    data = block_data_symbols(sk0, len(llr_pairs_rx))[:98]
     assert len(data) == 98
     dei = np.zeros((98, 2), np.int64)
     for k, s in enumerate(data):
