@@ -81,6 +81,16 @@ struct ddn_p25_chain {
     int32_t *d_sc, *d_nldu, *d_sc_out, *d_imbe_res, *d_res_out;
     uint8_t *d_imbe_fr, *d_imbe_soft, *d_imbe_fl, *d_imbe_d;
     float* d_pcm[NSET];
+    // The voice stage works on the call's live slots only (a channel's first 9 * n_ldu): their dense list, made on the device per
+    // buffer set (the synthesis of a pipelined call runs one call later), and the count as a device word.  Of the per-slot arrays,
+    //   kept   d_imbe_d, d_imbe_res, d_res_out, d_pcm[] - what ddn_p25_chain_get_results / _run_host hand out: a slot without a
+    //          frame holds the dead pattern (d_dead: what the whole-array kernels left there), put there at create and put back by
+    //          k_voice_live_fill when a slot goes from live to dead, by one "live when last written" byte per slot and array;
+    //   not    d_first, d_sc, d_sc_out, d_imbe_fr, d_imbe_soft, d_imbe_fl and the vocoder's synthesis records: read by the voice
+    //          kernels alone, and by those at live slots alone - a dead slot holds whatever an earlier call left.
+    int32_t *d_live_off, *d_live[NSET], *d_nlive[NSET];
+    DdnVoiceDead* d_dead;
+    uint8_t *d_was_bits, *d_was_res, *d_was_sres, *d_was_pcm[NSET];
     // pipelining
     hipStream_t s_main, s_aux, s_copy, s_copy2; // front end + loop | decode | H2D | D2H
     hipStream_t s_voice = nullptr;              // the voice stage of a decode, beside its frame FEC
@@ -238,6 +248,74 @@ ddn_p25_chain_destroy(ddn_p25_chain* c) {
     delete c;
 }
 
+// the arguments of k_voice_live_fill for buffer set `set` (a chain without a vocoder never writes d_res_out / d_pcm: not kept)
+static DdnVoiceLive
+chain_voice_live_args(const ddn_p25_chain* c, int set) {
+    DdnVoiceLive a;
+    memset(&a, 0, sizeof(a));
+    a.n_slots = (int)c->V;
+    a.max_ldu = c->Fv;
+    a.n_ldu = c->d_nldu;
+    a.live_off = c->d_live_off;
+    a.live_slot = c->d_live[set];
+    a.dead = c->d_dead;
+    a.bits = c->d_imbe_d;
+    a.was_bits = c->d_was_bits;
+    a.res = c->d_imbe_res;
+    a.was_res = c->d_was_res;
+    if (c->cfg.vocoder) {
+        a.res_out = c->d_res_out;
+        a.was_res_out = c->d_was_sres;
+        a.pcm = c->d_pcm[set];
+        a.was_pcm = c->d_was_pcm[set];
+    }
+    return a;
+}
+
+// The dead pattern, from the kernels themselves: one all-zero IMBE frame with the flag k_imbe_deinterleave gives a slot without
+// records, through the frame decode, the skip flag, the parameter kernel and the synthesis (a talk path of its own: the frame is
+// skipped whatever the history holds).  Then into every slot of every kept array: all "live when last written" bytes set, no
+// channel with an LDU (d_nldu is zero), and the fill kernel once per buffer set.
+static int
+chain_voice_dead_init(ddn_p25_chain* c) {
+    if (c->V > (size_t)1 << 30) {
+        ddn_set_error("ddn_p25_chain_create: %zu voice slots", c->V);
+        return DDN_EINVAL;
+    }
+    DdnPool tmp = {};
+    uint8_t *d_fr = nullptr, *d_fl = nullptr;
+    ddn_mbe_batch* one = nullptr;
+    int rc = DDN_ENOMEM;
+    if (tmp.alloc(&d_fr, 184) && tmp.alloc(&d_fl, 1) && hipMemset(d_fl, 0xFF, 1) == hipSuccess) {
+        rc = ddn_mbe_frame_decode_batch(DDN_MBE_IMBE_7200X4400, d_fr, nullptr, 1, c->d_dead->bits, c->d_dead->res, nullptr);
+        if (rc == DDN_OK) {
+            rc = ddn_mbe_result_skip_batch(d_fl, 1, c->d_dead->res, nullptr);
+        }
+        if (rc == DDN_OK && c->cfg.vocoder && (rc = ddn_mbe_batch_create(DDN_MBE_IMBE_7200X4400, 1, &one)) == DDN_OK
+            && (rc = ddn_mbe_batch_set_p25p1_tail_rule(one, 1)) == DDN_OK) {
+            rc = ddn_mbe_synth_batch(one, c->d_dead->bits, c->d_dead->res, 1, c->d_dead->pcm, c->d_dead->res_out, nullptr);
+        }
+    }
+    const size_t V = c->V;
+    if (rc == DDN_OK
+        && (hipMemset(c->d_was_bits, 1, V) != hipSuccess || hipMemset(c->d_was_res, 1, V) != hipSuccess
+            || hipMemset(c->d_was_sres, 1, V) != hipSuccess)) {
+        rc = DDN_EHIP;
+    }
+    for (int k = 0; k < NSET && rc == DDN_OK; k++) {
+        const DdnVoiceLive a = chain_voice_live_args(c, k);
+        if (hipMemset(c->d_was_pcm[k], 1, V) != hipSuccess || ddn_dev_voice_live_fill(&a, nullptr) != hipSuccess) {
+            rc = DDN_EHIP;
+        }
+    }
+    if (hipDeviceSynchronize() != hipSuccess && rc == DDN_OK) {
+        rc = DDN_EHIP;
+    }
+    ddn_mbe_batch_destroy(one);
+    tmp.release();
+    return rc;
+}
+
 extern "C" int
 ddn_p25_chain_create(const ddn_p25_chain_config* cfg, ddn_p25_chain** out) {
     if (!cfg || !out || cfg->n_channels <= 0 || cfg->samples_per_call <= 0 || cfg->block_len <= 0) {
@@ -315,7 +393,8 @@ ddn_p25_chain_create(const ddn_p25_chain_config* cfg, ddn_p25_chain** out) {
             ok = m.alloc(&c->d_rec[k], B * c->stride * 10) && m.alloc(&c->d_fl[k], B * c->stride) && m.alloc(&c->d_new[k], B)
                  && m.alloc(&c->d_ev[k], B * (size_t)c->E * 4) && m.alloc(&c->d_nev[k], B) && m.alloc(&c->d_evd[k], B * (size_t)c->E * 4)
                  && m.alloc(&c->d_evl[k], B * (size_t)c->EL * 4) && m.alloc(&c->d_evdl[k], B * (size_t)c->EL * 4) && m.alloc(&c->d_nevl[k], B)
-                 && m.alloc(&c->d_cnt_full[k], B) && m.alloc(&c->d_nid[k], S * 4) && m.alloc(&c->d_tsbk[k], 3 * S * 12) && m.alloc(&c->d_pcm[k], V * 160);
+                 && m.alloc(&c->d_cnt_full[k], B) && m.alloc(&c->d_nid[k], S * 4) && m.alloc(&c->d_tsbk[k], 3 * S * 12) && m.alloc(&c->d_pcm[k], V * 160)
+                 && m.alloc(&c->d_live[k], V) && m.alloc(&c->d_nlive[k], 1) && m.alloc(&c->d_was_pcm[k], V);
         }
         ok = ok && m.alloc(&c->d_cnt_scan, B) && m.alloc(&c->d_cls, S) && m.alloc(&c->d_lists, S * DDN_LIST_COUNT) && m.alloc(&c->d_list_n, 8)
              && m.alloc(&c->d_tsbk_crc, 3 * S) && m.alloc(&c->d_words[0], S * 240)
@@ -335,10 +414,15 @@ ddn_p25_chain_create(const ddn_p25_chain_config* cfg, ddn_p25_chain** out) {
              && m.alloc(&c->d_pdu_metric, B * (size_t)c->PF * (size_t)c->PB) && m.alloc(&c->d_pdu_llr, B * (size_t)c->PF * (size_t)c->PB * 196)
              && m.alloc(&c->d_pdu_wanted, B * (size_t)c->PF * (size_t)c->PB) && m.alloc(&c->d_pdu_cand, B * (size_t)c->PF * (size_t)c->PB * 8 * 24)
              && m.alloc(&c->d_pdu_blocks18, B * (size_t)c->PF * (size_t)c->PB * 18) && m.alloc(&c->d_pdu_crc9, B * (size_t)c->PF * (size_t)c->PB)
-             && m.alloc(&c->d_pdu_cnt, B * (size_t)c->PF * (size_t)c->PB) && m.alloc(&c->d_pdu_hllr, B * (size_t)c->PF * 196);
+             && m.alloc(&c->d_pdu_cnt, B * (size_t)c->PF * (size_t)c->PB) && m.alloc(&c->d_pdu_hllr, B * (size_t)c->PF * 196)
+             && m.alloc(&c->d_live_off, B + 1) && m.alloc(&c->d_dead, 1) && m.alloc(&c->d_was_bits, V) && m.alloc(&c->d_was_res, V)
+             && m.alloc(&c->d_was_sres, V);
         if (!ok) {
             ddn_set_error("ddn_p25_chain_create: device allocation failed");
             rc = DDN_ENOMEM;
+            break;
+        }
+        if ((rc = chain_voice_dead_init(c)) != DDN_OK) {
             break;
         }
         if (hipStreamCreateWithPriority(&c->s_main, hipStreamNonBlocking, -1) != hipSuccess
@@ -915,11 +999,17 @@ chain_decode(ddn_p25_chain* c, int cur, int flush, hipStream_t st, hipEvent_t ev
         c->want_rec2 = 0;
     }
     // voice: nine IMBE frames per LDU
-    DDN_TRY(ddn_p25p1_framer_voice_index(c->fr, c->d_nid[cur], c->d_cnt_full[cur], c->Fv, stride, c->d_first, c->d_sc, c->d_nldu, vst));
-    DDN_TRY(ddn_p25p1_imbe_deinterleave_batch(rec, (size_t)c->B * stride, c->d_first, c->d_sc, V, c->d_imbe_fr, c->d_imbe_soft,
-                                              c->d_imbe_fl, c->d_sc_out, vst));
-    DDN_TRY(ddn_mbe_frame_decode_batch(DDN_MBE_IMBE_7200X4400, c->d_imbe_fr, nullptr, V, c->d_imbe_d, c->d_imbe_res, vst));
-    DDN_TRY(ddn_mbe_result_skip_batch(c->d_imbe_fl, V, c->d_imbe_res, vst));
+    // - of the live slots only: the index leaves their count per channel, k_voice_live_fill makes this set's list of them (and puts
+    // the dead pattern back where a slot was live the last time and is not now), every kernel behind it walks that list
+    DDN_TRY(ddn_p25p1_framer_voice_live(c->fr, c->d_nid[cur], c->d_cnt_full[cur], c->Fv, stride, c->d_first, c->d_sc, c->d_nldu, c->d_live_off,
+                                        c->d_nlive[cur], vst));
+    {
+        const DdnVoiceLive a = chain_voice_live_args(c, cur);
+        HIP_TRY(ddn_dev_voice_live_fill(&a, vst));
+    }
+    DDN_TRY(ddn_p25p1_imbe_deinterleave_live(rec, (size_t)c->B * stride, c->d_first, c->d_sc, V, c->d_live[cur], c->d_nlive[cur], c->d_imbe_fr,
+                                             c->d_imbe_soft, c->d_imbe_fl, c->d_sc_out, vst));
+    DDN_TRY(ddn_mbe_frame_decode_live(c->d_imbe_fr, c->d_imbe_fl, V, c->d_live[cur], c->d_nlive[cur], c->d_imbe_d, c->d_imbe_res, vst));
     if (ev_pre) { // frame FEC (st) + the voice stage so far (vst): what the next call's receive loop waits for
         if (vst != st) {
             HIP_TRY(hipEventRecord(c->ev_join_a, vst));
@@ -930,7 +1020,7 @@ chain_decode(ddn_p25_chain* c, int cur, int flush, hipStream_t st, hipEvent_t ev
     if (defer_synth && vst != st && ev_pre && c->cfg.vocoder) { // the synthesis kernel: queued by chain_issue_deferred (the next call)
         // the parameter kernel stays here, ahead of the loop: one wave per talk path with the frame-to-frame recurrence - it is
         // latency-bound and lives on occupancy; beside the loop one wave per SIMD fits and it took 5.5 ms instead of 0.65
-        DDN_TRY(ddn_mbe_params_only(c->mbe, c->d_imbe_d, c->d_imbe_res, (size_t)c->Fv * 9, c->d_res_out, vst));
+        DDN_TRY(ddn_mbe_params_only(c->mbe, c->d_imbe_d, c->d_imbe_res, (size_t)c->Fv * 9, c->d_nldu, c->d_res_out, vst));
         HIP_TRY(hipEventRecord(c->ev_join_a, vst));
         HIP_TRY(hipStreamWaitEvent(st, c->ev_join_a, 0));
         HIP_TRY(hipEventRecord(ev_pre, st)); // (again: the loop of the next call also waits for the parameter kernel)
@@ -940,7 +1030,8 @@ chain_decode(ddn_p25_chain* c, int cur, int flush, hipStream_t st, hipEvent_t ev
         return DDN_OK;
     }
     if (c->cfg.vocoder) {
-        DDN_TRY(ddn_mbe_synth_batch(c->mbe, c->d_imbe_d, c->d_imbe_res, (size_t)c->Fv * 9, c->d_pcm[cur], c->d_res_out, vst));
+        DDN_TRY(ddn_mbe_synth_batch_live(c->mbe, c->d_imbe_d, c->d_imbe_res, (size_t)c->Fv * 9, c->d_nldu, c->d_live[cur], c->d_nlive[cur],
+                                         c->d_pcm[cur], c->d_res_out, vst));
     }
     if (vst != st) {
         HIP_TRY(hipEventRecord(c->ev_join, vst));
@@ -968,7 +1059,7 @@ chain_issue_deferred(ddn_p25_chain* c, hipEvent_t gate) {
         HIP_TRY(hipStreamWaitEvent(c->s_voice, gate, 0));
     }
     if (c->cfg.vocoder) {
-        DDN_TRY(ddn_mbe_synth_only(c->mbe, (size_t)c->Fv * 9, c->d_pcm[set], c->s_voice));
+        DDN_TRY(ddn_mbe_synth_only(c->mbe, (size_t)c->Fv * 9, c->d_live[set], c->d_nlive[set], c->d_pcm[set], c->s_voice));
         if (c->deferred_dense) {
             const size_t V = c->V;
             HIP_TRY(ddn_dev_chain_pcm_compact(c->d_imbe_res, c->d_pcm[set], (int)V, (long)V, c->d_pcm_bcnt, c->d_pcm_boff, c->d_pcm_dense[set],

@@ -1243,6 +1243,20 @@ ddn_p25p1_imbe_deinterleave_batch(const uint8_t* d_records10, size_t n_records, 
     return DDN_OK;
 }
 
+// internal (ddn_internal.h): the same over a live list of slots - the chain object's form
+extern "C" int
+ddn_p25p1_imbe_deinterleave_live(const uint8_t* d_records10, size_t n_records, const int64_t* d_first_record, const int32_t* d_status_count,
+                                 size_t n_slots, const int32_t* d_live_slot, const int32_t* d_n_live, uint8_t* d_imbe_fr, uint8_t* d_imbe_soft,
+                                 uint8_t* d_flags, int32_t* d_status_count_out, void* hip_stream) {
+    DDN_TRY(check_imbe_deinterleave(__func__, d_records10, d_first_record, d_status_count, d_imbe_fr, d_imbe_soft, d_flags, d_status_count_out));
+    if (!d_live_slot || !d_n_live || n_slots > (size_t)1 << 30) {
+        return ddn_bad_argument(__func__);
+    }
+    HIP_TRY(ddn_dev_imbe_deinterleave_live(d_records10, (long)n_records, d_first_record, d_status_count, (int)n_slots, d_live_slot, d_n_live,
+                                           d_imbe_fr, d_imbe_soft, d_flags, d_status_count_out, (hipStream_t)hip_stream));
+    return DDN_OK;
+}
+
 extern "C" int
 ddn_p25p1_imbe_deinterleave_host(const uint8_t* records10, size_t n_records, const int64_t* first_record,
                                  const int32_t* status_count, size_t n_frames, uint8_t* imbe_fr, uint8_t* imbe_soft,

@@ -217,8 +217,25 @@ ddn_p25p1_framer_voice_index(ddn_p25p1_framer* f, const int32_t* d_nid4, const i
         return DDN_EINVAL;
     }
     HIP_TRY(ddn_dev_voice_index(f->d_sync_pos, f->d_n_syncs, d_nid4, d_counts, f->n_channels, f->max_frames, max_ldu_per_channel,
-                                max_symbols, f->d_first9, f->d_status9, d_first_record, d_status_count, d_n_ldu,
+                                max_symbols, f->d_first9, f->d_status9, d_first_record, d_status_count, d_n_ldu, 1,
                                 (hipStream_t)hip_stream));
+    return DDN_OK;
+}
+
+// internal (ddn_internal.h): the chain object's form - the same index for the channels' LDUs, the slots behind them left alone
+// (nothing of the chain's reads them), plus the prefix sums of the live slots per channel and their total
+extern "C" int
+ddn_p25p1_framer_voice_live(ddn_p25p1_framer* f, const int32_t* d_nid4, const int32_t* d_counts, int max_ldu_per_channel, size_t max_symbols,
+                            int64_t* d_first_record, int32_t* d_status_count, int32_t* d_n_ldu, int32_t* d_live_off, int32_t* d_n_live,
+                            void* hip_stream) {
+    if (!f || !d_nid4 || !d_counts || max_ldu_per_channel <= 0 || !d_first_record || !d_status_count || !d_n_ldu || !d_live_off || !d_n_live) {
+        ddn_set_error("ddn_p25p1_framer_voice_live: bad argument");
+        return DDN_EINVAL;
+    }
+    HIP_TRY(ddn_dev_voice_index(f->d_sync_pos, f->d_n_syncs, d_nid4, d_counts, f->n_channels, f->max_frames, max_ldu_per_channel,
+                                max_symbols, f->d_first9, f->d_status9, d_first_record, d_status_count, d_n_ldu, 0,
+                                (hipStream_t)hip_stream));
+    HIP_TRY(ddn_dev_voice_live_scan(d_n_ldu, f->n_channels, max_ldu_per_channel, d_live_off, d_n_live, (hipStream_t)hip_stream));
     return DDN_OK;
 }
 

@@ -176,10 +176,12 @@ ddn_mbe_batch_set_p25p1_tail_rule(ddn_mbe_batch* b, int enable) {
     return DDN_OK;
 }
 
-extern "C" int
-ddn_mbe_synth_batch(ddn_mbe_batch* b, const uint8_t* d_bits, const int32_t* d_result_in, size_t n_frames, float* d_pcm,
-                    int32_t* d_result_out, void* hip_stream) {
-    if (!b || (n_frames && (!d_bits || !d_pcm)) || n_frames > (size_t)1 << 24) {
+// parameter kernel + synthesis on one stream, timed when the object's timing is on.  d_live_slot set (with d_n_ldu, d_n_live): the
+// chain object's form over the live frames of a call (ddn_mbe_synth_batch_live below), else every slot
+static int
+synth_batch(ddn_mbe_batch* b, const uint8_t* d_bits, const int32_t* d_result_in, size_t n_frames, const int32_t* d_n_ldu,
+            const int32_t* d_live_slot, const int32_t* d_n_live, float* d_pcm, int32_t* d_result_out, void* hip_stream) {
+    if (!b || (n_frames && (!d_bits || !d_pcm)) || n_frames > (size_t)1 << 24 || (d_live_slot && (!d_n_ldu || !d_n_live))) {
         ddn_set_error("ddn_mbe_synth_batch: bad argument");
         return DDN_EINVAL;
     }
@@ -199,11 +201,15 @@ ddn_mbe_synth_batch(ddn_mbe_batch* b, const uint8_t* d_bits, const int32_t* d_re
         HIP_TRY(hipEventRecord(b->ev[0], st));
     }
     HIP_TRY(ddn_dev_mbe_params(b->codec, d_bits, d_result_in, b->n_streams, (int)n_frames, b->d_tables, b->d_half_log2,
-                               b->d_streams, b->tail_rule, b->d_recs, d_result_out, st));
+                               b->d_streams, b->tail_rule, b->d_recs, d_result_out, d_live_slot ? d_n_ldu : nullptr, st));
     if (b->timing) {
         HIP_TRY(hipEventRecord(b->ev[1], st));
     }
-    HIP_TRY(ddn_dev_mbe_synth(b->d_recs, (size_t)b->n_streams * n_frames, d_pcm, st));
+    if (d_live_slot) {
+        HIP_TRY(ddn_dev_mbe_synth_live(b->d_recs, (int)((size_t)b->n_streams * n_frames), d_live_slot, d_n_live, d_pcm, st));
+    } else {
+        HIP_TRY(ddn_dev_mbe_synth(b->d_recs, (size_t)b->n_streams * n_frames, d_pcm, st));
+    }
     if (b->timing) {
         HIP_TRY(hipEventRecord(b->ev[2], st));
         HIP_TRY(hipEventSynchronize(b->ev[2]));
@@ -213,12 +219,32 @@ ddn_mbe_synth_batch(ddn_mbe_batch* b, const uint8_t* d_bits, const int32_t* d_re
     return DDN_OK;
 }
 
+extern "C" int
+ddn_mbe_synth_batch(ddn_mbe_batch* b, const uint8_t* d_bits, const int32_t* d_result_in, size_t n_frames, float* d_pcm,
+                    int32_t* d_result_out, void* hip_stream) {
+    return synth_batch(b, d_bits, d_result_in, n_frames, nullptr, nullptr, nullptr, d_pcm, d_result_out, hip_stream);
+}
+
+// internal (ddn_internal.h): ddn_mbe_synth_batch over the live frames of a call - a talk path walks its first 9 * d_n_ldu [path]
+// slots, the synthesis the live list; a slot outside them is not written (result words, record, PCM)
+extern "C" int
+ddn_mbe_synth_batch_live(ddn_mbe_batch* b, const uint8_t* d_bits, const int32_t* d_result_in, size_t n_frames, const int32_t* d_n_ldu,
+                         const int32_t* d_live_slot, const int32_t* d_n_live, float* d_pcm, int32_t* d_result_out, void* hip_stream) {
+    if (!d_live_slot) {
+        ddn_set_error("ddn_mbe_synth_batch_live: bad argument");
+        return DDN_EINVAL;
+    }
+    return synth_batch(b, d_bits, d_result_in, n_frames, d_n_ldu, d_live_slot, d_n_live, d_pcm, d_result_out, hip_stream);
+}
+
 // internal (ddn_internal.h): the two kernels of ddn_mbe_synth_batch as separate calls - the chain object runs the parameter kernel
 // (one wave per talk path, latency-bound, wants occupancy) ahead of the next call's receive loop and the synthesis kernel (16
-// registers, no LDS, throughput-bound) beside it.  Same order on one stream = ddn_mbe_synth_batch.
+// registers, no LDS, throughput-bound) beside it.  Same order on one stream = ddn_mbe_synth_batch - over the live frames only:
+// d_n_ldu [n_streams] (null = every slot) bounds a talk path's walk to its first 9 * n_ldu slots, and the synthesis takes the
+// call's live list.  A slot outside them is not written: neither its result words nor its record nor its PCM.
 extern "C" int
-ddn_mbe_params_only(ddn_mbe_batch* b, const uint8_t* d_bits, const int32_t* d_result_in, size_t n_frames, int32_t* d_result_out,
-                    void* hip_stream) {
+ddn_mbe_params_only(ddn_mbe_batch* b, const uint8_t* d_bits, const int32_t* d_result_in, size_t n_frames, const int32_t* d_n_ldu,
+                    int32_t* d_result_out, void* hip_stream) {
     if (!b || (n_frames && !d_bits) || n_frames > (size_t)1 << 24) {
         ddn_set_error("ddn_mbe_params_only: bad argument");
         return DDN_EINVAL;
@@ -236,20 +262,33 @@ ddn_mbe_params_only(ddn_mbe_batch* b, const uint8_t* d_bits, const int32_t* d_re
         b->rec_frames = n_frames;
     }
     HIP_TRY(ddn_dev_mbe_params(b->codec, d_bits, d_result_in, b->n_streams, (int)n_frames, b->d_tables, b->d_half_log2, b->d_streams,
-                               b->tail_rule, b->d_recs, d_result_out, st));
+                               b->tail_rule, b->d_recs, d_result_out, d_n_ldu, st));
     return DDN_OK;
 }
 
 extern "C" int
-ddn_mbe_synth_only(ddn_mbe_batch* b, size_t n_frames, float* d_pcm, void* hip_stream) {
-    if (!b || (n_frames && !d_pcm) || n_frames > b->rec_frames) {
+ddn_mbe_synth_only(ddn_mbe_batch* b, size_t n_frames, const int32_t* d_live_slot, const int32_t* d_n_live, float* d_pcm, void* hip_stream) {
+    if (!b || (n_frames && !d_pcm) || n_frames > b->rec_frames || !d_live_slot || !d_n_live) {
         ddn_set_error("ddn_mbe_synth_only: bad argument");
         return DDN_EINVAL;
     }
     if (n_frames == 0) {
         return DDN_OK;
     }
-    HIP_TRY(ddn_dev_mbe_synth(b->d_recs, (size_t)b->n_streams * n_frames, d_pcm, (hipStream_t)hip_stream));
+    HIP_TRY(ddn_dev_mbe_synth_live(b->d_recs, (int)((size_t)b->n_streams * n_frames), d_live_slot, d_n_live, d_pcm, (hipStream_t)hip_stream));
+    return DDN_OK;
+}
+
+// internal: ddn_mbe_frame_decode_batch (IMBE, hard input) + ddn_mbe_result_skip_batch over a live list of slots
+extern "C" int
+ddn_mbe_frame_decode_live(const uint8_t* d_frames, const uint8_t* d_skip, size_t n_slots, const int32_t* d_live_slot, const int32_t* d_n_live,
+                          uint8_t* d_bits, int32_t* d_result, void* hip_stream) {
+    if (n_slots > (size_t)1 << 30 || (n_slots && (!d_frames || !d_skip || !d_live_slot || !d_n_live || !d_bits || !d_result))) {
+        ddn_set_error("ddn_mbe_frame_decode_live: bad argument");
+        return DDN_EINVAL;
+    }
+    HIP_TRY(ddn_dev_mbe_frame_decode_live(d_frames, (int)n_slots, d_live_slot, d_n_live, d_bits, d_result, (hipStream_t)hip_stream));
+    HIP_TRY(ddn_dev_mbe_result_skip_live(d_skip, (int)n_slots, d_live_slot, d_n_live, d_result, (hipStream_t)hip_stream));
     return DDN_OK;
 }
 

@@ -1014,6 +1014,74 @@ ddn_dev_chain_pcm_compact(const int32_t* result5, const float* pcm, int n_slots,
     return hipGetLastError();
 }
 
+// The live list of a call and the dead-slot contract of the voice stage.  One thread per voice slot:
+//  - a live slot (one of the first 9 * n_ldu of its channel) writes its number into the dense list, at the channel's prefix sum
+//    (k_voice_live_scan) + its place in the channel: the list is in slot order;
+//  - per result array, a slot that is dead now and was live when that array was last written gets the dead pattern back - what the
+//    whole-array kernels used to leave in a slot without a frame - and the slot's "live last time" byte is brought up to date.
+//    In steady traffic the same slots stay live and nothing is stored.
+// Single-wave workgroups, as everything on the voice stream: they find room beside the front-end kernel of the next call at once
+// (with 256 threads this kernel waited 1.8 ms for CUs with four free wave slots).
+__global__ __launch_bounds__(64) void
+k_voice_live_fill(const DdnVoiceLive a) {
+    const int v = blockIdx.x * 64 + threadIdx.x;
+    if (v >= a.n_slots) {
+        return;
+    }
+    const int per = a.max_ldu * 9;
+    const int ch = v / per, j = v - ch * per;
+    int k = a.n_ldu[ch];
+    k = k < 0 ? 0 : (k > a.max_ldu ? a.max_ldu : k);
+    const bool live = j < 9 * k;
+    if (live) {
+        const int at = a.live_off[ch] + j;
+        if (at >= 0 && at < a.n_slots) {
+            a.live_slot[at] = v;
+        }
+    }
+    const uint8_t now = live ? 1 : 0;
+    auto turned_dead = [&](uint8_t* was) { // true: the pattern is to be restored
+        if (!was || was[v] == now) {
+            return false;
+        }
+        was[v] = now;
+        return !live;
+    };
+    if (turned_dead(a.was_bits)) {
+        const uint64_t* s = reinterpret_cast<const uint64_t*>(a.dead->bits);
+        uint64_t* d = reinterpret_cast<uint64_t*>(a.bits + (size_t)v * 88);
+        for (int i = 0; i < 11; i++) {
+            d[i] = s[i];
+        }
+    }
+    if (turned_dead(a.was_res)) {
+        for (int i = 0; i < 5; i++) {
+            a.res[(size_t)v * 5 + i] = a.dead->res[i];
+        }
+    }
+    if (turned_dead(a.was_res_out)) {
+        for (int i = 0; i < 5; i++) {
+            a.res_out[(size_t)v * 5 + i] = a.dead->res_out[i];
+        }
+    }
+    if (turned_dead(a.was_pcm)) {
+        const float* s = a.dead->pcm;
+        float4* d = reinterpret_cast<float4*>(a.pcm + (size_t)v * 160); // (a slot's PCM is 640 bytes: aligned)
+        for (int i = 0; i < 40; i++) {
+            d[i] = make_float4(s[4 * i], s[4 * i + 1], s[4 * i + 2], s[4 * i + 3]);
+        }
+    }
+}
+
+extern "C" hipError_t
+ddn_dev_voice_live_fill(const DdnVoiceLive* a, hipStream_t st) {
+    if (a->n_slots <= 0 || a->max_ldu <= 0) {
+        return hipSuccess;
+    }
+    hipLaunchKernelGGL(k_voice_live_fill, dim3((unsigned)((a->n_slots + 63) / 64)), dim3(64), 0, st, *a);
+    return hipGetLastError();
+}
+
 extern "C" hipError_t
 ddn_dev_chain_pack2(const uint8_t* rec, const uint8_t* fl, size_t n, uint8_t* out2, hipStream_t st) {
     if (n == 0) {

@@ -292,7 +292,9 @@ hipError_t ddn_dev_rs_pack(const uint8_t* words, long n_slots, int n_words, int 
 hipError_t ddn_dev_tdulc_rs_pack(const uint8_t* words, long n_slots, uint8_t* data, uint8_t* parity, hipStream_t st);
 hipError_t ddn_dev_voice_index(const int32_t* sync_pos, const int32_t* n_syncs, const int32_t* nid4, const int32_t* counts, int n_channels,
                                int max_frames, int max_ldu, size_t max_sym, const int32_t* first9, const int32_t* status9,
-                               int64_t* first, int32_t* status, int32_t* n_ldu, hipStream_t st);
+                               int64_t* first, int32_t* status, int32_t* n_ldu, int fill_tail, hipStream_t st);
+// live voice slots: live_off [n_channels + 1] = prefix sums of 9 * n_ldu in channel order, *n_live = the total (a device word)
+hipError_t ddn_dev_voice_live_scan(const int32_t* n_ldu, int n_channels, int max_ldu, int32_t* live_off, int32_t* n_live, hipStream_t st);
 hipError_t ddn_dev_imbe_index(const int32_t* sync_pos, const int32_t* n_syncs, int n_channels, int max_frames,
                               size_t max_sym, const int32_t* first9, const int32_t* status9, int64_t* first,
                               int32_t* status, hipStream_t st);
@@ -301,6 +303,21 @@ hipError_t ddn_dev_resample(const float* in, long n, size_t in_stride, int n_cha
 hipError_t ddn_dev_imbe_deinterleave(const uint8_t* rec, long n_records, const int64_t* first, const int32_t* status_count,
                                      int n_frames, uint8_t* fr, uint8_t* soft, uint8_t* flags, int32_t* status_out,
                                      hipStream_t st);
+// The chain object's voice kernels walk the call's live list (live_slot [*n_live], k_voice_live_fill) by a grid that does not depend on
+// the count, which stays on the device: min(what the slots would need, a cap) single-wave workgroups, each striding through the list.
+// The caps, by how evenly a kernel's frames cost:
+//   de-interleave  every frame costs the same: one workgroup per wave slot of the device (256 CUs x 4 SIMDs x 8), ten frames each on
+//                  the bench shape
+//   frame decode   a pass of 32 frames costs the same: a workgroup per 32 slots up to the cap, so a pass each at most on the bench
+//                  shape (with fewer workgroups than passes some would take two where others take one)
+//   synthesis      a frame costs by its harmonics (9 .. 56) and voicing: few frames per workgroup, so that the dispatcher evens the
+//                  load out as it did with a workgroup per slot; a workgroup past the list's end leaves at once
+#define DDN_VOICE_LIVE_GRID        8192
+#define DDN_VOICE_LIVE_GRID_DECODE 16384
+#define DDN_VOICE_LIVE_GRID_SYNTH  65536
+hipError_t ddn_dev_imbe_deinterleave_live(const uint8_t* rec, long n_records, const int64_t* first, const int32_t* status_count, int n_slots,
+                                          const int32_t* live_slot, const int32_t* n_live, uint8_t* fr, uint8_t* soft, uint8_t* flags,
+                                          int32_t* status_out, hipStream_t st);
 hipError_t ddn_dev_r34_list(const uint8_t* dibits, const uint8_t* reliab, int n, int max_cand, uint8_t* backs,
                             uint32_t* cand, int32_t* count, hipStream_t st);
 /* The sparse forms below take `wanted` [n] (one byte per item, 0 = nobody reads this item; NULL = every item is wanted).  A wanted
@@ -414,6 +431,32 @@ ddn_sel_grid(const DdnSel* sel, unsigned long n_blocks_full) {
 }
 hipError_t ddn_dev_chain_pcm_compact(const int32_t* result5, const float* pcm, int n_slots, long capacity, int32_t* block_cnt,
                                      int32_t* block_off, float* dense, int32_t* slot_of, int32_t* total, hipStream_t st);
+/* what a voice slot without a frame holds in the chain object's result arrays: taken once, at create, from the kernels themselves
+ * (one all-zero IMBE frame with its skip flag through the frame decode, the parameter kernel and the synthesis) */
+typedef struct {
+    uint8_t bits[88];   /* d_imbe_bits: the decode of the all-zero frame */
+    int32_t res[5];     /* d_imbe_result: its result words, the skip flag or-ed in */
+    int32_t res_out[5]; /* d_synth_result: the silent record's result words */
+    int32_t pad;
+    float pcm[160];     /* d_pcm: the silent frame */
+} DdnVoiceDead;
+/* k_voice_live_fill: the live list of a call + the dead pattern back into the slots that left it.  was_*: one "live when this array
+ * was last written" byte per slot and array; an array that is not kept (null was_*) is left alone */
+typedef struct {
+    int n_slots, max_ldu;    /* n_slots = channels * max_ldu * 9 */
+    const int32_t* n_ldu;    /* [channels] */
+    const int32_t* live_off; /* [channels + 1] (k_voice_live_scan) */
+    int32_t* live_slot;      /* [n_slots] out: the first live_off[channels] entries */
+    const DdnVoiceDead* dead;
+    uint8_t *bits, *was_bits;
+    int32_t* res;
+    uint8_t* was_res;
+    int32_t* res_out;
+    uint8_t* was_res_out;
+    float* pcm;
+    uint8_t* was_pcm;
+} DdnVoiceLive;
+hipError_t ddn_dev_voice_live_fill(const DdnVoiceLive* a, hipStream_t st);
 hipError_t ddn_dev_chain_pack2(const uint8_t* rec, const uint8_t* fl, size_t n, uint8_t* out2, hipStream_t st);
 hipError_t ddn_dev_chain_carry(const uint8_t* rec_prev, const uint8_t* fl_prev, const int32_t* cnt_prev, int have_prev,
                                uint8_t* rec_cur, uint8_t* fl_cur, size_t stride_sym, int T, int n_channels, hipStream_t st);

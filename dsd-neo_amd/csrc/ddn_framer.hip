@@ -256,7 +256,7 @@ __global__ void
 k_voice_index(const int32_t* __restrict__ sync_pos, const int32_t* __restrict__ n_syncs, const int32_t* __restrict__ nid4,
               const int32_t* __restrict__ counts, int n_channels, int max_frames, int max_ldu, size_t max_sym, const int32_t* __restrict__ first9,
               const int32_t* __restrict__ status9, int64_t* __restrict__ first, int32_t* __restrict__ status,
-              int32_t* __restrict__ n_ldu) {
+              int32_t* __restrict__ n_ldu, int fill_tail) {
     const int ch = blockIdx.x * 64 + threadIdx.x;
     if (ch >= n_channels) {
         return;
@@ -283,7 +283,8 @@ k_voice_index(const int32_t* __restrict__ sync_pos, const int32_t* __restrict__ 
     if (n_ldu) {
         n_ldu[ch] = k;
     }
-    for (; k < max_ldu; k++) {
+    // (fill_tail = 0, the chain object: its voice kernels walk the live list below and never read a slot behind a channel's LDUs)
+    for (; fill_tail && k < max_ldu; k++) {
         for (int v = 0; v < 9; v++) {
             first[((size_t)ch * max_ldu + k) * 9 + v] = -1;
             status[((size_t)ch * max_ldu + k) * 9 + v] = 0;
@@ -296,11 +297,53 @@ extern "C" hipError_t
 ddn_dev_voice_index(const int32_t* sync_pos, const int32_t* n_syncs, const int32_t* nid4, const int32_t* counts,
                     int n_channels, int max_frames,
                     int max_ldu, size_t max_sym, const int32_t* first9, const int32_t* status9, int64_t* first,
-                    int32_t* status, int32_t* n_ldu, hipStream_t st) {
+                    int32_t* status, int32_t* n_ldu, int fill_tail, hipStream_t st) {
     if (n_channels <= 0 || max_ldu <= 0) {
         return hipSuccess;
     }
     hipLaunchKernelGGL(k_voice_index, dim3((unsigned)((n_channels + 63) / 64)), dim3(64), 0, st, sync_pos, n_syncs, nid4,
-                       counts, n_channels, max_frames, max_ldu, max_sym, first9, status9, first, status, n_ldu);
+                       counts, n_channels, max_frames, max_ldu, max_sym, first9, status9, first, status, n_ldu, fill_tail);
+    return hipGetLastError();
+}
+
+namespace {
+// The live voice slots of a call: a channel's are the first 9 * n_ldu of its max_ldu * 9.  One wavefront sums the per-channel
+// counts in channel order, 64 channels a round by wave shuffles: live_off[ch] = live slots of the channels before ch,
+// live_off[n_channels] = *n_live = their total.  (A single wave, no LDS: it finds room beside the front-end kernel of the next call
+// at once, where a four-wave workgroup waited 1.9 ms for a CU with four free slots.)  What walks the list (k_voice_live_fill writes
+// it) never launches by that total - it stays a device word.
+__global__ __launch_bounds__(64) void
+k_voice_live_scan(const int32_t* __restrict__ n_ldu, int n_channels, int max_ldu, int32_t* __restrict__ live_off,
+                  int32_t* __restrict__ n_live) {
+    const int t = threadIdx.x;
+    int run = 0;
+    for (int c0 = 0; c0 < n_channels; c0 += 64) {
+        const int ch = c0 + t;
+        int k = ch < n_channels ? n_ldu[ch] : 0;
+        k = k < 0 ? 0 : (k > max_ldu ? max_ldu : k);
+        const int mine = 9 * k;
+        int inc = mine; // inclusive sums over the lanes, log steps
+        for (int d = 1; d < 64; d <<= 1) {
+            const int a = __shfl_up(inc, d);
+            inc += t >= d ? a : 0;
+        }
+        if (ch < n_channels) {
+            live_off[ch] = run + inc - mine;
+        }
+        run += __shfl(inc, 63);
+    }
+    if (t == 0) {
+        live_off[n_channels] = run;
+        *n_live = run;
+    }
+}
+} // namespace
+
+extern "C" hipError_t
+ddn_dev_voice_live_scan(const int32_t* n_ldu, int n_channels, int max_ldu, int32_t* live_off, int32_t* n_live, hipStream_t st) {
+    if (n_channels <= 0 || max_ldu <= 0) {
+        return hipSuccess;
+    }
+    hipLaunchKernelGGL(k_voice_live_scan, dim3(1), dim3(64), 0, st, n_ldu, n_channels, max_ldu, live_off, n_live);
     return hipGetLastError();
 }

@@ -16,15 +16,13 @@
 #include "ddn_device.h"
 
 namespace {
-__global__ __launch_bounds__(64) void
-k_imbe_deinterleave(const uint8_t* __restrict__ rec, long n_records, const int64_t* __restrict__ first,
-                    const int32_t* __restrict__ status_count, int n_frames, uint8_t* __restrict__ fr,
-                    uint8_t* __restrict__ soft, uint8_t* __restrict__ flags, int32_t* __restrict__ status_out) {
-    __shared__ uint8_t c0[23];
-    __shared__ int short_read;
-    const int f = blockIdx.x;
-    const int t0 = threadIdx.x; // one wavefront per frame, three passes over the 184 cells (a single-wave workgroup finds room beside
-                                // the front-end kernel of the next call, a three-wave one waited for it: DDN_WG, ddn_device.h)
+// one voice frame by one wavefront (called by every lane of a single-wave workgroup; c0 / short_read are the workgroup's)
+__device__ __forceinline__ void
+imbe_frame(const int f, const int t0, uint8_t* c0, int& short_read, const uint8_t* __restrict__ rec, long n_records, const int64_t* __restrict__ first,
+           const int32_t* __restrict__ status_count, uint8_t* __restrict__ fr, uint8_t* __restrict__ soft, uint8_t* __restrict__ flags,
+           int32_t* __restrict__ status_out) {
+    // t0 = the lane: one wavefront per frame, three passes over the 184 cells (a single-wave workgroup finds room beside the
+    // front-end kernel of the next call, a three-wave one waited for it: DDN_WG, ddn_device.h)
     if (t0 == 0) {
         short_read = 0;
     }
@@ -78,6 +76,39 @@ k_imbe_deinterleave(const uint8_t* __restrict__ rec, long n_records, const int64
         status_out[f] = s71 == 0 ? sc0 + 72 : (71 - (t1 + 35 * (s71 - 1))) + 1;
     }
 }
+
+__global__ __launch_bounds__(64) void
+k_imbe_deinterleave(const uint8_t* __restrict__ rec, long n_records, const int64_t* __restrict__ first,
+                    const int32_t* __restrict__ status_count, int n_frames, uint8_t* __restrict__ fr,
+                    uint8_t* __restrict__ soft, uint8_t* __restrict__ flags, int32_t* __restrict__ status_out) {
+    __shared__ uint8_t c0[23];
+    __shared__ int short_read;
+    imbe_frame(blockIdx.x, threadIdx.x, c0, short_read, rec, n_records, first, status_count, fr, soft, flags, status_out);
+}
+
+// The chain object's form: the frames of the live list only (live_slot [*n_live], slot numbers in slot order), each at its own slot
+// of the same per-slot arrays.  The grid is fixed - the count stays on the device - and every workgroup strides through the list.
+__global__ __launch_bounds__(64) void
+k_imbe_deinterleave_live(const uint8_t* __restrict__ rec, long n_records, const int64_t* __restrict__ first,
+                         const int32_t* __restrict__ status_count, int n_slots, const int32_t* __restrict__ live_slot,
+                         const int32_t* __restrict__ n_live, uint8_t* __restrict__ fr, uint8_t* __restrict__ soft,
+                         uint8_t* __restrict__ flags, int32_t* __restrict__ status_out) {
+    __shared__ uint8_t c0[23];
+    __shared__ int short_read;
+    int n = *n_live;
+    n = n < n_slots ? n : n_slots;
+#pragma nounroll
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        int f = __builtin_amdgcn_readfirstlane(live_slot[i]);
+        f = f < 0 ? 0 : (f >= n_slots ? n_slots - 1 : f); // clamped before any address is formed
+        // (the lane made opaque per frame: the compiler would otherwise keep every cell's schedule in registers across the frames -
+        // 23 of them; 18 this way, where k_imbe_deinterleave takes 15: profiles/voice_live_kernel_resources.txt)
+        int t0 = threadIdx.x;
+        asm volatile("" : "+v"(t0));
+        imbe_frame(f, t0, c0, short_read, rec, n_records, first, status_count, fr, soft, flags, status_out);
+        __syncthreads(); // (lane 0 has read c0 / short_read before the next frame's cells are written)
+    }
+}
 } // namespace
 
 extern "C" hipError_t
@@ -88,5 +119,18 @@ ddn_dev_imbe_deinterleave(const uint8_t* rec, long n_records, const int64_t* fir
     }
     hipLaunchKernelGGL(k_imbe_deinterleave, dim3((unsigned)n_frames), dim3(64), 0, st, rec, n_records, first,
                        status_count, n_frames, fr, soft, flags, status_out);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+ddn_dev_imbe_deinterleave_live(const uint8_t* rec, long n_records, const int64_t* first, const int32_t* status_count, int n_slots,
+                               const int32_t* live_slot, const int32_t* n_live, uint8_t* fr, uint8_t* soft, uint8_t* flags,
+                               int32_t* status_out, hipStream_t st) {
+    if (n_slots <= 0) {
+        return hipSuccess;
+    }
+    const int grid = n_slots < DDN_VOICE_LIVE_GRID ? n_slots : DDN_VOICE_LIVE_GRID;
+    hipLaunchKernelGGL(k_imbe_deinterleave_live, dim3((unsigned)grid), dim3(64), 0, st, rec, n_records, first, status_count, n_slots,
+                       live_slot, n_live, fr, soft, flags, status_out);
     return hipGetLastError();
 }

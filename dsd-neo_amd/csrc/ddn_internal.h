@@ -42,9 +42,24 @@ int ddn_fec_viterbi_k5_batch_wanted(const uint16_t* d_soft, size_t n, int in_len
                                     int out_stride, uint32_t* d_cost, const uint8_t* d_wanted, void* hip_stream);
 /* the two kernels of ddn_mbe_synth_batch as separate calls (ddn_api_mbe.cpp) */
 struct ddn_mbe_batch;
-int ddn_mbe_params_only(struct ddn_mbe_batch* b, const uint8_t* d_bits, const int32_t* d_result_in, size_t n_frames, int32_t* d_result_out,
-                        void* hip_stream);
-int ddn_mbe_synth_only(struct ddn_mbe_batch* b, size_t n_frames, float* d_pcm, void* hip_stream);
+int ddn_mbe_params_only(struct ddn_mbe_batch* b, const uint8_t* d_bits, const int32_t* d_result_in, size_t n_frames, const int32_t* d_n_ldu,
+                        int32_t* d_result_out, void* hip_stream);
+int ddn_mbe_synth_batch_live(struct ddn_mbe_batch* b, const uint8_t* d_bits, const int32_t* d_result_in, size_t n_frames, const int32_t* d_n_ldu,
+                             const int32_t* d_live_slot, const int32_t* d_n_live, float* d_pcm, int32_t* d_result_out, void* hip_stream);
+int ddn_mbe_synth_only(struct ddn_mbe_batch* b, size_t n_frames, const int32_t* d_live_slot, const int32_t* d_n_live, float* d_pcm,
+                       void* hip_stream);
+/* the chain object's voice stage over the live slots of a call: the voice index without the slots behind a channel's
+ * LDUs + the per-channel prefix sums of the live slots and their total, and the de-interleave / frame decode + skip flag over the
+ * list those make (ddn_dev_voice_live_fill, ddn_device.h) */
+struct ddn_p25p1_framer;
+int ddn_p25p1_framer_voice_live(struct ddn_p25p1_framer* f, const int32_t* d_nid4, const int32_t* d_counts, int max_ldu_per_channel,
+                                size_t max_symbols, int64_t* d_first_record, int32_t* d_status_count, int32_t* d_n_ldu, int32_t* d_live_off,
+                                int32_t* d_n_live, void* hip_stream);
+int ddn_p25p1_imbe_deinterleave_live(const uint8_t* d_records10, size_t n_records, const int64_t* d_first_record, const int32_t* d_status_count,
+                                     size_t n_slots, const int32_t* d_live_slot, const int32_t* d_n_live, uint8_t* d_imbe_fr,
+                                     uint8_t* d_imbe_soft, uint8_t* d_flags, int32_t* d_status_count_out, void* hip_stream);
+int ddn_mbe_frame_decode_live(const uint8_t* d_frames, const uint8_t* d_skip, size_t n_slots, const int32_t* d_live_slot,
+                              const int32_t* d_n_live, uint8_t* d_bits, int32_t* d_result, void* hip_stream);
 #ifdef __cplusplus
 }
 #endif

@@ -60,30 +60,14 @@ hamming_fix(uint32_t w, int& errs) {
 }
 
 #define DDN_MBE_FRAMES_PER_WG 32
+// one frame by one lane: f = its staged bytes, o = its staged parameter bits, r5 = its five result words (global)
 template <int CODEC>
-__global__ __launch_bounds__(64) void
-k_mbe_frame_decode(const uint8_t* __restrict__ frames, const uint8_t* __restrict__ soft, size_t n,
-                   uint8_t* __restrict__ bits_out, int32_t* __restrict__ result) {
-    constexpr int FB = CODEC == DDN_MBE_IMBE_7200X4400 ? 184 : 96; // bytes per frame
+__device__ __forceinline__ void
+frame_decode_lane(const uint8_t* f, uint8_t* o, int32_t* r5, bool soft_input) {
     constexpr int OB = CODEC == DDN_MBE_IMBE_7200X4400 ? 88 : 49;
     constexpr int ROWLEN = CODEC == DDN_MBE_IMBE_7200X4400 ? 23 : 24;
-    // 32 frames per workgroup, the Golay table read in place (8 KB: it stays in the L1): 8.7 KB of LDS per workgroup instead of 25.6,
-    // which fits beside the front-end kernel of the next call (153 KB of a CU's 160) - in the chain object this kernel is on the path
-    // the next receive loop waits for, and with 25.6 KB it waited for a front-end workgroup to end
-    constexpr int FPW = DDN_MBE_FRAMES_PER_WG;
-    __shared__ uint8_t stage[FPW * FB];
-    __shared__ uint8_t outb[FPW * OB];
     const uint32_t* tab = Golay23::v.e;
-    const int lane = threadIdx.x;
-    const size_t f0 = (size_t)blockIdx.x * FPW;
-    const size_t nf = (n - f0) < (size_t)FPW ? (n - f0) : (size_t)FPW;
-    const uint8_t* src = frames + f0 * FB;
-    for (size_t i = lane; i < nf * FB; i += 64) {
-        stage[i] = src[i];
-    }
-    __syncthreads();
-    if ((size_t)lane < nf) {
-        const uint8_t* f = stage + lane * FB;
+    {
         uint32_t row[8];
         bool bad = false;
         constexpr int NROW = CODEC == DDN_MBE_IMBE_7200X4400 ? 8 : 4;
@@ -97,9 +81,8 @@ k_mbe_frame_decode(const uint8_t* __restrict__ frames, const uint8_t* __restrict
             }
             row[r] = w;
         }
-        uint8_t* o = outb + lane * OB;
         int c0 = 0, c4 = 0, total = 0, e = 0;
-        unsigned flags = MBE_PROCESS_FLAG_C0_VALID | (soft ? MBE_PROCESS_FLAG_SOFT_INPUT : 0u);
+        unsigned flags = MBE_PROCESS_FLAG_C0_VALID | (soft_input ? MBE_PROCESS_FLAG_SOFT_INPUT : 0u);
         if (CODEC == DDN_MBE_IMBE_7200X4400) {
             flags |= MBE_PROCESS_FLAG_C4_VALID;
             row[0] = golay_fix(row[0], tab, c0);
@@ -170,7 +153,6 @@ k_mbe_frame_decode(const uint8_t* __restrict__ frames, const uint8_t* __restrict
                 o[k++] = (uint8_t)((row[3] >> j) & 1u);
             }
         }
-        int32_t* r5 = result + (f0 + lane) * 5;
         if (bad) { // a byte other than 0 / 1: MBE_STATUS_INVALID_BITS for this frame
             for (int k = 0; k < OB; k++) {
                 o[k] = 0;
@@ -185,10 +167,85 @@ k_mbe_frame_decode(const uint8_t* __restrict__ frames, const uint8_t* __restrict
             r5[4] = total - c0;
         }
     }
+}
+
+template <int CODEC>
+__global__ __launch_bounds__(64) void
+k_mbe_frame_decode(const uint8_t* __restrict__ frames, const uint8_t* __restrict__ soft, size_t n,
+                   uint8_t* __restrict__ bits_out, int32_t* __restrict__ result) {
+    constexpr int FB = CODEC == DDN_MBE_IMBE_7200X4400 ? 184 : 96; // bytes per frame
+    constexpr int OB = CODEC == DDN_MBE_IMBE_7200X4400 ? 88 : 49;
+    // 32 frames per workgroup, the Golay table read in place (8 KB: it stays in the L1): 8.7 KB of LDS per workgroup instead of 25.6,
+    // which fits beside the front-end kernel of the next call (153 KB of a CU's 160) - in the chain object this kernel is on the path
+    // the next receive loop waits for, and with 25.6 KB it waited for a front-end workgroup to end
+    constexpr int FPW = DDN_MBE_FRAMES_PER_WG;
+    __shared__ uint8_t stage[FPW * FB];
+    __shared__ uint8_t outb[FPW * OB];
+    const int lane = threadIdx.x;
+    const size_t f0 = (size_t)blockIdx.x * FPW;
+    const size_t nf = (n - f0) < (size_t)FPW ? (n - f0) : (size_t)FPW;
+    const uint8_t* src = frames + f0 * FB;
+    for (size_t i = lane; i < nf * FB; i += 64) {
+        stage[i] = src[i];
+    }
+    __syncthreads();
+    if ((size_t)lane < nf) {
+        frame_decode_lane<CODEC>(stage + lane * FB, outb + lane * OB, result + (f0 + lane) * 5, soft != nullptr);
+    }
     __syncthreads();
     uint8_t* dst = bits_out + f0 * OB;
     for (size_t i = lane; i < nf * OB; i += 64) {
         dst[i] = outb[i];
+    }
+}
+
+// The chain object's form (IMBE, hard input): the frames of the live list (live_slot [*n_live]), 32 list entries per pass of a
+// workgroup - a lane per frame, filled from the list, so a pass is full but for the list's last one - read from and written to the
+// frames' own slots of the per-slot arrays.  Fixed grid, the passes strided; the same 8.7 KB of LDS.
+// (amdgpu_waves_per_eu: held to the 168 registers - three waves per SIMD - of k_mbe_frame_decode; no scratch)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void
+k_mbe_frame_decode_live(const uint8_t* __restrict__ frames, int n_slots, const int32_t* __restrict__ live_slot,
+                        const int32_t* __restrict__ n_live, uint8_t* __restrict__ bits_out, int32_t* __restrict__ result) {
+    constexpr int FB = 184, OB = 88, FPW = DDN_MBE_FRAMES_PER_WG;
+    __shared__ uint8_t stage[FPW * FB];
+    __shared__ uint8_t outb[FPW * OB];
+    int n = *n_live;
+    n = n < n_slots ? n : n_slots;
+    auto slot_of = [&](int i) { // clamped before any address is formed
+        const int v = live_slot[i];
+        return (size_t)(v < 0 ? 0 : (v >= n_slots ? n_slots - 1 : v));
+    };
+    for (int i0 = blockIdx.x * FPW; i0 < n; i0 += gridDim.x * FPW) {
+        int lane = threadIdx.x; // (opaque per pass: nothing of a lane's decode is kept in registers across the passes)
+        asm volatile("" : "+v"(lane));
+        const int nf = (n - i0) < FPW ? (n - i0) : FPW;
+        // lane k's slot: one list read per pass and side of the decode (not held across it), handed round by __shfl
+        int mine = (int)slot_of(i0 + (lane < nf ? lane : nf - 1));
+        for (int k = 0; k < nf; k++) {
+            const uint8_t* src = frames + (size_t)__shfl(mine, k) * FB;
+            for (int b = lane; b < FB; b += 64) {
+                stage[k * FB + b] = src[b];
+            }
+        }
+        __syncthreads();
+        if (lane < nf) {
+            // the five result words go out through the lane's own staged frame, which it has read by then (184 = 8 x 23 bytes)
+            frame_decode_lane<DDN_MBE_IMBE_7200X4400>(stage + lane * FB, outb + lane * OB, reinterpret_cast<int32_t*>(stage + lane * FB), false);
+        }
+        __syncthreads();
+        asm volatile("" : "+v"(lane));
+        mine = (int)slot_of(i0 + (lane < nf ? lane : nf - 1));
+        for (int k = 0; k < nf; k++) {
+            const size_t v = (size_t)__shfl(mine, k);
+            uint8_t* dst = bits_out + v * OB;
+            for (int b = lane; b < OB; b += 64) {
+                dst[b] = outb[k * OB + b];
+            }
+            if (lane < 5) {
+                result[v * 5 + lane] = reinterpret_cast<const int32_t*>(stage + k * FB)[lane];
+            }
+        }
+        __syncthreads();
     }
 }
 
@@ -277,19 +334,26 @@ template <int CODEC>
 __global__ __launch_bounds__(64) void
 k_mbe_params(const uint8_t* __restrict__ bits, const int32_t* __restrict__ res_in, int n_frames,
              const ddn_mbe_tables* __restrict__ T, const float* __restrict__ half_log2, DdnMbeStream* __restrict__ streams,
-             int tail_rule, DdnMbeFrameRec* __restrict__ recs, int32_t* __restrict__ res_out) {
+             int tail_rule, DdnMbeFrameRec* __restrict__ recs, int32_t* __restrict__ res_out, const int32_t* __restrict__ n_ldu) {
     constexpr int NB = CODEC == DDN_MBE_IMBE_7200X4400 ? 88 : 49;
     __shared__ uint32_t fld[64];
     __shared__ float sG[12], sR[12], sC[64], sPl[64], sA[64], sB[64];
     __shared__ float sCb[5][64]; // AMBE: per-block coefficient rows (1-based)
     const int s = blockIdx.x;
     const int l = threadIdx.x;
+    // n_ldu (the chain object): a talk path's frames of this call are the first 9 * n_ldu [s] of its n_frames slots; the slots behind
+    // them hold no frame (there the walk below would find the skip flag, write the silent record and leave the history alone), and a
+    // path without a frame leaves before it has loaded anything - its carried state stays as it is, frame_no included
+    const int n_walk = n_ldu ? (9 * n_ldu[s] < n_frames ? 9 * n_ldu[s] : n_frames) : n_frames;
+    if (n_walk <= 0) {
+        return;
+    }
     DdnMbeStream* st = streams + s;
     LaneParms cur = lane_load(&st->cur, l), prev = lane_load(&st->prev, l), enh = lane_load(&st->enh, l);
     uint32_t frame_no = st->frame_no;
     const uint32_t seed = st->seed;
 
-    for (int f = 0; f < n_frames; f++) {
+    for (int f = 0; f < n_walk; f++) {
         const size_t fi = (size_t)s * (size_t)n_frames + (size_t)f;
         const uint8_t* d = bits + fi * NB;
         int32_t r[5] = {0, 0, 0, 0, 0};
@@ -700,11 +764,9 @@ unvoiced_mix(float w0, float w0l, int l, int n, uint32_t base, uint32_t tag) {
     return c3;
 }
 
-__global__ __launch_bounds__(64) void
-k_mbe_synth(const DdnMbeFrameRec* __restrict__ recs, float* __restrict__ pcm) {
-    const DdnMbeFrameRec* rec = recs + blockIdx.x;
-    float* out = pcm + (size_t)blockIdx.x * 160;
-    const int lane = threadIdx.x;
+// one frame by one wavefront
+__device__ __forceinline__ void
+synth_frame(const DdnMbeFrameRec* __restrict__ rec, float* __restrict__ out, const int lane) {
     const int maxl = rec->maxl;
     float acc[3] = {0.0f, 0.0f, 0.0f};
     if (!(rec->flags & DDN_MBE_REC_SILENCE)) {
@@ -764,11 +826,48 @@ k_mbe_synth(const DdnMbeFrameRec* __restrict__ recs, float* __restrict__ pcm) {
     }
 }
 
+__global__ __launch_bounds__(64) void
+k_mbe_synth(const DdnMbeFrameRec* __restrict__ recs, float* __restrict__ pcm) {
+    synth_frame(recs + blockIdx.x, pcm + (size_t)blockIdx.x * 160, threadIdx.x);
+}
+
+// The chain object's form: the frames of the live list (live_slot [*n_live]) at their own slots, fixed grid, strided
+__global__ __launch_bounds__(64) void
+k_mbe_synth_live(const DdnMbeFrameRec* __restrict__ recs, int n_slots, const int32_t* __restrict__ live_slot,
+                 const int32_t* __restrict__ n_live, float* __restrict__ pcm) {
+    int n = *n_live;
+    n = n < n_slots ? n : n_slots;
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        int v = __builtin_amdgcn_readfirstlane(live_slot[i]); // (wave-uniform: the record's fields stay scalar loads)
+        v = v < 0 ? 0 : (v >= n_slots ? n_slots - 1 : v); // clamped before any address is formed
+        // (the lane made opaque per frame: the window values of a lane's three samples are worked out per frame as in k_mbe_synth, not
+        // kept across the loop.  32 registers where k_mbe_synth takes 30: the same allocation - registers come in eights - and what
+        // the receive loop leaves free per SIMD; profiles/voice_live_kernel_resources.txt)
+        int lane = threadIdx.x;
+        asm volatile("" : "+v"(lane));
+        synth_frame(recs + v, pcm + (size_t)v * 160, lane);
+    }
+}
+
 __global__ void
 k_mbe_result_skip(const uint8_t* __restrict__ skip, size_t n, int32_t* __restrict__ result) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && skip[i]) {
         result[i * 5] = (int32_t)((uint32_t)result[i * 5] | DDN_MBE_RESULT_INVALID);
+    }
+}
+
+__global__ void
+k_mbe_result_skip_live(const uint8_t* __restrict__ skip, int n_slots, const int32_t* __restrict__ live_slot,
+                       const int32_t* __restrict__ n_live, int32_t* __restrict__ result) {
+    int n = *n_live;
+    n = n < n_slots ? n : n_slots;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        int v = live_slot[i];
+        v = v < 0 ? 0 : (v >= n_slots ? n_slots - 1 : v);
+        if (skip[v]) {
+            result[(size_t)v * 5] = (int32_t)((uint32_t)result[(size_t)v * 5] | DDN_MBE_RESULT_INVALID);
+        }
     }
 }
 
@@ -817,17 +916,17 @@ ddn_dev_mbe_stream_init(DdnMbeStream* streams, int n_streams, uint32_t seed0, hi
 extern "C" hipError_t
 ddn_dev_mbe_params(int codec, const uint8_t* bits, const int32_t* res_in, int n_streams, int n_frames,
                    const ddn_mbe_tables* d_tables, const float* d_half_log2, DdnMbeStream* streams, int tail_rule,
-                   DdnMbeFrameRec* recs, int32_t* res_out, hipStream_t st) {
+                   DdnMbeFrameRec* recs, int32_t* res_out, const int32_t* n_ldu, hipStream_t st) {
     if (n_streams <= 0 || n_frames <= 0) {
         return hipSuccess;
     }
     const dim3 grid((unsigned)n_streams), blk(64);
     if (codec == DDN_MBE_IMBE_7200X4400) {
         hipLaunchKernelGGL(k_mbe_params<DDN_MBE_IMBE_7200X4400>, grid, blk, 0, st, bits, res_in, n_frames, d_tables,
-                           d_half_log2, streams, tail_rule, recs, res_out);
+                           d_half_log2, streams, tail_rule, recs, res_out, n_ldu);
     } else {
         hipLaunchKernelGGL(k_mbe_params<DDN_MBE_AMBE_3600X2450>, grid, blk, 0, st, bits, res_in, n_frames, d_tables,
-                           d_half_log2, streams, tail_rule, recs, res_out);
+                           d_half_log2, streams, tail_rule, recs, res_out, n_ldu);
     }
     return hipGetLastError();
 }
@@ -847,5 +946,41 @@ ddn_dev_mbe_result_skip(const uint8_t* skip, size_t n, int32_t* result, hipStrea
         return hipSuccess;
     }
     hipLaunchKernelGGL(k_mbe_result_skip, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, skip, n, result);
+    return hipGetLastError();
+}
+
+// ---- the chain object's forms: over the call's live list (fixed grids; the count is a device word) -----------------------------
+extern "C" hipError_t
+ddn_dev_mbe_frame_decode_live(const uint8_t* frames, int n_slots, const int32_t* live_slot, const int32_t* n_live, uint8_t* bits,
+                              int32_t* result, hipStream_t st) {
+    if (n_slots <= 0) {
+        return hipSuccess;
+    }
+    const int groups = (n_slots + DDN_MBE_FRAMES_PER_WG - 1) / DDN_MBE_FRAMES_PER_WG;
+    const int grid = groups < DDN_VOICE_LIVE_GRID_DECODE ? groups : DDN_VOICE_LIVE_GRID_DECODE;
+    hipLaunchKernelGGL(k_mbe_frame_decode_live, dim3((unsigned)grid), dim3(64), 0, st, frames, n_slots, live_slot, n_live, bits, result);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+ddn_dev_mbe_result_skip_live(const uint8_t* skip, int n_slots, const int32_t* live_slot, const int32_t* n_live, int32_t* result,
+                             hipStream_t st) {
+    if (n_slots <= 0) {
+        return hipSuccess;
+    }
+    const int groups = (n_slots + 63) / 64;
+    const int grid = groups < DDN_VOICE_LIVE_GRID / 8 ? groups : DDN_VOICE_LIVE_GRID / 8;
+    hipLaunchKernelGGL(k_mbe_result_skip_live, dim3((unsigned)grid), dim3(64), 0, st, skip, n_slots, live_slot, n_live, result);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+ddn_dev_mbe_synth_live(const DdnMbeFrameRec* recs, int n_slots, const int32_t* live_slot, const int32_t* n_live, float* pcm,
+                       hipStream_t st) {
+    if (n_slots <= 0) {
+        return hipSuccess;
+    }
+    const int grid = n_slots < DDN_VOICE_LIVE_GRID_SYNTH ? n_slots : DDN_VOICE_LIVE_GRID_SYNTH;
+    hipLaunchKernelGGL(k_mbe_synth_live, dim3((unsigned)grid), dim3(64), 0, st, recs, n_slots, live_slot, n_live, pcm);
     return hipGetLastError();
 }

@@ -35,7 +35,14 @@ hipError_t ddn_dev_mbe_result_skip(const uint8_t* skip, size_t n, int32_t* resul
 hipError_t ddn_dev_mbe_stream_init(DdnMbeStream* streams, int n_streams, uint32_t seed0, hipStream_t st);
 hipError_t ddn_dev_mbe_params(int codec, const uint8_t* bits, const int32_t* res_in, int n_streams, int n_frames,
                               const ddn_mbe_tables* d_tables, const float* d_half_log2, DdnMbeStream* streams,
-                              int tail_rule, DdnMbeFrameRec* recs, int32_t* res_out, hipStream_t st);
+                              int tail_rule, DdnMbeFrameRec* recs, int32_t* res_out, const int32_t* n_ldu, hipStream_t st);
 hipError_t ddn_dev_mbe_synth(const DdnMbeFrameRec* recs, size_t n_frames_total, float* pcm, hipStream_t st);
+// over a live list (live_slot [*n_live], entries clamped to [0, n_slots)): fixed grids, the count is read on the device
+hipError_t ddn_dev_mbe_frame_decode_live(const uint8_t* frames, int n_slots, const int32_t* live_slot, const int32_t* n_live, uint8_t* bits,
+                                         int32_t* result, hipStream_t st);
+hipError_t ddn_dev_mbe_result_skip_live(const uint8_t* skip, int n_slots, const int32_t* live_slot, const int32_t* n_live, int32_t* result,
+                                        hipStream_t st);
+hipError_t ddn_dev_mbe_synth_live(const DdnMbeFrameRec* recs, int n_slots, const int32_t* live_slot, const int32_t* n_live, float* pcm,
+                                  hipStream_t st);
 }
 #endif

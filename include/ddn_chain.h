@@ -110,6 +110,11 @@ typedef struct ddn_p25_chain_results {
     const uint8_t* d_pdu_blocks18; /* [..][pdu_blocks][18] confirmed data (flag 4): DBSN(7) | CRC9, then 16 payload bytes per block */
     const uint8_t* d_pdu_crc9_ok;  /* [..][pdu_blocks] a candidate with a good CRC9 was found (else the cheapest one is stored) */
     const int32_t* d_n_ldu;     /* [B] voice LDUs of this call */
+    /* Voice slots: a channel's frames of this call are the first 9 * d_n_ldu[channel] of its max_ldu * 9 slots; the chain works on
+     * those alone.  Every slot behind them holds, in each of the four arrays below and in ddn_p25_chain_host_out.pcm, the same
+     * constant bytes after every call: the decode of an all-zero frame with the skip flag set in its first result word
+     * (0x80000000), the silent frame's result words, 160 zero samples - what ddn_mbe_frame_decode_batch + ddn_mbe_result_skip_batch
+     * + ddn_mbe_synth_batch give for such a frame.  A caller may rely on either: the count, or the skip flag of a slot. */
     const uint8_t* d_imbe_bits; /* [B][max_ldu * 9][88] voice parameter bits */
     const int32_t* d_imbe_result; /* [B][max_ldu * 9][5] */
     const float* d_pcm;         /* [B][max_ldu * 9][160] (vocoder = 1) */
