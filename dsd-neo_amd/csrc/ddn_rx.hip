@@ -732,6 +732,12 @@ div5_exact(float x) {
 #ifndef DDN_RX_CYCLES
 #define DDN_RX_CYCLES 0
 #endif
+// 1: the helper waves' service orders are selectable (cfg.dbg bits 2 / 4 / 8 / 16 / 32, see the handler and the staging loop) and a
+// request carries a ticket.  Measured and not kept in the product build (profiles/README.md, "The two recurrence waves of a
+// workgroup"): compiled with the instrumentation, so that the tables can be taken again.
+#ifndef DDN_RXW_ORDERS
+#define DDN_RXW_ORDERS DDN_RX_CYCLES
+#endif
 
 template <int CPW, bool SMALL = false>
 struct LdsW {
@@ -771,7 +777,9 @@ struct LdsH {
 #endif
     int tile_done[4]; // per recurrence wave: tiles it has finished; bit 30 (DDN_RXW_RAW): the tile its staging picks up next may be read
                       // unfiltered by one of its channels (see stage_half_load)
-    int hwid[8];      // HW_ID of the workgroup's waves (role placement)
+    int hwid[6];      // HW_ID of the workgroup's waves (role placement)
+    int tick;         // requests posted in this launch: a request's ticket is the count before it (bits 8.. of its req_kind word)
+    int spare_;       // (hwid was eight words: the members below keep their addresses)
     int ready[4];     // per recurrence wave: tiles the staging wave has made enterable for its channels (staged + window
                       // summaries of the checkpoint before)
     int fready[4];    // per recurrence wave: tiles whose matched-filter row the handler wave has computed (filter in the loop)
@@ -879,7 +887,19 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         };
-        __builtin_amdgcn_s_setprio(3); // a lane of the recurrence wave (and with it the wave) waits on every decision
+        // A lane of a recurrence wave (and with it the wave) waits on every decision, so this wave goes ahead of other kernels'
+        // waves - but one step below the recurrence waves (priority 3): it shares its SIMD with the OTHER workgroup's recurrence
+        // wave 1, which at equal priority lost issue slots to this wave's decoders and idle bursts that wave 0, beside a staging
+        // wave at priority 0, never lost - wave 1 was 5 - 8 % busier than wave 0 on the same traffic and set the kernel's time
+        // (profiles/README.md, "The two recurrence waves of a workgroup").  cfg.dbg bit 64 = priority 3 as it was, bit 1 =
+        // priority 1 (A/B timing; handler mode never runs k_p25_rx, which reads these bits otherwise).
+        if (cfg.dbg & 64) {
+            __builtin_amdgcn_s_setprio(3);
+        } else if (cfg.dbg & 1) {
+            __builtin_amdgcn_s_setprio(1);
+        } else {
+            __builtin_amdgcn_s_setprio(2);
+        }
     // handler wave: its per-channel words (lane = channel), the history ring, the mailboxes, the decoder tables
     DdnP25HState hs = DdnP25HState{};
     int h_served = 0, h_nev = 0;
@@ -898,6 +918,9 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
         }
         ddn_p25h::crc_cols_fill(H.sc.crc_cols, lane);
         if (lane == 0) {
+            if (DDN_RXW_ORDERS) {
+                H.tick = 0;
+            }
             for (int w = 0; w < 4; w++) {
                 H.tile_done[w] = DDN_RXW_RAW; // (tiles 0 and 1 of a call are staged whole)
                 H.ready[w] = 1; // tile 0 is staged and summarised by the prologue
@@ -915,7 +938,7 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
     auto serve = [&](int c, int seq) {
         using namespace ddn_p25h;
         Scratch& sc = H.sc;
-        const int kind = H.req_kind[c], hw = H.req_hw[c], nsym = H.req_n[c], o_dec = H.req_o[c], neg = H.req_neg[c];
+        const int kind = DDN_RXW_ORDERS ? (H.req_kind[c] & 255) : H.req_kind[c], hw = H.req_hw[c], nsym = H.req_n[c], o_dec = H.req_o[c], neg = H.req_neg[c];
         const int gch = ch0 + c;
         const long long dbg_t0 = (cfg.dbg & 65536) ? (long long)clock64() : 0; // timing experiments: cycles per decision
 #if DDN_RX_CYCLES
@@ -1254,9 +1277,39 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
             const unsigned long long pend = __ballot(lane < CPW && rq != h_served);
             if (pend != 0) {
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                // (lowest channel first.  Serving a pending NID - 2 k cycles - ahead of a pending block was tried once the block's
-                // decision was short: the step did not move, profiles/r11_rxw_cycle_tables.txt)
-                const int c = __ffsll((long long)pend) - 1;
+                // Lowest channel first: of several pending requests recurrence wave 0's go ahead of wave 1's.  A channel has one
+                // request open at most and its own event list, so the order changes no output (tests/test_rx_wave_service_gpu.py),
+                // only who waits.  Measured against three other orders, DDN_RXW_ORDERS builds, cfg.dbg bit (handler mode never runs
+                // k_p25_rx, which reads these bits otherwise): 2 = highest channel first; 8 = oldest ticket first; 16 = the request of
+                // the recurrence wave with fewer tiles done first, ties by the older ticket.  On control traffic the order accounts
+                // for two thirds of what wave 1 is slower by and "behind first" takes 1.2 % off the loop; on the bench mix the excess
+                // stays with wave 1 whatever the order and the loop's time does not move (profiles/README.md, "The two recurrence
+                // waves of a workgroup") - so the product build keeps this order.
+                // (Serving a pending NID - 2 k cycles - ahead of a pending block was tried once the block's decision was short: the
+                // step did not move, profiles/r11_rxw_cycle_tables.txt)
+                int c = __ffsll((long long)pend) - 1;
+                if (DDN_RXW_ORDERS && (pend & (pend - 1)) != 0 && (cfg.dbg & (2 | 8 | 16))) {
+                    if (cfg.dbg & 2) {
+                        c = 63 - __clzll((long long)pend);
+                    } else {
+                        // (after the fence: every request seen above took its ticket before `now` was read)
+                        // (wave-uniform throughout: one pending channel after the other, two LDS words each)
+                        const unsigned now = (unsigned)__hip_atomic_load(&H.tick, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        const bool behind = (cfg.dbg & 16) != 0;
+                        unsigned best = 0xFFFFFFFFu;
+                        for (unsigned long long m = pend; m != 0; m &= m - 1) {
+                            const int l = __ffsll((long long)m) - 1;
+                            const unsigned age = (now - 1u - ((unsigned)H.req_kind[l] >> 8)) & 0xFFFFFFu;
+                            const unsigned td = behind ? (unsigned)(__hip_atomic_load(&H.tile_done[l / LPR_H], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & (DDN_RXW_RAW - 1))
+                                                       : 0u;
+                            const unsigned k = (td << 8) | (255u - (age < 255u ? age : 255u)); // least first: fewest tiles, then oldest
+                            if (k < best) {
+                                best = k;
+                                c = l;
+                            }
+                        }
+                    }
+                }
                 dbg_pend = __popcll(pend);
 #if DDN_RX_CYCLES
                 const long long sv_t0 = (long long)clock64();
@@ -1865,7 +1918,13 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                 H.req_t[ln] = (int)clock64();
 #endif
             }
-            H.req_kind[ln] = s.hphase;
+            if (DDN_RXW_ORDERS) {
+                // the ticket (the workgroup's count of requests so far, 24 bits) rides above the kind: the handler wave can serve by age
+                const unsigned tk = (unsigned)__hip_atomic_fetch_add(&H.tick, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                H.req_kind[ln] = (int)((unsigned)s.hphase | (tk << 8));
+            } else {
+                H.req_kind[ln] = s.hphase;
+            }
             H.req_hw[ln] = s.hw;
             H.req_n[ln] = s.hn;
             H.req_o[ln] = o_last;
@@ -2082,6 +2141,7 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
 #define DBG_B2(k, k2) do { if (DDN_RX_CYCLES && (cfg.dbg & 8192)) { const uint32_t n_ = (uint32_t)clock64(); dbg_b[k] += n_ - dbg_b0; dbg_b[k2] += n_ - dbg_b0; dbg_b0 = n_; } } while (0)
     long long dbg_run[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // lean runs: count, trips, -, -, -, runs polling a mailbox, cycles inside the run, phases
     long long dbg_ent[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // a lean run's entry, by part: queue hand-over, lean tests + entry proof, run length
+    long long dbg_hw[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dbg_hw_t0 = 0; // with a lane in hwait: cycles, passes, passes that found an answer
     if (HM && loader) {
         // Handler mode, staging wave: job j of recurrence wave h's channels (stage tile j + 1, drain tile j - 1's queue, the
         // window summaries of checkpoint j) falls due when that wave has finished tile j - 1, and lets it into tile j + 1; job
@@ -2101,11 +2161,26 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
         };
         while (jobs_left()) {
             bool served = false;
+            // Every due half in one pass, lowest first.  DDN_RXW_ORDERS builds, cfg.dbg bit 4: one half a pass, the highest due
+            // one; bit 32: one half a pass, the one whose recurrence wave has fewer tiles done (measured: the voice-only loop, which
+            // this wave bounds, 3 % longer; the others unchanged - profiles/README.md)
+            int only = -1;
+            if (DDN_RXW_ORDERS && (cfg.dbg & (4 | 32))) {
+                int td_min = 0x7fffffff;
+#pragma unroll
+                for (int h = 0; h < NRW; h++) {
+                    const int td = __hip_atomic_load(&H.tile_done[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & (DDN_RXW_RAW - 1);
+                    if (job[h] <= n_tiles && td >= job[h] && ((cfg.dbg & 4) ? true : td < td_min)) {
+                        td_min = td;
+                        only = h;
+                    }
+                }
+            }
 #pragma unroll
             for (int h = 0; h < NRW; h++) {
                 const int j = job[h];
                 const int tdw = __hip_atomic_load(&H.tile_done[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (j > n_tiles || (tdw & (DDN_RXW_RAW - 1)) < j) {
+                if (j > n_tiles || (tdw & (DDN_RXW_RAW - 1)) < j || (only >= 0 && h != only)) {
                     continue;
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -2248,7 +2323,18 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
             while (true) {
                 const long long dbg_p0 = (DDN_RX_CYCLES && (cfg.dbg & 8192)) ? (long long)clock64() : 0;
                 long long dbg_p1 = 0;
+                if (DDN_RX_CYCLES && HM && (cfg.dbg & 8192)) { // cycles of passes that began with a lane waiting for its answer
+                    if (dbg_hw_t0 != 0) {
+                        dbg_hw[0] += dbg_p0 - dbg_hw_t0;
+                        dbg_hw[1]++;
+                    }
+                    dbg_hw_t0 = __any(hwait) ? dbg_p0 : 0;
+                }
                 if (HM && __any(hwait)) {
+                    if (DDN_RX_CYCLES && (cfg.dbg & 8192)
+                        && __any(hwait && __hip_atomic_load(&H.rsp_seq[ln], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == hseq)) {
+                        dbg_hw[2]++; // ... and of those, the passes that found an answer
+                    }
                     if (hwait
                         && __hip_atomic_load(&H.rsp_seq[ln], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == hseq) {
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
@@ -3487,10 +3573,20 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
         // (written over the unused tail of the workgroup's first channel's record area)
         uint8_t* d = rec + ((size_t)ch0 + 1) * max_sym * 10 - 192 + (wave < NRW ? (wave ? 1 : 0) : 2) * 64; // (recurrence 0, another one, staging)
         const long long v[8] = {dbg_busy, dbg_wait, dbg_cyc[0], dbg_cyc[1], dbg_cyc[2], dbg_n[0], dbg_n[1], dbg_n[2]};
-        for (int k = 0; k < 64; k++) {
+        for (int k = 0; k < 64 && !(wave >= 2 && wave < NRW); k++) {
             d[k] = reinterpret_cast<const uint8_t*>(v)[k];
         }
-        if (wave == 0) { // the recurrence wave's standard-trip sections, one block further down; its lean-run figures, another one
+        if (wave < NRW) {
+            // a recurrence wave's standard-trip sections, one block further down; its lean-run figures, another one; ... its cycles
+            // with a lane in hwait, the last one.  Recurrence wave w's blocks lie 640 bytes * w below wave 0's (in its bank the three
+            // blocks above are free: a third or fourth recurrence wave's busy / wait block goes where wave 0's is).
+            const int bank = 640 * wave;
+            if (wave >= 2) {
+                uint8_t* d3 = rec + ((size_t)ch0 + 1) * max_sym * 10 - 192 - bank;
+                for (int k = 0; k < 64; k++) {
+                    d3[k] = reinterpret_cast<const uint8_t*>(v)[k];
+                }
+            }
             long long dbg_blk2[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // {the crossing masks' part of dbg_blk[1], passes of several owners}
             if constexpr (LPR == 2 || LPR == 4) {
                 for (int k = 0; k < 8; k++) {
@@ -3499,8 +3595,9 @@ k_p25_rxw(const float* __restrict__ raw, const float* __restrict__ filt, const f
                 dbg_blk2[0] = dbg_b[8];
                 dbg_blk2[1] = dbg_b[9];
             }
-            uint8_t* d2 = rec + ((size_t)ch0 + 1) * max_sym * 10 - 256;
+            uint8_t* d2 = rec + ((size_t)ch0 + 1) * max_sym * 10 - 256 - bank;
             for (int k = 0; k < 64; k++) {
+                d2[k - 384] = reinterpret_cast<const uint8_t*>(dbg_hw)[k];
                 d2[k] = reinterpret_cast<const uint8_t*>(dbg_sec)[k];
                 d2[k - 64] = reinterpret_cast<const uint8_t*>(dbg_run)[k];
                 d2[k - 128] = reinterpret_cast<const uint8_t*>(dbg_blk)[k];
