@@ -12,7 +12,18 @@ LIB_PATH = os.environ.get("DDN_LIB_PATH") or os.path.join(ROOT, "dsd-neo_amd", "
 
 DDN_OK, DDN_EINVAL, DDN_ENODEV, DDN_ENOMEM, DDN_EHIP, DDN_ERANGE = 0, -1, -2, -3, -4, -5
 LPF_WIDE, LPF_6K25, LPF_12K5, LPF_PROVOICE, LPF_P25_C4FM, LPF_P25_CQPSK = range(6)
-IN_CU8, IN_CF32 = 0, 1
+IN_CU8, IN_CF32, IN_CS16 = 0, 1, 2  # cs16: little-endian int16 pairs, I then Q, widened on the device as s * 2^-15 (exact)
+
+
+def check_host_iq(input_format, iq, n_channels, n):
+    """a cs16 object reads n_channels * n * 2 int16 from a host array: anything else is refused here, before the library would read past
+    the array.  The other formats accept what they always did."""
+    if input_format == IN_CS16:
+        import numpy as np
+        if iq.dtype != np.int16:
+            raise TypeError("a cs16 object takes int16 samples, not %s" % iq.dtype)
+        if iq.size != n_channels * n * 2:
+            raise ValueError("a cs16 object of %d channels takes %d int16 for n = %d, not %d" % (n_channels, n_channels * n * 2, n, iq.size))
 
 
 class FrontEndConfig(C.Structure):
@@ -69,6 +80,7 @@ class FskModemState(C.Structure):
 PROTOTYPES = {
     "ddn_last_error": (C.c_char_p, []),
     "ddn_version": (C.c_char_p, []),
+    "ddn_input_format_bytes": (C.c_size_t, [C.c_int]),
     "ddn_batch_create": (C.c_int, [C.POINTER(FrontEndConfig), C.POINTER(C.c_void_p)]),
     "ddn_batch_destroy": (None, [C.c_void_p]),
     "ddn_batch_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -681,12 +693,13 @@ def mixed_partition(n_p25, n_dmr, n_nxdn48, rank, world):
 class Fsk4ChainC:
     """ddn_fsk4_chain (include/ddn_chain.h): the DMR / NXDN48 path as one C object; fetch() copies a result array to the host"""
 
-    def __init__(self, n_channels, samples_per_call, protocol, rf_mod=0, inverted=0, block_len=8192, handlers=1, vocoder=1, handle=None):
+    def __init__(self, n_channels, samples_per_call, protocol, rf_mod=0, inverted=0, block_len=8192, handlers=1, vocoder=1, handle=None,
+                 input_format=IN_CU8):
         import numpy as np
         self.np = np
         self.own = handle is None
         if handle is None:
-            cfg = Fsk4ChainConfig(n_channels, samples_per_call, block_len, 0, protocol, rf_mod, inverted, handlers, vocoder)
+            cfg = Fsk4ChainConfig(n_channels, samples_per_call, block_len, input_format, protocol, rf_mod, inverted, handlers, vocoder)
             self.h = C.c_void_p()
             _check(lib().ddn_fsk4_chain_create(C.byref(cfg), C.byref(self.h)), "ddn_fsk4_chain_create")
         else:
@@ -770,8 +783,8 @@ class Fsk4ChainC:
 class MixedChainC:
     """ddn_mixed_chain: P25 Phase 1 + DMR + NXDN48 channel groups of one GPU (BASELINE configs[3])"""
 
-    def __init__(self, n_p25, n_dmr, n_nxdn48, samples_per_call, block_len=8192, vocoder=1, overlap=0):
-        cfg = MixedChainConfig(n_p25, n_dmr, n_nxdn48, samples_per_call, block_len, 0, vocoder, overlap)
+    def __init__(self, n_p25, n_dmr, n_nxdn48, samples_per_call, block_len=8192, vocoder=1, overlap=0, input_format=IN_CU8):
+        cfg = MixedChainConfig(n_p25, n_dmr, n_nxdn48, samples_per_call, block_len, input_format, vocoder, overlap)
         self.h = C.c_void_p()
         _check(lib().ddn_mixed_chain_create(C.byref(cfg), C.byref(self.h)), "ddn_mixed_chain_create")
         self.counts = (n_p25, n_dmr, n_nxdn48)
@@ -1127,9 +1140,10 @@ class Batch:
                "ddn_batch_set_iq_conditioning")
 
     def run_host(self, iq, n):
-        """iq: numpy [B, n, 2] uint8 or float32 (channel-major).  Returns float32 [B, n >> passes]."""
+        """iq: numpy [B, n, 2] uint8, float32 or (a cs16 batch) int16, channel-major.  Returns float32 [B, n >> passes]."""
         import numpy as np
         iq = np.ascontiguousarray(iq)
+        check_host_iq(self.cfg.input_format, iq, self.cfg.n_channels, n)
         out = np.empty((self.cfg.n_channels, n >> getattr(self, "passes", 0)), np.float32)
         _check(lib().ddn_front_end_run_host(self.h, iq.ctypes.data, n, out.ctypes.data), "ddn_front_end_run_host")
         return out
@@ -1235,6 +1249,7 @@ class CqpskBatch:
         import numpy as np
         iq = np.ascontiguousarray(iq)
         n = iq.shape[1]
+        check_host_iq(self.cfg.input_format, iq, self.B, n)
         stride = lib().ddn_cqpsk_max_symbols(self.h, n)
         sym = np.zeros((self.B, stride), np.float32)
         cnt = np.zeros(self.B, np.int32)

@@ -83,13 +83,24 @@ struct ddn_batch {
     size_t lpf_cap;
 };
 
+// bytes per complex sample of an input format; 0 = not a format (host only, touches no device)
+extern "C" size_t
+ddn_input_format_bytes(int input_format) {
+    switch (input_format) {
+        case DDN_IN_CU8: return 2;
+        case DDN_IN_CF32: return 8;
+        case DDN_IN_CS16: return 4;
+        default: return 0;
+    }
+}
+
 extern "C" int
 ddn_batch_create(const ddn_front_end_config* cfg, ddn_batch** out) {
     if (!cfg || !out || cfg->n_channels <= 0 || cfg->sample_rate_hz <= 0) {
         ddn_set_error("ddn_batch_create: bad config");
         return DDN_EINVAL;
     }
-    if (cfg->input_format != DDN_IN_CU8 && cfg->input_format != DDN_IN_CF32) {
+    if (ddn_input_format_bytes(cfg->input_format) == 0) {
         ddn_set_error("ddn_batch_create: unknown input_format %d", cfg->input_format);
         return DDN_EINVAL;
     }
@@ -395,9 +406,20 @@ check_front_end_run(const char* who, const ddn_batch* b, const void* iq, const f
     return (b && iq && disc) ? DDN_OK : ddn_bad_argument(who);
 }
 
+// the cs16 kernels load one 32-bit word per complex sample
+static int
+check_cs16_aligned(const char* who, int input_format, const void* d_iq) {
+    if (input_format == DDN_IN_CS16 && (((uintptr_t)d_iq) & 3) != 0) {
+        ddn_set_error("%s: cs16 input must be 4-byte aligned (d_iq %p)", who, d_iq);
+        return DDN_EINVAL;
+    }
+    return DDN_OK;
+}
+
 extern "C" int
 ddn_front_end_run(ddn_batch* b, const void* d_iq, size_t n, float* d_disc, void* hip_stream) {
     DDN_TRY(check_front_end_run(__func__, b, d_iq, d_disc));
+    DDN_TRY(check_cs16_aligned(__func__, b->cfg.input_format, d_iq));
     if (n == 0) {
         return DDN_OK;
     }
@@ -536,7 +558,7 @@ ddn_front_end_run_host(ddn_batch* b, const void* h_iq, size_t n, float* h_disc) 
         return DDN_OK;
     }
     const size_t B = (size_t)b->cfg.n_channels;
-    const size_t in_bytes = B * n * (b->cfg.input_format == DDN_IN_CU8 ? 2 : 8);
+    const size_t in_bytes = B * n * ddn_input_format_bytes(b->cfg.input_format);
     const size_t out_bytes = B * (n >> b->passes) * sizeof(float);
     int rc = grow(&b->d_in, &b->in_cap, in_bytes);
     if (rc != DDN_OK) {

@@ -322,6 +322,10 @@ ddn_p25_chain_create(const ddn_p25_chain_config* cfg, ddn_p25_chain** out) {
         ddn_set_error("ddn_p25_chain_create: bad configuration");
         return DDN_EINVAL;
     }
+    if (ddn_input_format_bytes(cfg->input_format) == 0) {
+        ddn_set_error("ddn_p25_chain_create: unknown input_format %d", cfg->input_format);
+        return DDN_EINVAL;
+    }
     *out = nullptr;
     ddn_p25_chain* c = new (std::nothrow) ddn_p25_chain();
     if (!c) {
@@ -451,7 +455,7 @@ ddn_p25_chain_create(const ddn_p25_chain_config* cfg, ddn_p25_chain** out) {
                 rc = DDN_EHIP;
             }
         }
-        c->iq_bytes = B * (size_t)c->n * (cfg->input_format == DDN_IN_CF32 ? 8 : 2);
+        c->iq_bytes = B * (size_t)c->n * ddn_input_format_bytes(cfg->input_format);
         c->synth_beside_loop = 1;
         if (const char* e = DDN_EXP_ENV("DDN_CHAIN_SYNTH_BESIDE_LOOP")) {
             c->synth_beside_loop = atoi(e) != 0;

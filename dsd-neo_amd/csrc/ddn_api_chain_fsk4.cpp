@@ -515,6 +515,10 @@ ddn_fsk4_chain_create(const ddn_fsk4_chain_config* cfg, ddn_fsk4_chain** out) {
         ddn_set_error("ddn_fsk4_chain_create: bad configuration");
         return DDN_EINVAL;
     }
+    if (ddn_input_format_bytes(cfg->input_format) == 0) {
+        ddn_set_error("ddn_fsk4_chain_create: unknown input_format %d", cfg->input_format);
+        return DDN_EINVAL;
+    }
     *out = nullptr;
     ddn_fsk4_chain* c = new (std::nothrow) ddn_fsk4_chain();
     if (!c) {

@@ -61,6 +61,10 @@ ddn_mixed_chain_create(const ddn_mixed_chain_config* cfg, ddn_mixed_chain** out)
         ddn_set_error("ddn_mixed_chain_create: bad configuration");
         return DDN_EINVAL;
     }
+    if (ddn_input_format_bytes(cfg->input_format) == 0) {
+        ddn_set_error("ddn_mixed_chain_create: unknown input_format %d", cfg->input_format);
+        return DDN_EINVAL;
+    }
     *out = nullptr;
     ddn_mixed_chain* m = new (std::nothrow) ddn_mixed_chain();
     if (!m) {

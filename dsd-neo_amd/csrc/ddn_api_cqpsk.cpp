@@ -53,8 +53,12 @@ cq_fill(ddn_cqpsk_batch* b, hipStream_t st) {
 extern "C" int
 ddn_cqpsk_batch_create(const ddn_cqpsk_config* cfg, ddn_cqpsk_batch** out) {
     if (!cfg || !out || cfg->n_channels <= 0 || cfg->sample_rate_hz <= 0 || cfg->symbol_rate_hz <= 0
-        || cfg->block_len < 4 || (cfg->input_format != DDN_IN_CU8 && cfg->input_format != DDN_IN_CF32)) {
+        || cfg->block_len < 4) {
         ddn_set_error("ddn_cqpsk_batch_create: bad configuration");
+        return DDN_EINVAL;
+    }
+    if (ddn_input_format_bytes(cfg->input_format) == 0) {
+        ddn_set_error("ddn_cqpsk_batch_create: unknown input_format %d", cfg->input_format);
         return DDN_EINVAL;
     }
     DDN_TRY(ddn_have_device());
@@ -131,6 +135,10 @@ extern "C" int
 ddn_cqpsk_run(ddn_cqpsk_batch* b, const void* d_iq, size_t n, float* d_symbols, size_t sym_stride, int32_t* d_counts,
               void* hip_stream) {
     DDN_TRY(check_cqpsk_run(__func__, b, d_iq, d_symbols, d_counts));
+    if (b->cfg.input_format == DDN_IN_CS16 && (((uintptr_t)d_iq) & 3) != 0) {
+        ddn_set_error("ddn_cqpsk_run: cs16 input must be 4-byte aligned (d_iq %p)", d_iq); // (the kernels load one 32-bit word per sample)
+        return DDN_EINVAL;
+    }
     hipStream_t st = (hipStream_t)hip_stream;
     const int B = b->cfg.n_channels;
     if (n == 0) {
@@ -173,7 +181,7 @@ ddn_cqpsk_run(ddn_cqpsk_batch* b, const void* d_iq, size_t n, float* d_symbols, 
         cur = b->d_a;
         fmt = DDN_IN_CF32;
     } else if (fmt != DDN_IN_CF32) {
-        ddn_set_error("ddn_cqpsk_run: cu8 input needs the channel LPF stage (it does the widening)");
+        ddn_set_error("ddn_cqpsk_run: %s input needs the channel LPF stage (it does the widening)", fmt == DDN_IN_CS16 ? "cs16" : "cu8");
         return DDN_EINVAL;
     }
     HIP_TRY(ddn_dev_cqpsk_agc_fll(cur, (long)n, n, B, b->fll_nt, b->fll_alpha, b->fll_beta, b->d_fll_taps, b->d_state, b->d_delay, b->d_b,
@@ -197,7 +205,7 @@ ddn_cqpsk_run_host(ddn_cqpsk_batch* b, const void* iq, size_t n, float* symbols,
         return DDN_ERANGE;
     }
     DdnStaged s;
-    const void* in = s.in(iq, B * n * (b->cfg.input_format == DDN_IN_CU8 ? 2 : 8));
+    const void* in = s.in(iq, B * n * ddn_input_format_bytes(b->cfg.input_format));
     float* o = s.out((float*)nullptr, B * scap * 4); // rows of scap symbols: they go into the caller's rows of sym_stride below
     int32_t* c = s.out(counts, B * 4);
     DDN_TRY(s.staged());

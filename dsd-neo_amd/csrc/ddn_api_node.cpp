@@ -451,6 +451,10 @@ ddn_node_create(const ddn_node_config* cfg, ddn_node** out) {
         ddn_set_error("ddn_node_create: bad configuration (kind %d)", kind);
         return DDN_EINVAL;
     }
+    if (ddn_input_format_bytes(cfg->input_format) == 0) {
+        ddn_set_error("ddn_node_create: unknown input_format %d", cfg->input_format);
+        return DDN_EINVAL;
+    }
     *out = nullptr;
     int visible = 0;
     if (hipGetDeviceCount(&visible) != hipSuccess || visible <= 0) {
@@ -466,7 +470,7 @@ ddn_node_create(const ddn_node_config* cfg, ddn_node** out) {
         return DDN_ENOMEM;
     }
     n->cfg = *cfg;
-    n->sample_bytes = cfg->input_format == DDN_IN_CF32 ? 8 : 2;
+    n->sample_bytes = ddn_input_format_bytes(cfg->input_format);
     if (kind == DDN_NODE_FSK4) {
         n->fsk4_copy = *cfg->fsk4;
         n->cfg.fsk4 = &n->fsk4_copy;

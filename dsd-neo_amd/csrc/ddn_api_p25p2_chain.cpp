@@ -66,6 +66,10 @@ ddn_p25p2_chain_create(const ddn_p25p2_chain_config* cfg, const uint64_t* seed44
         ddn_set_error("ddn_p25p2_chain_create: bad configuration");
         return DDN_EINVAL;
     }
+    if (ddn_input_format_bytes(cfg->input_format) == 0) {
+        ddn_set_error("ddn_p25p2_chain_create: unknown input_format %d", cfg->input_format);
+        return DDN_EINVAL;
+    }
     *out = nullptr;
     ddn_p25p2_chain* c = new (std::nothrow) ddn_p25p2_chain();
     if (!c) {

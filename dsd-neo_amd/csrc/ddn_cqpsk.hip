@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "ddn_device.h"
+#include "ddn_iq_load_dev.h"
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -112,16 +113,6 @@ atan2_qpsk(float y, float x) {
     return (y > 0.0f) ? (1.57079632679489661923f - a) : (-1.57079632679489661923f - a);
 }
 
-template <int FMT>
-__device__ __forceinline__ f2
-load_iq(const void* base, size_t idx) {
-    if (FMT == DDN_IN_CU8) {
-        const uchar2 v = ((const uchar2*)base)[idx];
-        f2 r = {((float)v.x - 127.5f) * (1.0f / 127.5f), ((float)v.y - 127.5f) * (1.0f / 127.5f)};
-        return r;
-    }
-    return ((const f2*)base)[idx];
-}
 } // namespace
 
 // ---- channel LPF, complex -> complex -------------------------------------------------------------------------------
@@ -160,7 +151,7 @@ k_channel_lpf_c2c(const void* __restrict__ in, long n, size_t in_stride, int blo
         if (j < 0) {
             v = hist[(size_t)ch * H + (size_t)(H + j)];
         } else {
-            v = load_iq<FMT>(in, (size_t)ch * in_stride + (size_t)j);
+            v = ddn_iq_load<FMT>(in, (size_t)ch * in_stride + (size_t)j);
         }
         win[i] = v;
     }
@@ -217,7 +208,7 @@ k_channel_lpf_c2c_u(const void* __restrict__ in, long n, size_t in_stride, int b
     for (int i = threadIdx.x; i < 256 + H; i += 128) {
         long j = t0 - CEN_T + i;
         j = j > last ? last : j;
-        win[i] = (j < 0) ? hist[(size_t)ch * H + (size_t)(H + j)] : load_iq<FMT>(in, (size_t)ch * in_stride + (size_t)j);
+        win[i] = (j < 0) ? hist[(size_t)ch * H + (size_t)(H + j)] : ddn_iq_load<FMT>(in, (size_t)ch * in_stride + (size_t)j);
     }
     __syncthreads();
     const long m = t0 + 2 * threadIdx.x;
@@ -271,7 +262,7 @@ k_lpf_hist(const void* __restrict__ in, long n, size_t in_stride, int H, f2* __r
     f2 v = {0.0f, 0.0f};
     if (i < H) {
         const long j = n - H + i;
-        v = (j >= 0) ? load_iq<FMT>(in, (size_t)ch * in_stride + (size_t)j) : hist[(size_t)ch * H + (size_t)(H + j)];
+        v = (j >= 0) ? ddn_iq_load<FMT>(in, (size_t)ch * in_stride + (size_t)j) : hist[(size_t)ch * H + (size_t)(H + j)];
     }
     __syncthreads();
     if (i < H) {
@@ -833,54 +824,58 @@ k_cqpsk_symbols(const f2* __restrict__ sym, size_t stride, const int* __restrict
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------
-extern "C" hipError_t
-ddn_dev_channel_lpf_c2c(const void* in, int in_fmt, long n, size_t in_stride, int block_len, int n_channels,
-                        const float* taps_dev, int taps_len, int has_zero_tap, void* hist, void* out, size_t out_stride,
-                        hipStream_t st) {
-    if (n_channels <= 0 || n <= 0) {
-        return hipSuccess;
-    }
+template <int FMT>
+static hipError_t
+launch_lpf_c2c(const void* in, long n, size_t in_stride, int block_len, int n_channels, const float* taps_dev, int taps_len,
+               int has_zero_tap, void* hist, void* out, size_t out_stride, hipStream_t st) {
     const int tiles_per_block = (block_len + 255) / 256;
     const long n_blocks = (n + block_len - 1) / block_len;
     const dim3 grid((unsigned)(n_blocks * tiles_per_block), (unsigned)n_channels), blk(256);
-#define DDN_C2C_U(FMTV, CENV)                                                                                          \
+#define DDN_C2C_U(CENV)                                                                                                \
     do {                                                                                                               \
         if (has_zero_tap) {                                                                                            \
-            hipLaunchKernelGGL((k_channel_lpf_c2c_u<FMTV, CENV, true>), grid, dim3(128), 0, st, in, n, in_stride,      \
+            hipLaunchKernelGGL((k_channel_lpf_c2c_u<FMT, CENV, true>), grid, dim3(128), 0, st, in, n, in_stride,       \
                                block_len, tiles_per_block, taps_dev, (const f2*)hist, (f2*)out, out_stride);           \
         } else {                                                                                                       \
-            hipLaunchKernelGGL((k_channel_lpf_c2c_u<FMTV, CENV, false>), grid, dim3(128), 0, st, in, n, in_stride,     \
+            hipLaunchKernelGGL((k_channel_lpf_c2c_u<FMT, CENV, false>), grid, dim3(128), 0, st, in, n, in_stride,      \
                                block_len, tiles_per_block, taps_dev, (const f2*)hist, (f2*)out, out_stride);           \
         }                                                                                                              \
     } while (0)
-    if (taps_len == 135 && in_fmt == DDN_IN_CU8) {
-        DDN_C2C_U(DDN_IN_CU8, 67);
-    } else if (taps_len == 135) {
-        DDN_C2C_U(DDN_IN_CF32, 67);
-    } else if (taps_len == 67 && in_fmt == DDN_IN_CU8) {
-        DDN_C2C_U(DDN_IN_CU8, 33);
+    if (taps_len == 135) {
+        DDN_C2C_U(67);
     } else if (taps_len == 67) {
-        DDN_C2C_U(DDN_IN_CF32, 33);
-    } else if (in_fmt == DDN_IN_CU8) {
-        hipLaunchKernelGGL((k_channel_lpf_c2c<DDN_IN_CU8>), grid, blk, 0, st, in, n, in_stride, block_len, tiles_per_block,
-                           taps_dev, taps_len, (const f2*)hist, (f2*)out, out_stride);
+        DDN_C2C_U(33);
     } else {
-        hipLaunchKernelGGL((k_channel_lpf_c2c<DDN_IN_CF32>), grid, blk, 0, st, in, n, in_stride, block_len, tiles_per_block,
-                           taps_dev, taps_len, (const f2*)hist, (f2*)out, out_stride);
+        hipLaunchKernelGGL((k_channel_lpf_c2c<FMT>), grid, blk, 0, st, in, n, in_stride, block_len, tiles_per_block, taps_dev,
+                           taps_len, (const f2*)hist, (f2*)out, out_stride);
     }
 #undef DDN_C2C_U
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         return e;
     }
-    if (in_fmt == DDN_IN_CU8) {
-        hipLaunchKernelGGL((k_lpf_hist<DDN_IN_CU8>), dim3((unsigned)n_channels), dim3(192), 0, st, in, n, in_stride,
-                           taps_len - 1, (f2*)hist);
-    } else {
-        hipLaunchKernelGGL((k_lpf_hist<DDN_IN_CF32>), dim3((unsigned)n_channels), dim3(192), 0, st, in, n, in_stride,
-                           taps_len - 1, (f2*)hist);
-    }
+    hipLaunchKernelGGL((k_lpf_hist<FMT>), dim3((unsigned)n_channels), dim3(192), 0, st, in, n, in_stride, taps_len - 1, (f2*)hist);
     return hipGetLastError();
+}
+
+extern "C" hipError_t
+ddn_dev_channel_lpf_c2c(const void* in, int in_fmt, long n, size_t in_stride, int block_len, int n_channels,
+                        const float* taps_dev, int taps_len, int has_zero_tap, void* hist, void* out, size_t out_stride,
+                        hipStream_t st) {
+    if (in_fmt != DDN_IN_CU8 && in_fmt != DDN_IN_CS16 && in_fmt != DDN_IN_CF32) {
+        return hipErrorInvalidValue; // (no instance reads a buffer of a format it does not know)
+    }
+    if (n_channels <= 0 || n <= 0) {
+        return hipSuccess;
+    }
+    switch (in_fmt) {
+        case DDN_IN_CU8:
+            return launch_lpf_c2c<DDN_IN_CU8>(in, n, in_stride, block_len, n_channels, taps_dev, taps_len, has_zero_tap, hist, out, out_stride, st);
+        case DDN_IN_CS16:
+            return launch_lpf_c2c<DDN_IN_CS16>(in, n, in_stride, block_len, n_channels, taps_dev, taps_len, has_zero_tap, hist, out, out_stride, st);
+        default:
+            return launch_lpf_c2c<DDN_IN_CF32>(in, n, in_stride, block_len, n_channels, taps_dev, taps_len, has_zero_tap, hist, out, out_stride, st);
+    }
 }
 
 extern "C" hipError_t

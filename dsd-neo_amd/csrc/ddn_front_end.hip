@@ -1,11 +1,11 @@
 // ddn_front_end.hip — gfx950 kernel for the dsd-neo FSK front end, one persistent launch per call:
 //
-//   cu8/cf32 widen -> zero-latency symmetric complex channel LPF -> phase delta   (sample-parallel, VALU-bound)
+//   cu8/cs16/cf32 widen -> zero-latency symmetric complex channel LPF -> phase delta   (sample-parallel, VALU-bound)
 //   dc centring + asymmetric peak AGC                                              (per-channel serial chains)
 //   scale to +-30000, clip, store                                                  (sample-parallel)
 //
 // Reference behaviour reproduced (paths relative to the dsd-neo tree):
-//   widen                     src/dsp/simd_widen.cpp:139-149
+//   widen                     src/dsp/simd_widen.cpp:139-149 (cu8), src/io/radio/rtl_device.cpp:1247-1264 (cs16): ddn_iq_load_dev.h
 //   channel LPF               src/dsp/simd_fir_avx2.cpp:119-143 (per-output FMA chain: centre tap, then
 //                             k = 0..centre-1 of fma(h[k], x[n-d] + x[n+d], acc)); block-edge sample
 //                             replication src/dsp/simd_fir.cpp:66-85
@@ -27,7 +27,7 @@
 //   HBM traffic is the algorithmic minimum: input read once (+ a 2*CENTER halo per tile from L2), output
 //   written once.  Two barriers per tile; everything else stays in LDS / registers.
 //
-// Data layout in HBM: input [B][n] interleaved I/Q (2 B or 8 B per complex sample), output [B][n] f32, both
+// Data layout in HBM: input [B][n] interleaved I/Q (2, 4 or 8 B per complex sample), output [B][n] f32, both
 // channel-major so one channel's stream is contiguous (what the stream-read hook hands out).  Per-channel
 // carried state: DDN_CARRY_LEN widened samples of FIR look-back + 5 words of modem state.
 
@@ -36,6 +36,7 @@
 
 #include "ddn_atan2f.h"
 #include "ddn_device.h"
+#include "ddn_iq_load_dev.h"
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -57,21 +58,6 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 
 // ------------------------------------------------------------------------------------------------------
 // helpers
-
-__device__ __forceinline__ f2
-ddn_load_iq(const void* base, int fmt, size_t ch_stride_samples, int ch, long p) {
-    if (fmt == DDN_IN_CU8) {
-        const uint16_t* s = (const uint16_t*)base + (size_t)ch * ch_stride_samples + p;
-        const uint16_t v = *s;
-        const float inv = 1.0f / 127.5f;
-        f2 r;
-        r.x = ((float)(v & 0xFF) - 127.5f) * inv;
-        r.y = ((float)(v >> 8) - 127.5f) * inv;
-        return r;
-    }
-    const f2* s = (const f2*)base + (size_t)ch * ch_stride_samples + p;
-    return *s;
-}
 
 // src/dsp/fsk_modem.c:23-35 + :89-94
 __device__ __forceinline__ float
@@ -243,7 +229,8 @@ k_front_end_fused(DdnFusedArgs a) {
         }
     }
     // raw samples of the NEXT tile, fetched while the current one is filtered (hides HBM latency)
-    uint32_t pre_u[(FMT == DDN_IN_CU8) ? NPRE : 1];
+    // (cu8 and cs16: the raw sample in one 32-bit register, widened when it is staged; cf32: the float pair)
+    uint32_t pre_u[(FMT != DDN_IN_CF32) ? NPRE : 1];
     f2 pre_f[(FMT == DDN_IN_CF32) ? NPRE : 1];
     __syncthreads();
 
@@ -317,7 +304,7 @@ k_front_end_fused(DdnFusedArgs a) {
                             if (p > tc.blk_end - 1) {
                                 p = tc.blk_end - 1; // the reference replicates the block's last sample
                             }
-                            v = ddn_load_iq(in_s, FMT, a.ch_stride, chl, p);
+                            v = ddn_iq_load<FMT>(in_s, (size_t)chl * a.ch_stride + p);
                         }
                         win[g][i + i / R] = v;
                     }
@@ -327,11 +314,8 @@ k_front_end_fused(DdnFusedArgs a) {
                         const int i = u + 32 * k;
                         if (i < Weff) {
                             f2 v;
-                            if constexpr (FMT == DDN_IN_CU8) {
-                                const uint32_t r = pre_u[k];
-                                const float inv = 1.0f / 127.5f;
-                                v.x = ((float)(r & 0xFF) - 127.5f) * inv;
-                                v.y = ((float)(r >> 8) - 127.5f) * inv;
+                            if constexpr (FMT != DDN_IN_CF32) {
+                                v = ddn_iq_unpack<FMT>(pre_u[k]);
                             } else {
                                 v = pre_f[k];
                             }
@@ -368,8 +352,8 @@ k_front_end_fused(DdnFusedArgs a) {
                             p = tn.blk_end - 1;
                         }
                         if (i < Weff) {
-                            if constexpr (FMT == DDN_IN_CU8) {
-                                pre_u[k] = *((const uint16_t*)in_s + (size_t)chl * a.ch_stride + p);
+                            if constexpr (FMT != DDN_IN_CF32) {
+                                pre_u[k] = ddn_iq_fetch<FMT>(in_s, (size_t)chl * a.ch_stride + p);
                             } else {
                                 pre_f[k] = *((const f2*)in_s + (size_t)chl * a.ch_stride + p);
                             }
@@ -762,7 +746,7 @@ k_front_end_fused(DdnFusedArgs a) {
         // or writes this channel's row (it read it at tile 0), so no other ordering is needed.
         f2* c = a.carry_out + (size_t)ch * DDN_CARRY_LEN;
         for (int i = u; i < DDN_CARRY_LEN; i += 32) {
-            c[i] = ddn_load_iq(in_s, FMT, a.ch_stride, chl, a.n - DDN_CARRY_LEN + i);
+            c[i] = ddn_iq_load<FMT>(in_s, (size_t)chl * a.ch_stride + (a.n - DDN_CARRY_LEN + i));
         }
     }
     if (role == 1 && ch_ok && g < G && a.n > 0) {
@@ -787,7 +771,7 @@ k_carry_update(const void* in, int in_fmt, size_t ch_stride, long n, f2* carry) 
     const long p = n - DDN_CARRY_LEN + i;
     f2 v;
     if (p >= 0) {
-        v = ddn_load_iq(in, in_fmt, ch_stride, ch, p);
+        v = ddn_iq_load_rt(in, in_fmt, (size_t)ch * ch_stride + p);
     } else {
         v = c[i + n]; // shift older history down
     }
@@ -859,25 +843,19 @@ launch_fused_c(const DdnFusedArgs& a, const DdnTapsK& tp, bool has_zero, hipStre
 extern "C" hipError_t
 ddn_dev_launch_fused_ex(const DdnFusedArgs* a, bool has_zero, int group, hipStream_t st) {
     DdnTapsK tp = {}; // (the kernels take their taps from a->taps_dev; the structure only selects the instance)
-    if (a->squelch_on) {
-        // squelch builds keep the first 256 LPF outputs of each block in LDS for the block-power sum: use the
-        // 8-channel workgroup so everything still fits in 160 KB
-        if (a->in_fmt == DDN_IN_CU8) {
-            return launch_fused_c<8, DDN_IN_CU8>(*a, tp, has_zero, st);
-        }
-        return launch_fused_c<8, DDN_IN_CF32>(*a, tp, has_zero, st);
+    // squelch builds keep the first 256 LPF outputs of each block in LDS for the block-power sum: they use the 8-channel
+    // workgroup so everything still fits in 160 KB
+    const bool small = a->squelch_on || group == 8 || (group != 16 && a->n_channels <= 2048);
+    switch (a->in_fmt) {
+        case DDN_IN_CU8:
+            return small ? launch_fused_c<8, DDN_IN_CU8>(*a, tp, has_zero, st) : launch_fused_c<DDN_GROUP, DDN_IN_CU8>(*a, tp, has_zero, st);
+        case DDN_IN_CS16:
+            return small ? launch_fused_c<8, DDN_IN_CS16>(*a, tp, has_zero, st) : launch_fused_c<DDN_GROUP, DDN_IN_CS16>(*a, tp, has_zero, st);
+        case DDN_IN_CF32:
+            return small ? launch_fused_c<8, DDN_IN_CF32>(*a, tp, has_zero, st) : launch_fused_c<DDN_GROUP, DDN_IN_CF32>(*a, tp, has_zero, st);
+        default:
+            return hipErrorInvalidValue; // (no instance reads a buffer of a format it does not know)
     }
-    const bool small = group == 8 || (group != 16 && a->n_channels <= 2048);
-    if (small) {
-        if (a->in_fmt == DDN_IN_CU8) {
-            return launch_fused_c<8, DDN_IN_CU8>(*a, tp, has_zero, st);
-        }
-        return launch_fused_c<8, DDN_IN_CF32>(*a, tp, has_zero, st);
-    }
-    if (a->in_fmt == DDN_IN_CU8) {
-        return launch_fused_c<DDN_GROUP, DDN_IN_CU8>(*a, tp, has_zero, st);
-    }
-    return launch_fused_c<DDN_GROUP, DDN_IN_CF32>(*a, tp, has_zero, st);
 }
 
 extern "C" hipError_t
@@ -892,6 +870,9 @@ ddn_dev_launch_fused(const DdnFusedArgs* a, const float* taps_host, int group, h
 extern "C" hipError_t
 ddn_dev_launch_carry(const void* in, int in_fmt, size_t ch_stride, long n, void* carry, int n_channels,
                      hipStream_t st) {
+    if (in_fmt != DDN_IN_CU8 && in_fmt != DDN_IN_CS16 && in_fmt != DDN_IN_CF32) {
+        return hipErrorInvalidValue;
+    }
     hipLaunchKernelGGL(k_carry_update, dim3((unsigned)n_channels), dim3(DDN_CARRY_LEN), 0, st, in, in_fmt, ch_stride,
                        n, (f2*)carry);
     return hipGetLastError();

@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "ddn_device.h"
+#include "ddn_iq_load_dev.h"
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -26,17 +27,6 @@ __constant__ float c_hb31[31] = {0.0f, 0.0f, Q15(13.0f), 0.0f, Q15(-73.0f), 0.0f
                                  0.0f, Q15(-2953.0f), 0.0f, Q15(1314.0f), 0.0f, Q15(-587.0f), 0.0f, Q15(233.0f), 0.0f,
                                  Q15(-73.0f), 0.0f, Q15(13.0f), 0.0f, 0.0f};
 #undef Q15
-
-template <int FMT>
-__device__ __forceinline__ f2
-load_iq(const void* base, size_t idx) {
-    if (FMT == DDN_IN_CU8) {
-        const uchar2 v = ((const uchar2*)base)[idx];
-        f2 r = {((float)v.x - 127.5f) * (1.0f / 127.5f), ((float)v.y - 127.5f) * (1.0f / 127.5f)};
-        return r;
-    }
-    return ((const f2*)base)[idx];
-}
 } // namespace
 
 // One workgroup = 256 outputs of one reference block of one channel (grid.x enumerates (block, tile-in-block), so the
@@ -68,7 +58,7 @@ k_hb_decim2(const void* __restrict__ in, long n_in, size_t in_stride, int block_
     for (int i = threadIdx.x; i < 512 + H; i += 256) {
         long j = j0 + i;
         j = j > last ? last : j;
-        win[i] = (j < 0) ? hist[(size_t)ch * H + (size_t)(H + j)] : load_iq<FMT>(in, (size_t)ch * in_stride + (size_t)j);
+        win[i] = (j < 0) ? hist[(size_t)ch * H + (size_t)(H + j)] : ddn_iq_load<FMT>(in, (size_t)ch * in_stride + (size_t)j);
     }
     __syncthreads();
     const long ml = m0 + threadIdx.x;
@@ -104,7 +94,7 @@ k_hb_hist(const void* __restrict__ in, long n, size_t in_stride, int H, f2* __re
     f2 v = {0.0f, 0.0f};
     if (i < H) {
         const long j = n - H + i;
-        v = (j >= 0) ? load_iq<FMT>(in, (size_t)ch * in_stride + (size_t)j) : hist[(size_t)ch * H + (size_t)(H + j)];
+        v = (j >= 0) ? ddn_iq_load<FMT>(in, (size_t)ch * in_stride + (size_t)j) : hist[(size_t)ch * H + (size_t)(H + j)];
     }
     __syncthreads();
     if (i < H) {
@@ -112,40 +102,40 @@ k_hb_hist(const void* __restrict__ in, long n, size_t in_stride, int H, f2* __re
     }
 }
 
-extern "C" hipError_t
-ddn_dev_hb_decim2(const void* in, int in_fmt, long n_in, size_t in_stride, int block_in, int n_channels, int taps_len,
-                  void* hist, void* out, size_t out_stride, hipStream_t st) {
-    if (n_channels <= 0 || n_in < 2) {
-        return hipSuccess;
-    }
+template <int FMT>
+static hipError_t
+launch_hb(const void* in, long n_in, size_t in_stride, int block_in, int n_channels, int taps_len, void* hist, void* out,
+          size_t out_stride, hipStream_t st) {
     const long n_blocks = (n_in + block_in - 1) / block_in;
     const int tiles_per_block = ((block_in >> 1) + 255) / 256;
     const dim3 grid((unsigned)(n_blocks * tiles_per_block), (unsigned)n_channels), blk(256);
     const f2* h = (const f2*)hist;
     f2* o = (f2*)out;
-    if (in_fmt == DDN_IN_CU8) {
-        if (taps_len == 31) {
-            hipLaunchKernelGGL((k_hb_decim2<DDN_IN_CU8, 31>), grid, blk, 0, st, in, n_in, in_stride, block_in, tiles_per_block, h, o, out_stride);
-        } else {
-            hipLaunchKernelGGL((k_hb_decim2<DDN_IN_CU8, 15>), grid, blk, 0, st, in, n_in, in_stride, block_in, tiles_per_block, h, o, out_stride);
-        }
+    if (taps_len == 31) {
+        hipLaunchKernelGGL((k_hb_decim2<FMT, 31>), grid, blk, 0, st, in, n_in, in_stride, block_in, tiles_per_block, h, o, out_stride);
     } else {
-        if (taps_len == 31) {
-            hipLaunchKernelGGL((k_hb_decim2<DDN_IN_CF32, 31>), grid, blk, 0, st, in, n_in, in_stride, block_in, tiles_per_block, h, o, out_stride);
-        } else {
-            hipLaunchKernelGGL((k_hb_decim2<DDN_IN_CF32, 15>), grid, blk, 0, st, in, n_in, in_stride, block_in, tiles_per_block, h, o, out_stride);
-        }
+        hipLaunchKernelGGL((k_hb_decim2<FMT, 15>), grid, blk, 0, st, in, n_in, in_stride, block_in, tiles_per_block, h, o, out_stride);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         return e;
     }
-    if (in_fmt == DDN_IN_CU8) {
-        hipLaunchKernelGGL((k_hb_hist<DDN_IN_CU8>), dim3((unsigned)n_channels), dim3(32), 0, st, in, n_in, in_stride,
-                           taps_len - 1, (f2*)hist);
-    } else {
-        hipLaunchKernelGGL((k_hb_hist<DDN_IN_CF32>), dim3((unsigned)n_channels), dim3(32), 0, st, in, n_in, in_stride,
-                           taps_len - 1, (f2*)hist);
-    }
+    hipLaunchKernelGGL((k_hb_hist<FMT>), dim3((unsigned)n_channels), dim3(32), 0, st, in, n_in, in_stride, taps_len - 1, (f2*)hist);
     return hipGetLastError();
+}
+
+extern "C" hipError_t
+ddn_dev_hb_decim2(const void* in, int in_fmt, long n_in, size_t in_stride, int block_in, int n_channels, int taps_len,
+                  void* hist, void* out, size_t out_stride, hipStream_t st) {
+    if (in_fmt != DDN_IN_CU8 && in_fmt != DDN_IN_CS16 && in_fmt != DDN_IN_CF32) {
+        return hipErrorInvalidValue; // (no instance reads a buffer of a format it does not know)
+    }
+    if (n_channels <= 0 || n_in < 2) {
+        return hipSuccess;
+    }
+    switch (in_fmt) {
+        case DDN_IN_CU8: return launch_hb<DDN_IN_CU8>(in, n_in, in_stride, block_in, n_channels, taps_len, hist, out, out_stride, st);
+        case DDN_IN_CS16: return launch_hb<DDN_IN_CS16>(in, n_in, in_stride, block_in, n_channels, taps_len, hist, out, out_stride, st);
+        default: return launch_hb<DDN_IN_CF32>(in, n_in, in_stride, block_in, n_channels, taps_len, hist, out, out_stride, st);
+    }
 }

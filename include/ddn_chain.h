@@ -32,7 +32,7 @@ typedef struct ddn_p25_chain_config {
     int n_channels;
     int samples_per_call; /* complex samples per channel and call (fixed per object) */
     int block_len;        /* front end: samples per reference full_demod() block (8192) */
-    int input_format;     /* DDN_IN_CU8 / DDN_IN_CF32 */
+    int input_format;     /* DDN_IN_CU8 / DDN_IN_CF32 / DDN_IN_CS16 (include/ddn_hip.h) */
     int vocoder;          /* 1 = IMBE synthesis to PCM, 0 = stop after the voice frames' FEC */
     int max_frames;       /* frame slots per channel and call; 0 = samples_per_call / 1800 + 6 (back-to-back single-block TSDUs, the
                              densest traffic a control channel carries; a run of 72-symbol TDUs or of false syncs can exceed it -
@@ -243,7 +243,7 @@ typedef struct ddn_p25p2_chain_config {
     int n_channels;
     int samples_per_call;
     int block_len;       /* the demodulator's full_demod() block (8192) */
-    int input_format;    /* DDN_IN_CU8 / DDN_IN_CF32 */
+    int input_format;    /* DDN_IN_CU8 / DDN_IN_CF32 / DDN_IN_CS16 (include/ddn_hip.h) */
     int sample_rate_hz;  /* 0 = 48000 (8 samples per symbol) */
     int vocoder;         /* 1 = AMBE synthesis to PCM */
     int max_groups;      /* syncs decoded per channel and call; 0 = samples_per_call * 6000 / rate / 720 + 3 */
@@ -292,7 +292,7 @@ typedef struct ddn_fsk4_chain_config {
     int n_channels;
     int samples_per_call;
     int block_len;
-    int input_format; /* DDN_IN_CU8 / DDN_IN_CF32 */
+    int input_format; /* DDN_IN_CU8 / DDN_IN_CF32 / DDN_IN_CS16 (include/ddn_hip.h) */
     int protocol;     /* DDN_FSK4_DMR / DDN_FSK4_NXDN48 / _NXDN96 / _M17 / _YSF / _DPMR / _DSTAR / _EDACS (include/ddn_fsk4.h) */
     int rf_mod;       /* 0 = C4FM rules, 2 = GFSK rules (what dsd-neo runs DMR with) */
     int inverted;     /* DMR: opts->inverted_dmr (handlers need 0); dPMR: opts->inverted_dpmr (-xd) */

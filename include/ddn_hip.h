@@ -60,7 +60,19 @@ enum {
     DDN_LPF_P25_CQPSK = 5,
 };
 
-enum { DDN_IN_CU8 = 0, DDN_IN_CF32 = 1 };
+/* Input sample formats of every entry point that takes raw I/Q.  All are interleaved I then Q, channel-major:
+ *   DDN_IN_CU8   unsigned byte pairs, 2 bytes per complex sample; widened as (u - 127.5) / 127.5
+ *                (widen_u8_to_f32_bias127, src/dsp/simd_widen.cpp:139-149)
+ *   DDN_IN_CF32  float pairs, 8 bytes per complex sample, taken as they are
+ *   DDN_IN_CS16  little-endian int16 pairs, 4 bytes per complex sample - one of the two SoapySDR stream formats and one of the three
+ *                capture formats; widened as (float)s * (1.0f / 32768.0f) like soapy_copy_cs16_samples()
+ *                (src/io/radio/rtl_device.cpp:1247-1264, scale set at :1316).  Every int16 is exact in binary32 and the scale is a
+ *                power of two, so the widened value is exact: a cs16 run equals, bit for bit, the cf32 run fed
+ *                (float)s * 2^-15.  The kernels load one 32-bit word per sample: the sample array must be 4-byte aligned
+ *                (DDN_EINVAL otherwise).  The j^n rotation and the cs16 input-level metrics of the reference stay with the host. */
+enum { DDN_IN_CU8 = 0, DDN_IN_CF32 = 1, DDN_IN_CS16 = 2 };
+/* bytes per complex sample of a format: 2, 8, 4; 0 for any other value.  Host function, touches no device. */
+size_t ddn_input_format_bytes(int input_format);
 
 /* Per-batch front-end configuration: the subset of struct demod_state (include/dsd-neo/dsp/demod_state.h:67-262)
  * that the FSK-discriminator path reads, fixed for all channels of the batch. */
@@ -70,7 +82,7 @@ typedef struct ddn_front_end_config {
     int symbol_rate_hz;  /* informational (fsk modem cfg) */
     int levels;          /* 2 or 4 */
     int lpf_profile;     /* DDN_LPF_* */
-    int input_format;    /* DDN_IN_CU8 / DDN_IN_CF32 */
+    int input_format;    /* DDN_IN_CU8 / DDN_IN_CF32 / DDN_IN_CS16 (layouts and widening: at the enum above) */
     int block_len;       /* complex samples per reference full_demod() block (edge-replication granule) */
     float squelch_level; /* channel_squelch_level; 0 = disabled (reference default) */
 } ddn_front_end_config;
@@ -104,7 +116,8 @@ int ddn_batch_set_iq_conditioning(ddn_batch* b, int dc_block_enable, int dc_shif
                                   float iqbal_ema_alpha);
 
 /* One pass of widen -> channel LPF -> (squelch) -> FSK discriminator over n complex samples per channel.
- *   d_iq   : [B][n] interleaved I/Q, u8 pairs (CU8) or float pairs (CF32), channel-major
+ *   d_iq   : [B][n] interleaved I/Q, channel-major: u8 pairs (CU8), float pairs (CF32) or little-endian int16 pairs (CS16, 4 bytes
+ *            per sample, widened as (float)s * (1.0f / 32768.0f), src/io/radio/rtl_device.cpp:1247-1264; d_iq 4-byte aligned)
  *   d_disc : [B][n] float discriminator samples (AGC'd to +-30000, clipped to int16 range)
  * The call is equivalent to ceil(n / block_len) consecutive full_demod() calls per channel; carried state
  * persists in `b` across calls.  Asynchronous on `hip_stream` (NULL = default stream). */
@@ -511,7 +524,8 @@ int dsd_resampler_process_block(ddn_dsd_resampler_state* state, const float* in,
  * src/dsp/demod_pipeline.cpp:1100-1118,1330-1350): channel LPF (profile DDN_LPF_P25_CQPSK) -> cqpsk_rms_agc ->
  * op25_fll_band_edge_cc -> op25_gardner_cc -> op25_diff_phasor_cc -> op25_costas_loop_cc -> qpsk_differential_demod
  * (include/dsd-neo/dsp/costas.h) for B channels; all loop state is carried inside the batch object.
- *   d_iq      : [B][n] interleaved I/Q (cu8 or cf32), channel-major; block_len = the reference's block size (LPF edge
+ *   d_iq      : [B][n] interleaved I/Q (cu8, cf32 or cs16 = little-endian int16 pairs, 4 bytes per sample, widened as
+ *               (float)s * (1.0f / 32768.0f), src/io/radio/rtl_device.cpp:1247-1264, 4-byte aligned), channel-major; block_len = the reference's block size (LPF edge
  *               rule); every block must hold >= 4 samples
  *   d_symbols : [B][sym_stride] f32 symbols (theta * 4/pi, nominal levels +-1 / +-3), sym_stride >=
  *               ddn_cqpsk_max_symbols(n); d_counts[B] = symbols produced by this call
@@ -522,7 +536,7 @@ typedef struct ddn_cqpsk_config {
     int symbol_rate_hz; /* 4800 (6000 for P25p2) */
     int lpf_profile;    /* DDN_LPF_P25_CQPSK */
     int lpf_enable;
-    int input_format;   /* DDN_IN_CU8 / DDN_IN_CF32 */
+    int input_format;   /* DDN_IN_CU8 / DDN_IN_CF32 / DDN_IN_CS16 (include/ddn_hip.h) */
     int block_len;
     float ted_gain;     /* 0 = the reference default */
 } ddn_cqpsk_config;

@@ -26,7 +26,7 @@ typedef struct ddn_node_config {
     int n_channels;       /* over all devices */
     int samples_per_call;
     int block_len;
-    int input_format;     /* DDN_IN_CU8 / DDN_IN_CF32 */
+    int input_format;     /* DDN_IN_CU8 / DDN_IN_CF32 / DDN_IN_CS16 (include/ddn_hip.h) */
     int vocoder;
     int modulation;       /* DDN_P25_MOD_* */
     int n_devices;        /* 0 = every visible device; more than are visible: the list wraps around (several chain objects share a

@@ -2,7 +2,10 @@
 """Per-stage throughput of the batched FEC / timing kernels on one MI355X, next to the CPU oracle on one core.
 Prints one JSON line per stage.  (bench.py stays the BASELINE metric; this is the per-row measurement of SURVEY §8.)
 
-    python tools/bench_stages.py [--reps 20]
+    python tools/bench_stages.py [--reps 20] [--input-format cu8|cs16|cf32] [--stages all|input]
+
+--input-format picks the raw I/Q format of the stages that read raw I/Q (the fused front end and the P25 chain step; default cu8);
+--stages input runs only those.
 """
 import argparse
 import ctypes as C
@@ -16,9 +19,89 @@ sys.path.insert(0, os.path.join(ROOT, "dsd-neo_amd", "bindings"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
+def input_stages(args, np, torch, ddn, orc):
+    """the stages that read raw I/Q, at the headline shape 4096 channels x 48000 samples, in the format --input-format names:
+    front_end_fused   ddn_front_end_run alone (HIP events on the launch stream)
+    p25_chain_step    ddn_p25_chain_run_pipelined on bench.py's traffic, I/Q resident on the device (host clock around steps that end
+                      in a device synchronise: the step spans the chain's own streams)
+    p25_chain_step_host_iq   ddn_p25_chain_run_host, the I/Q coming from pinned host memory, results left on the device
+    cs16 samples are 256 (u - 127.5) of the cu8 traffic (tests/cs16.py), cf32 samples its widened values: the same signal."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import cs16
+    fmt = {"cu8": ddn.IN_CU8, "cs16": ddn.IN_CS16, "cf32": ddn.IN_CF32}[args.input_format]
+    nbytes = ddn.lib().ddn_input_format_bytes(fmt)
+
+    def convert(u8):
+        if fmt == ddn.IN_CS16:
+            return cs16.cu8_to_cs16(u8)
+        if fmt == ddn.IN_CF32:
+            return ((u8.astype(np.float32) - np.float32(127.5)) * np.float32(1.0 / 127.5)).astype(np.float32)
+        return u8
+
+    def line(stage, n, ms, **more):
+        print(json.dumps(dict(stage=stage, input_format=args.input_format, n=n, ms=round(ms, 4), Msamples_per_s=round(n / ms / 1e3, 1),
+                              input_GBps=round(n * nbytes / ms / 1e6, 2), **more)), flush=True)
+
+    def host_timed(fn, reps):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / reps
+
+    B, n = 4096, 48000
+    st = torch.cuda.current_stream().cuda_stream
+    d_i = torch.from_numpy(np.tile(convert(orc.synth_c4fm_cu8(0, 8, n)), (B // 8, 1, 1))).cuda()
+    d_o = torch.zeros((B, n), dtype=torch.float32, device="cuda")
+    fb = ddn.Batch(B, block_len=8192, input_format=fmt)
+    fb.run_device(d_i.data_ptr(), n, d_o.data_ptr(), st)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(args.reps):
+        fb.run_device(d_i.data_ptr(), n, d_o.data_ptr(), st)
+    e1.record()
+    torch.cuda.synchronize()
+    line("front_end_fused", B * n, e0.elapsed_time(e1) / args.reps)
+    fb.close()
+    del d_i, d_o
+
+    voice, ctrl = bench.make_base_traffic(n)
+    rows = np.stack([(voice if kind == "voice" else ctrl)[bi] for kind, bi in (bench.channel_source(c) for c in range(2 * bench.N_BASE))])
+    d_iq = torch.from_numpy(np.tile(convert(rows), (B // len(rows), 1, 1))).cuda()
+    chain = ddn.P25ChainC(B, n, block_len=bench.BLOCK, input_format=fmt)
+    line("p25_chain_step", B * n, host_timed(lambda: chain.run_pipelined(d_iq.data_ptr()), args.reps))
+    chain.wait()
+    pinned = []
+    for _ in range(2):
+        p = C.c_void_p()
+        assert ddn.lib().ddn_host_alloc_pinned(B * n * nbytes, C.byref(p)) == 0
+        assert ddn.lib().ddn_device_download(p, d_iq.data_ptr(), B * n * nbytes) == 0
+        pinned.append(p)
+    k = [0]
+
+    def host_step():
+        chain.run_host(pinned[k[0] & 1], None)
+        k[0] += 1
+
+    line("p25_chain_step_host_iq", B * n, host_timed(host_step, args.reps), results="left on the device")
+    chain.wait()
+    chain.close()
+    for p in pinned:
+        ddn.lib().ddn_host_free_pinned(p)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--input-format", choices=["cu8", "cs16", "cf32"], default="cu8",
+                    help="raw I/Q format of the front-end stage and the P25 chain step (the other stages have one format)")
+    ap.add_argument("--stages", choices=["all", "input"], default="all",
+                    help="input: only the stages --input-format applies to (fused front end, P25 chain step from device and from host I/Q)")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -28,6 +111,9 @@ def main():
     l = ddn.lib()
     rng = np.random.default_rng(1)
     st = torch.cuda.current_stream().cuda_stream
+    input_stages(args, np, torch, ddn, orc)
+    if args.stages == "input":
+        return
 
     def timeit(fn):
         fn()

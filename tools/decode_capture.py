@@ -4,6 +4,8 @@ reference's --iq-replay log carries (NAC, DUID, TSBK opcodes with CRC status, LD
 voice-frame counts).  Everything between the capture file and the printed lines runs through the C-ABI: capture reader,
 front end, receive loop, framer gathers, BCH / trellis / CRC / Hamming / Reed-Solomon kernels.
 
+A cu8, cf32 or cs16 capture goes to the device in its own format (the kernels widen it).
+
 usage: python tools/decode_capture.py CAPTURE.iq[.json] [--lock SYMBOLS] [--max-frames N] [--m17]
        --lock: in-frame symbols after a sync (default 840 = LDU-sized; 156 / 336 suit one- / three-block TSDU control
                channels - dibits read outside the in-frame span carry no soft decisions)
@@ -33,18 +35,19 @@ def decode(path, lock=840, max_frames=64, out=print):
     if rc != 0:
         raise SystemExit("cannot open capture (%d): %s" % (rc, l.ddn_last_error().decode()))
     fmt, rate, base_dec, _, demod_rate = np.frombuffer(bytes(info[:24]), np.uint32)[1:6]
-    bps = {1: 2, 2: 8}.get(int(fmt))
-    if bps is None:
-        raise SystemExit("sample format %d is not supported by the front end (cu8 / cf32 only)" % fmt)
+    # capture format (DDN_IQ_FORMAT_*) -> (name, the front end's input format); every capture format goes to the device as it is
+    name, in_fmt = {1: ("cu8", ddn.IN_CU8), 2: ("cf32", ddn.IN_CF32), 3: ("cs16", ddn.IN_CS16)}.get(int(fmt), (None, None))
+    if name is None:
+        raise SystemExit("sample format %d is not a capture format this tool knows (cu8 / cf32 / cs16)" % fmt)
+    bps = l.ddn_input_format_bytes(in_fmt)
     n = n.value
     host = np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_uint8)), (n * bps,)).copy()
     l.ddn_iq_free(buf)
     out("capture: %d complex samples, %s @ %d Hz, base_decimation %d -> demod %d Hz"
-        % (n, "cu8" if fmt == 1 else "cf32", rate, base_dec, demod_rate))
+        % (n, name, rate, base_dec, demod_rate))
     passes = int(base_dec).bit_length() - 1
     n -= n % (1 << passes)
-    fe = ddn.Batch(1, sample_rate_hz=int(demod_rate), input_format=ddn.IN_CU8 if fmt == 1 else ddn.IN_CF32,
-                   block_len=8192)
+    fe = ddn.Batch(1, sample_rate_hz=int(demod_rate), input_format=in_fmt, block_len=8192)
     if passes:
         fe.set_decimation(passes)
     d_iq = torch.from_numpy(host[:n * bps]).cuda()
