@@ -59,7 +59,17 @@ class DemodState(C.Structure):  # == struct demod_state of include/ddn_demod_ada
                 ("rate_in", C.c_int), ("rate_out", C.c_int), ("output_kind", C.c_int), ("symbol_rate_hz", C.c_int),
                 ("symbol_levels", C.c_int), ("channel_lpf_enable", C.c_int), ("channel_lpf_profile", C.c_int),
                 ("channel_squelch_level", C.c_float), ("cqpsk_enable", C.c_int), ("ted_enabled", C.c_int), ("ted_sps", C.c_int),
-                ("ted_gain", C.c_float), ("ddn_adapter", C.c_void_p)]
+                ("ted_gain", C.c_float), ("ddn_adapter", C.c_void_p),
+                # the audio-monitor kind's members (after ddn_adapter: the offsets above stay)
+                ("downsample_passes", C.c_int), ("post_downsample", C.c_int), ("deemph", C.c_int), ("deemph_a", C.c_float),
+                ("audio_lpf_enable", C.c_int), ("audio_lpf_alpha", C.c_float), ("dc_block", C.c_int), ("rate_out2", C.c_int),
+                ("squelch_env", C.c_float), ("squelch_gate_open", C.c_int)]
+
+
+class FmAudioConfig(C.Structure):  # == ddn_fm_audio_config
+    _fields_ = [("post_downsample", C.c_int), ("deemph", C.c_int), ("deemph_tau_us", C.c_int), ("audio_lpf_cutoff_hz", C.c_int),
+                ("dc_block_off", C.c_int), ("lpr_fast_hz", C.c_int), ("lpr_slow_hz", C.c_int), ("squelch_env_attack", C.c_float),
+                ("squelch_env_release", C.c_float)]
 
 
 class FskModemState(C.Structure):
@@ -93,6 +103,15 @@ PROTOTYPES = {
     "ddn_batch_get_fsk_state": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "ddn_batch_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "ddn_batch_get_timing": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ddn_batch_set_audio_monitor": (C.c_int, [C.c_void_p, C.POINTER(FmAudioConfig)]),
+    "ddn_fm_audio_max_samples": (C.c_size_t, [C.c_void_p, C.c_size_t]),
+    "ddn_fm_audio_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    "ddn_fm_audio_host_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ddn_batch_get_audio_coefficients": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ddn_batch_get_audio_state": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "ddn_fm_audio_design": (C.c_int, [C.c_int, C.POINTER(FmAudioConfig), C.c_void_p, C.c_void_p]),
+    "ddn_fm_audio_plan": (C.c_int, [C.POINTER(FmAudioConfig), C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                    C.POINTER(C.c_size_t)]),
     "simd_fir_complex_apply": (None, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "simd_hb_decim2_complex": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "simd_hb_decim2_real": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
@@ -1162,6 +1181,53 @@ class Batch:
         t = np.zeros(3, np.float32)
         _check(lib().ddn_batch_get_timing(self.h, t.ctypes.data), "ddn_batch_get_timing")
         return t
+
+
+class FmAudio(Batch):
+    """A ddn_batch set to the analog FM monitor (ddn_batch_set_audio_monitor): full_demod()'s audio output kind.  `audio` = the
+    ddn_fm_audio_config fields by name; passes = the half-band cascade in front (the input then runs at sample_rate_hz << passes)."""
+
+    def __init__(self, n_channels, sample_rate_hz=48000, lpf_profile=LPF_WIDE, input_format=IN_CU8, block_len=8192, squelch_level=0.0,
+                 passes=0, **audio):
+        Batch.__init__(self, n_channels, sample_rate_hz, 4800, 4, lpf_profile, input_format, block_len, squelch_level)
+        if passes:
+            self.set_decimation(passes)
+        self.audio = FmAudioConfig(**audio)
+        _check(lib().ddn_batch_set_audio_monitor(self.h, C.byref(self.audio)), "ddn_batch_set_audio_monitor")
+
+    def max_samples(self, n):
+        return lib().ddn_fm_audio_max_samples(self.h, n)
+
+    def run_device(self, d_iq_ptr, n, d_audio_ptr, audio_stride, stream=None):
+        """-> the samples per channel this call wrote to each [audio_stride] row (known without a device sync)"""
+        cnt = C.c_size_t(0)
+        _check(lib().ddn_fm_audio_run(self.h, d_iq_ptr, n, d_audio_ptr, audio_stride, C.byref(cnt), stream), "ddn_fm_audio_run")
+        return cnt.value
+
+    def run_host(self, iq, n):
+        """iq: numpy [B, n, 2] uint8, float32 or (a cs16 batch) int16, channel-major.  Returns float32 [B, count]."""
+        import numpy as np
+        iq = np.ascontiguousarray(iq)
+        check_host_iq(self.cfg.input_format, iq, self.cfg.n_channels, n)
+        cap = max(1, self.max_samples(n))
+        out = np.zeros((self.cfg.n_channels, cap), np.float32)
+        cnt = C.c_size_t(0)
+        _check(lib().ddn_fm_audio_host_run(self.h, iq.ctypes.data, n, out.ctypes.data, cap, C.byref(cnt)), "ddn_fm_audio_host_run")
+        return np.ascontiguousarray(out[:, :cnt.value])
+
+    def coefficients(self):
+        """-> (float32 [3] {deemph_a, audio_lpf_alpha, 2^-11}, float32 [16] decimator taps)"""
+        import numpy as np
+        c3, t16 = np.zeros(3, np.float32), np.zeros(16, np.float32)
+        _check(lib().ddn_batch_get_audio_coefficients(self.h, c3.ctypes.data, t16.ctypes.data), "ddn_batch_get_audio_coefficients")
+        return c3, t16
+
+    def audio_state(self, ch):
+        """-> float32 [8] {pre_r, pre_j, deemph_avg, audio_lpf_state, dc_avg, now_lpr, squelch_env, gate}"""
+        import numpy as np
+        s = np.zeros(8, np.float32)
+        _check(lib().ddn_batch_get_audio_state(self.h, ch, s.ctypes.data), "ddn_batch_get_audio_state")
+        return s
 
 
 class P25RxConfig(C.Structure):

@@ -14,6 +14,7 @@
 #include <new>
 
 #include "ddn_api_util.h"
+#include "ddn_batch.h"
 #include "ddn_device.h"
 
 static thread_local char g_err[512] = "";
@@ -49,39 +50,6 @@ ddn_version(void) {
         }                                                                                                              \
     } while (0)
 
-struct ddn_batch {
-    ddn_front_end_config cfg;
-    float taps[DDN_MAX_TAPS + 1];
-    int taps_len;
-    int center;
-    int group; // channels per workgroup of the fused kernel (8 or 16; 0 = by batch size)
-    float* d_taps;
-    // segments (ddn_batch_set_segments): tap sets of the second and third run of the channel index, where those runs start
-    int n_seg, seg_first[3];
-    float taps_s[2][DDN_MAX_TAPS + 1];
-    float* d_taps_s[2];
-    ddn_f2* d_carry;      // [B][DDN_CARRY_LEN]
-    DdnFskState* d_state; // [B]
-    // host-call staging
-    void* d_in;
-    size_t in_cap;
-    float* d_out;
-    size_t out_cap;
-    int timing;
-    hipEvent_t ev[3];
-    int ev_valid;
-    // half-band decimation cascade in front of the channel LPF (0 = none)
-    int passes;
-    void* d_hbhist[DDN_MAX_HB_PASSES]; // [B][taps_len-1] complex per stage
-    void* d_dec[2];                    // ping-pong decimated streams
-    size_t dec_cap[2];
-    // optional IQ conditioning (row a5): unfused route channel LPF -> k_iq_cond_disc
-    DdnIqCondConfig iqc;
-    DdnIqCondState* d_iqstate; // [B]
-    void* d_lpf_hist;          // [B][taps_len - 1] complex
-    void* d_lpf;               // [B][n] complex channel-LPF output
-    size_t lpf_cap;
-};
 
 // bytes per complex sample of an input format; 0 = not a format (host only, touches no device)
 extern "C" size_t
@@ -181,6 +149,8 @@ ddn_batch_destroy(ddn_batch* b) {
     (void)hipFree(b->d_iqstate);
     (void)hipFree(b->d_lpf_hist);
     (void)hipFree(b->d_lpf);
+    (void)hipFree(b->d_audio_state);
+    (void)hipFree(b->d_audio_ring);
     for (int i = 0; i < DDN_MAX_HB_PASSES; i++) {
         (void)hipFree(b->d_hbhist[i]);
     }
@@ -201,6 +171,11 @@ ddn_batch_set_decimation(ddn_batch* b, int passes) {
     if ((b->cfg.block_len & ((1 << passes) - 1)) != 0 || (b->cfg.block_len >> passes) < b->taps_len) {
         ddn_set_error("ddn_batch_set_decimation: block_len %d must be a multiple of %d and leave >= %d samples",
                       b->cfg.block_len, 1 << passes, b->taps_len);
+        return DDN_ERANGE;
+    }
+    if (b->audio_on && (b->cfg.block_len >> passes) < b->audio_cfg.post_downsample) {
+        ddn_set_error("ddn_batch_set_decimation: a block of %d samples is shorter than the audio monitor's post_downsample = %d",
+                      b->cfg.block_len >> passes, b->audio_cfg.post_downsample);
         return DDN_ERANGE;
     }
     const size_t B = (size_t)b->cfg.n_channels;
@@ -229,8 +204,16 @@ ddn_batch_reset(ddn_batch* b, void* hip_stream) {
     HIP_DRV_TRY(ddn_dev_zero(b->d_state, sizeof(DdnFskState) * B, st));
     if (b->d_iqstate) {
         HIP_DRV_TRY(hipMemsetAsync(b->d_iqstate, 0, sizeof(DdnIqCondState) * B, st));
+    }
+    if (b->d_lpf_hist) {
         HIP_DRV_TRY(hipMemsetAsync(b->d_lpf_hist, 0, sizeof(ddn_f2) * B * (size_t)(b->taps_len - 1), st));
     }
+    if (b->d_audio_state) { // (all zero = a fresh stream: the kernel starts the envelope at 1 with the gate open)
+        HIP_DRV_TRY(hipMemsetAsync(b->d_audio_state, 0, sizeof(DdnFmAudioState) * B, st));
+        HIP_DRV_TRY(hipMemsetAsync(b->d_audio_ring, 0, sizeof(float) * B * 16, st));
+    }
+    b->audio_phase = 0;
+    b->audio_lpr_index = 0;
     return DDN_OK;
 }
 
@@ -240,10 +223,14 @@ ddn_batch_set_iq_conditioning(ddn_batch* b, int dc_block_enable, int dc_shift, i
     if (!b) {
         return DDN_EINVAL;
     }
+    if (b->audio_on && (dc_block_enable || iqbal_enable)) {
+        ddn_set_error("ddn_batch_set_iq_conditioning: the audio-monitor kind has no IQ conditioning stages");
+        return DDN_EINVAL;
+    }
     if ((dc_block_enable || iqbal_enable) && !b->d_iqstate) {
         const size_t B = (size_t)b->cfg.n_channels;
         if (hipMalloc(&b->d_iqstate, sizeof(DdnIqCondState) * B) != hipSuccess
-            || hipMalloc(&b->d_lpf_hist, sizeof(ddn_f2) * B * (size_t)(b->taps_len - 1)) != hipSuccess) {
+            || (!b->d_lpf_hist && hipMalloc(&b->d_lpf_hist, sizeof(ddn_f2) * B * (size_t)(b->taps_len - 1)) != hipSuccess)) {
             (void)hipFree(b->d_iqstate);
             b->d_iqstate = nullptr;
             ddn_set_error("ddn_batch_set_iq_conditioning: device allocation failed");
@@ -269,8 +256,8 @@ ddn_batch_get_taps(const ddn_batch* b, float* taps_out, int cap) {
     return b->taps_len;
 }
 
-static int
-grow(void** p, size_t* cap, size_t need) {
+int
+ddn_batch_grow(void** p, size_t* cap, size_t need) {
     if (*cap >= need) {
         return DDN_OK;
     }
@@ -299,6 +286,10 @@ ddn_batch_set_channels_per_workgroup(ddn_batch* b, int channels) {
 extern "C" int
 ddn_batch_set_segments(ddn_batch* b, int n_seg, const int32_t* seg_channels, const int32_t* lpf_profiles) {
     if (!b || n_seg < 1 || n_seg > 3 || !seg_channels || !lpf_profiles) {
+        return DDN_EINVAL;
+    }
+    if (b->audio_on) {
+        ddn_set_error("ddn_batch_set_segments: the audio-monitor kind has no segmented form");
         return DDN_EINVAL;
     }
     long total = 0;
@@ -407,8 +398,8 @@ check_front_end_run(const char* who, const ddn_batch* b, const void* iq, const f
 }
 
 // the cs16 kernels load one 32-bit word per complex sample
-static int
-check_cs16_aligned(const char* who, int input_format, const void* d_iq) {
+int
+ddn_batch_check_cs16_aligned(const char* who, int input_format, const void* d_iq) {
     if (input_format == DDN_IN_CS16 && (((uintptr_t)d_iq) & 3) != 0) {
         ddn_set_error("%s: cs16 input must be 4-byte aligned (d_iq %p)", who, d_iq);
         return DDN_EINVAL;
@@ -416,22 +407,18 @@ check_cs16_aligned(const char* who, int input_format, const void* d_iq) {
     return DDN_OK;
 }
 
-extern "C" int
-ddn_front_end_run(ddn_batch* b, const void* d_iq, size_t n, float* d_disc, void* hip_stream) {
-    DDN_TRY(check_front_end_run(__func__, b, d_iq, d_disc));
-    DDN_TRY(check_cs16_aligned(__func__, b->cfg.input_format, d_iq));
-    if (n == 0) {
-        return DDN_OK;
-    }
-    hipStream_t st = (hipStream_t)hip_stream;
+// the half-band cascade in front of the channel LPF, shared by the batch's output kinds: on return *d_iq / *in_fmt / *n / *block_len
+// describe the decimated stream (untouched with no passes)
+int
+ddn_batch_run_cascade(ddn_batch* b, const char* who, const void** d_iq_p, int* in_fmt_p, size_t* n_p, int* block_len_p, hipStream_t st) {
     const int B = b->cfg.n_channels;
-    int block_len = b->cfg.block_len;
-    int in_fmt = b->cfg.input_format;
+    const void* d_iq = *d_iq_p;
+    int in_fmt = *in_fmt_p, block_len = *block_len_p;
+    size_t n = *n_p;
     if (b->passes > 0) {
         // half-band cascade: 31-tap first stage, 15-tap afterwards, each stage on the block partition it inherits
         if ((n & (((size_t)1 << b->passes) - 1)) != 0) {
-            ddn_set_error("ddn_front_end_run: n = %zu must be a multiple of %d with %d decimation passes", n,
-                          1 << b->passes, b->passes);
+            ddn_set_error("%s: n = %zu must be a multiple of %d with %d decimation passes", who, n, 1 << b->passes, b->passes);
             return DDN_ERANGE;
         }
         for (int i = 0; i < b->passes; i++) {
@@ -454,18 +441,48 @@ ddn_front_end_run(ddn_batch* b, const void* d_iq, size_t n, float* d_disc, void*
         }
         n >>= b->passes;
     }
+    *d_iq_p = d_iq;
+    *in_fmt_p = in_fmt;
+    *n_p = n;
+    *block_len_p = block_len;
+    return DDN_OK;
+}
+
+// room for the channel LPF's complex output of n samples per channel
+int
+ddn_batch_grow_lpf(ddn_batch* b, size_t n, hipStream_t st) {
+    const size_t need = sizeof(ddn_f2) * (size_t)b->cfg.n_channels * n;
+    if (b->lpf_cap < need) {
+        HIP_DRV_TRY(hipStreamSynchronize(st));
+        (void)hipFree(b->d_lpf);
+        b->d_lpf = nullptr;
+        b->lpf_cap = 0;
+        HIP_DRV_TRY(hipMalloc(&b->d_lpf, need));
+        b->lpf_cap = need;
+    }
+    return DDN_OK;
+}
+
+extern "C" int
+ddn_front_end_run(ddn_batch* b, const void* d_iq, size_t n, float* d_disc, void* hip_stream) {
+    DDN_TRY(check_front_end_run(__func__, b, d_iq, d_disc));
+    DDN_TRY(ddn_batch_check_cs16_aligned(__func__, b->cfg.input_format, d_iq));
+    if (b->audio_on) {
+        ddn_set_error("ddn_front_end_run: the batch is set to the audio-monitor kind (ddn_fm_audio_run serves it)");
+        return DDN_EINVAL;
+    }
+    if (n == 0) {
+        return DDN_OK;
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int B = b->cfg.n_channels;
+    int block_len = b->cfg.block_len;
+    int in_fmt = b->cfg.input_format;
+    DDN_TRY(ddn_batch_run_cascade(b, "ddn_front_end_run", &d_iq, &in_fmt, &n, &block_len, st));
     if (b->iqc.dc_enable || b->iqc.bal_enable) {
         // IQ conditioning on: the stages sit between the channel LPF and the discriminator, so the LPF result goes
         // through HBM once (8 B/sample each way) and the recurrences run one lane per channel (ddn_iqcond.hip)
-        const size_t need = sizeof(ddn_f2) * (size_t)B * n;
-        if (b->lpf_cap < need) {
-            HIP_DRV_TRY(hipStreamSynchronize(st));
-            (void)hipFree(b->d_lpf);
-            b->d_lpf = nullptr;
-            b->lpf_cap = 0;
-            HIP_DRV_TRY(hipMalloc(&b->d_lpf, need));
-            b->lpf_cap = need;
-        }
+        DDN_TRY(ddn_batch_grow_lpf(b, n, st));
         DdnIqCondConfig c = b->iqc;
         c.squelch_on = b->cfg.squelch_level > 0.0f ? 1 : 0;
         c.squelch_level = b->cfg.squelch_level;
@@ -560,11 +577,11 @@ ddn_front_end_run_host(ddn_batch* b, const void* h_iq, size_t n, float* h_disc) 
     const size_t B = (size_t)b->cfg.n_channels;
     const size_t in_bytes = B * n * ddn_input_format_bytes(b->cfg.input_format);
     const size_t out_bytes = B * (n >> b->passes) * sizeof(float);
-    int rc = grow(&b->d_in, &b->in_cap, in_bytes);
+    int rc = ddn_batch_grow(&b->d_in, &b->in_cap, in_bytes);
     if (rc != DDN_OK) {
         return rc;
     }
-    rc = grow((void**)&b->d_out, &b->out_cap, out_bytes);
+    rc = ddn_batch_grow((void**)&b->d_out, &b->out_cap, out_bytes);
     if (rc != DDN_OK) {
         return rc;
     }

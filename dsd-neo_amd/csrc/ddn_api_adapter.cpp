@@ -6,6 +6,7 @@
 #include <new>
 #include <vector>
 
+#include "ddn_batch.h"
 #include "ddn_demod_adapter.h"
 #include "ddn_device.h"
 
@@ -23,6 +24,10 @@ struct Adapter {
     int ted_key[2] = {0, 0};
     float ted_gain = 0.0f;
     std::vector<float> cq_row; // CQPSK symbols of one call at the loop's own row capacity
+    ddn_batch* au = nullptr;   // the audio-monitor kind
+    int au_key[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    float au_f[3] = {0.0f, 0.0f, 0.0f};
+    std::vector<float> au_row;
 };
 
 Adapter*
@@ -48,6 +53,9 @@ ddn_demod_state_release(struct demod_state* s) {
     }
     if (a->ted) {
         ddn_ted_batch_destroy(a->ted);
+    }
+    if (a->au) {
+        ddn_batch_destroy(a->au);
     }
     delete a;
     s->ddn_adapter = nullptr;
@@ -125,7 +133,60 @@ full_demod(struct demod_state* s) {
         }
         return;
     }
-    ddn_set_error("full_demod adapter: output_kind %d (audio monitor) is outside this library's path", s->output_kind);
+    if (s->output_kind != DSD_DEMOD_OUTPUT_AUDIO_MONITOR) {
+        ddn_set_error("full_demod adapter: unknown output_kind %d", s->output_kind);
+        return;
+    }
+    // audio monitor: a one-channel batch in the audio kind; s->lowpassed holds the block in front of the half-band cascade
+    if (!s->channel_lpf_enable) {
+        ddn_set_error("full_demod adapter: the audio-monitor batch always runs the channel LPF (channel_lpf_enable = 0 unsupported)");
+        return;
+    }
+    const int passes = s->downsample_passes > 0 ? s->downsample_passes : 0;
+    const int key[9] = {rate,      s->channel_lpf_profile, passes,      s->post_downsample, s->deemph ? 1 : 0, s->audio_lpf_enable ? 1 : 0,
+                        s->dc_block ? 1 : 0, s->rate_in, s->rate_out2};
+    const float fk[3] = {s->channel_squelch_level, s->deemph_a, s->audio_lpf_alpha};
+    if (!a->au || memcmp(key, a->au_key, sizeof(key)) != 0 || memcmp(fk, a->au_f, sizeof(fk)) != 0) {
+        if (a->au) {
+            ddn_batch_destroy(a->au);
+            a->au = nullptr;
+        }
+        ddn_front_end_config c = {1, rate, s->symbol_rate_hz, s->symbol_levels, s->channel_lpf_profile, DDN_IN_CF32, kBlock,
+                                  s->channel_squelch_level};
+        ddn_fm_audio_config ac;
+        memset(&ac, 0, sizeof(ac));
+        ac.post_downsample = s->post_downsample;
+        ac.deemph = s->deemph ? 1 : 0;
+        ac.audio_lpf_cutoff_hz = s->audio_lpf_enable ? 1000 : 0; // (the switch; the coefficient itself is the state's, below)
+        ac.dc_block_off = s->dc_block ? 0 : 1;
+        ac.lpr_fast_hz = s->rate_in;
+        ac.lpr_slow_hz = s->rate_out2;
+        if (ddn_batch_create(&c, &a->au) != DDN_OK) {
+            return;
+        }
+        if ((passes > 0 && ddn_batch_set_decimation(a->au, passes) != DDN_OK) || ddn_batch_set_audio_monitor(a->au, &ac) != DDN_OK
+            || ddn_batch_override_audio_coefficients(a->au, s->deemph_a, s->audio_lpf_alpha) != DDN_OK) {
+            ddn_batch_destroy(a->au);
+            a->au = nullptr;
+            return;
+        }
+        memcpy(a->au_key, key, sizeof(key));
+        memcpy(a->au_f, fk, sizeof(fk));
+    }
+    const size_t cap = ddn_fm_audio_max_samples(a->au, (size_t)n) + 1;
+    if (a->au_row.size() < cap) {
+        a->au_row.resize(cap);
+    }
+    size_t cnt = 0;
+    if (ddn_fm_audio_host_run(a->au, s->lowpassed, (size_t)n, a->au_row.data(), cap, &cnt) == DDN_OK) {
+        memcpy(s->result, a->au_row.data(), sizeof(float) * cnt);
+        s->result_len = (int)cnt;
+        float st8[8];
+        if (ddn_batch_get_audio_state(a->au, 0, st8) == DDN_OK) {
+            s->squelch_env = st8[6];
+            s->squelch_gate_open = (int)st8[7];
+        }
+    }
 }
 
 extern "C" void

@@ -38,6 +38,33 @@ typedef struct DdnIqCondState { /* iq_dc_avg_r/i, iqbal_alpha_ema_r/i */
     float dc_r, dc_i, er, ei;
 } DdnIqCondState;
 
+typedef struct DdnFmAudioState { /* the words of demod_state the audio-monitor path carries per channel (ddn_fm_audio.hip) */
+    float pre_r, pre_j;                                  /* dsd_fm_demod history */
+    float deemph_avg, audio_lpf_state, dc_avg, now_lpr;  /* the post filters and low_pass_real */
+    float squelch_env;
+    int history_valid, gate_open;                        /* fm_demod_history_valid, squelch_gate_open */
+    int initialised;                                     /* 0 after a reset: squelch_env = 1, gate open on first use */
+} DdnFmAudioState;
+typedef struct DdnFmAudioArgs {
+    const void* in;  /* [B][stride] complex channel-LPF output */
+    float* out;      /* [B][out_stride] audio, compacted */
+    DdnFmAudioState* state;
+    float* ring;     /* [B][16] decimator inputs before this call, oldest first (read and written when M > 1) */
+    size_t stride, out_stride;
+    long n;          /* complex samples per channel in this call (after the half-band cascade) */
+    int block_len;   /* samples per full_demod() block at that rate */
+    int n_channels;
+    int squelch_on;
+    float squelch_level;
+    int M, phase0;   /* post_downsample (1 = off) and post_polydecim_phase at the call's first sample */
+    float taps[16];
+    int deemph_on, lpf_on, dc_on;
+    float deemph_a, lpf_alpha, dc_scale; /* already clamped to [0, 1] as the filters do */
+    int lpr_on, lpr_fast, lpr_slow, lpr_index0;
+    float lpr_recip;
+    float env_attack, env_release;
+} DdnFmAudioArgs;
+
 typedef struct DdnFusedArgs {
     const void* in;       /* [B][ch_stride] complex samples (cu8 pairs or float pairs) */
     float* out;           /* [B][out_stride] discriminator samples */
@@ -185,6 +212,7 @@ hipError_t ddn_dev_p25_matched_filter(const float* in, long n, size_t stride, in
 #define DDN_MAX_HB_PASSES 4
 hipError_t ddn_dev_hb_decim2(const void* in, int in_fmt, long n_in, size_t in_stride, int block_in, int n_channels,
                              int taps_len, void* hist, void* out, size_t out_stride, hipStream_t st);
+hipError_t ddn_dev_fm_audio(const DdnFmAudioArgs* args, hipStream_t st);
 hipError_t ddn_dev_p25_matched_filter_only(const float* in, long n, size_t stride, int n_channels, const float* hist,
                                            float* out, hipStream_t st);
 hipError_t ddn_dev_p25_filter_hist_update(const float* in, long n, size_t stride, int n_channels, float* hist,

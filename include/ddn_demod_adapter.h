@@ -2,7 +2,8 @@
  * A/B runs: one stream, one block per call, host pointers - per-call granularity is far too fine for a GPU, the batched
  * entry points (ddn_front_end_run, ddn_cqpsk_run, ddn_gardner_run) are the product.
  *
- *   void full_demod(struct demod_state*)        include/dsd-neo/dsp/demod_pipeline.h:106 (src/dsp/demod_pipeline.cpp:1300-1350)
+ *   void full_demod(struct demod_state*)        include/dsd-neo/dsp/demod_pipeline.h:106 (src/dsp/demod_pipeline.cpp:1300-1350),
+ *                                               all three output kinds
  *   void op25_gardner_cc(struct demod_state*)   include/dsd-neo/dsp/costas.h (src/dsp/costas.cpp:804-858)
  *   dsd_fsk_modem_discriminator_process         is in ddn_hip.h
  *
@@ -43,6 +44,23 @@ struct demod_state {
     int cqpsk_enable, ted_enabled, ted_sps;
     float ted_gain;                            /* 0 = the reference default */
     void* ddn_adapter;                         /* owned by the adapter; release with ddn_demod_state_release() */
+    /* DSD_DEMOD_OUTPUT_AUDIO_MONITOR reads these (after ddn_adapter: the offsets above stay).  A state is set up as
+     * demod_init_common_defaults does (src/io/radio/rtl_demod_config.cpp:258-337): post_downsample 1, dc_block 1, rate_out2 -1,
+     * squelch_env 1, squelch_gate_open 1.  deemph_a and audio_lpf_alpha are used as given (clamped to [0, 1] as the filters do).
+     * squelch_env and squelch_gate_open are OUT only: the stream's envelope and gate live on the device behind
+     * ddn_adapter, start at 1 / open with the first call (and again whenever a configuration member changes), and the values a caller
+     * stores here are ignored; after every call the two members hold what the reference's would.  The envelope's attack and release
+     * are the reference's defaults (0.125 / 0.03125): this struct has no members for them. */
+    int downsample_passes;                     /* half-band stages in front of the channel LPF; rate_in = rate_out << passes */
+    int post_downsample;                       /* <= 1 = off */
+    int deemph;
+    float deemph_a;
+    int audio_lpf_enable;
+    float audio_lpf_alpha;
+    int dc_block;
+    int rate_out2;                             /* low_pass_real to this rate from rate_in; <= 0 = off */
+    float squelch_env;
+    int squelch_gate_open;
 };
 
 void full_demod(struct demod_state* s);

@@ -146,6 +146,60 @@ int ddn_batch_get_fsk_state(ddn_batch* b, int channel, float out5[5]);
 int ddn_batch_set_timing(ddn_batch* b, int enable);
 int ddn_batch_get_timing(ddn_batch* b, float out3[3]);
 
+/* ---- analog FM monitor: full_demod()'s third output kind, DSD_DEMOD_OUTPUT_AUDIO_MONITOR, batched ------------------------
+ * What a dsd-neo run produces with no digital mode, with analog_only or under the M17 encoder
+ * (src/io/radio/rtl_demod_config.cpp:238-239).  Per full_demod() block, after the half-band cascade and the channel LPF, in the
+ * reference's order and IEEE operation order (src/dsp/demod_pipeline.cpp):
+ *   squelch gate           full_demod_update_channel_state :1003-1020 - a closed block has its I/Q zeroed, nothing else is reset
+ *   dsd_fm_demod           :628-666 - phase delta per sample, history seeded from the stream's first sample, pre_r / pre_j carried
+ *   post decimation        full_demod_apply_post_audio_decimation :1259-1293, audio_polydecim_process :412-439 (post_downsample > 1):
+ *                          16-tap Hamming-windowed sinc, ring and phase carried across blocks and calls
+ *   deemph_filter :849-867, audio_lpf_filter :895-916, dc_block_filter :874-888 (k = 11), each with its own switch
+ *   low_pass_real          :597-621 when lpr_slow_hz > 0: integrate-and-dump from lpr_fast_hz to lpr_slow_hz, 1 / (fast / slow) with the
+ *                          integer division as written; now_lpr and prev_lpr_index carried
+ *   squelch envelope       full_demod_apply_squelch_envelope :1311-1325 - one step per block, every output of the block scaled
+ * The output is the phase step in radians (|x| <= pi before the filters); the consumer-side gains of the reference's audio path stay
+ * with the host.  The mode lives on a ddn_batch and uses its rate (rate_out: the coefficients' Fs), profile, input_format, block_len,
+ * squelch_level and ddn_batch_set_decimation.  Segments and IQ conditioning have no audio form: each refuses the other (DDN_EINVAL).
+ * With the mode set ddn_front_end_run returns DDN_EINVAL, as ddn_fm_audio_run does on a plain batch.
+ *
+ * The number of outputs depends on lengths and the two carried integer phases alone, never on data or the squelch: every channel of
+ * a batch produces the same count, the batch keeps the phases on the host and the call returns the count without a device sync.
+ * Not restated: the reference keeps a block un-decimated when it yields no decimator output (:1268-1271), which takes a block shorter
+ * than post_downsample - a call whose last block (after the cascade) is shorter than post_downsample is refused with DDN_ERANGE, as
+ * is a block_len that short; and lpr_slow_hz > lpr_fast_hz (prev_lpr_index then grows without bound in the reference). */
+typedef struct ddn_fm_audio_config {   /* all zero = the reference's analog defaults where one exists */
+    int   post_downsample;      /* demod_state.post_downsample; <= 1 = off */
+    int   deemph;               /* 0 off, 1 on */
+    int   deemph_tau_us;        /* 0 -> 75; 50, 75, 750 (src/io/radio/rtl_sdr_fm.cpp:6183-6193) */
+    int   audio_lpf_cutoff_hz;  /* 0 = off; < 100 -> 100 (src/io/radio/rtl_sdr_fm.cpp:6213-6238) */
+    int   dc_block_off;         /* the reference default is ON (src/io/radio/rtl_demod_config.cpp:292) */
+    int   lpr_fast_hz, lpr_slow_hz; /* the two integers low_pass_real reads (rate_in, rate_out2); slow <= 0 = stage off */
+    float squelch_env_attack, squelch_env_release; /* 0 -> 0.125 / 0.03125 */
+} ddn_fm_audio_config;
+/* switches the batch to the audio-monitor kind (cfg NULL: back to the FSK discriminator).  Resets the batch, as
+ * ddn_batch_set_decimation on a batch in this kind does: a fresh stream, the two integer phases included. */
+int ddn_batch_set_audio_monitor(ddn_batch* b, const ddn_fm_audio_config* cfg);
+/* the most samples per channel a call of n input samples can produce, whatever the carried phases (a row's capacity) */
+size_t ddn_fm_audio_max_samples(const ddn_batch* b, size_t n);
+/* d_iq [B][n] as for ddn_front_end_run (n a multiple of 2^passes); d_audio [B][audio_stride] floats, the first *out_count of each row
+ * written, audio_stride >= the call's count (DDN_ERANGE otherwise, before anything runs).  Asynchronous on hip_stream. */
+int ddn_fm_audio_run(ddn_batch* b, const void* d_iq, size_t n, float* d_audio, size_t audio_stride, size_t* out_count, void* hip_stream);
+/* same, host buffers (H2D, run, D2H, synchronous) */
+int ddn_fm_audio_host_run(ddn_batch* b, const void* h_iq, size_t n, float* h_audio, size_t audio_stride, size_t* out_count);
+int ddn_batch_get_audio_coefficients(const ddn_batch* b, float out3[3] /* deemph_a, audio_lpf_alpha, 1/2^11 */, float taps16[16]);
+/* pre_r pre_j deemph_avg audio_lpf_state dc_avg now_lpr squelch_env gate (synchronous) */
+int ddn_batch_get_audio_state(ddn_batch* b, int channel, float out8[8]);
+/* The host side of the mode without a batch (no device needed).  ddn_fm_audio_design: the coefficients a batch at rate_out_hz would
+ * use - deemph_a as at src/io/radio/rtl_sdr_fm.cpp:6198-6210 (Q15 rounding included), the audio LPF alpha as at :6226-6237, and the
+ * 16 taps of audio_polydecim_design_taps (src/dsp/demod_pipeline.cpp:339-359; zeros when post_downsample <= 1).
+ * ddn_fm_audio_plan: the count rule of ddn_fm_audio_run - n input samples in blocks of block_len with `passes` half-band stages,
+ * from the carried phases *poly_phase (post_polydecim_phase) and *lpr_index (prev_lpr_index), which it advances; the refusals of the
+ * call (DDN_EINVAL / DDN_ERANGE) leave them untouched. */
+int ddn_fm_audio_design(int rate_out_hz, const ddn_fm_audio_config* cfg, float out3[3], float taps16[16]);
+int ddn_fm_audio_plan(const ddn_fm_audio_config* cfg, int passes, int block_len, size_t n, int* poly_phase, int* lpr_index,
+                      size_t* out_count);
+
 /* ---- P25 Phase 1 C4FM slicer + soft decisions, and the per-sample P25 matched filter, batched --------------
  * ddn_p25_slicer_run == one getDibitSoft() per symbol per channel (include/dsd-neo/core/dibit.h:43-52) for a stream
  * whose last sync type is P25p1 (thresholds track continuously): symbols [B][n] f32 -> records [B][n][10], the
@@ -379,7 +433,8 @@ int ddn_mode_config(const ddn_mode_flags* flags, int demod_rate_hz, ddn_mode_res
  * (include/dsd-neo/runtime/rtl_stream_io_hooks.h:25-32; callers src/dsp/dsd_symbol.c:889-920,1412-1435: count is 512 or
  * 1, blocks until >= 1 sample, < 0 on end of stream).  A ddn_stream_set holds one single-producer / single-consumer
  * float queue per channel: the producer pushes the rows of each batch interval (discriminator samples from
- * ddn_front_end_run_host, or CQPSK symbols with their per-channel counts), every decoder instance gets
+ * ddn_front_end_run_host, CQPSK symbols with their per-channel counts, or the audio-monitor kind's samples from
+ * ddn_fm_audio_run with the call's count for every channel), every decoder instance gets
  * state->rtl_ctx = ddn_stream_set_ctx(set, channel) and the host installs
  *     dsd_rtl_stream_io_hooks h = { ddn_hooks_read, ddn_hooks_return_pwr };  dsd_rtl_stream_io_hooks_set(h);
  * The metrics getters the symbol loop polls (rtl_stream_metrics_hooks.h:28-48: output_rate_hz, output_kind 0 = FSK

@@ -2,10 +2,10 @@
 """Per-stage throughput of the batched FEC / timing kernels on one MI355X, next to the CPU oracle on one core.
 Prints one JSON line per stage.  (bench.py stays the BASELINE metric; this is the per-row measurement of SURVEY §8.)
 
-    python tools/bench_stages.py [--reps 20] [--input-format cu8|cs16|cf32] [--stages all|input]
+    python tools/bench_stages.py [--reps 20] [--input-format cu8|cs16|cf32] [--stages all|input|fm_audio]
 
 --input-format picks the raw I/Q format of the stages that read raw I/Q (the fused front end and the P25 chain step; default cu8);
---stages input runs only those.
+--stages input runs only those; --stages fm_audio only the analog FM monitor next to its yardstick.
 """
 import argparse
 import ctypes as C
@@ -95,13 +95,57 @@ def input_stages(args, np, torch, ddn, orc):
         ddn.lib().ddn_host_free_pinned(p)
 
 
+def fm_audio_stage(args, np, torch, ddn, orc):
+    """the analog FM monitor (ddn_fm_audio_run) at 4096 channels x 48000 cu8 samples, no half-band stage, de-emphasis and DC block on,
+    low_pass_real 48000 -> 8000; and in the same process, on the same input, the unfused FSK route as the yardstick
+    (ddn_batch_set_iq_conditioning with the DC blocker on: the same channel-LPF kernel, then k_iq_cond_disc).  Per route: the two
+    kernels' times from the batch's own HIP events (median of --reps calls) and the whole call between two events around the loop."""
+    B, n = 4096, 48000
+    st = torch.cuda.current_stream().cuda_stream
+    d_i = torch.from_numpy(np.tile(orc.synth_c4fm_cu8(0, 8, n), (B // 8, 1, 1))).cuda()
+    d_o = torch.zeros((B, n), dtype=torch.float32, device="cuda")
+
+    def measure(batch, run):
+        run()
+        torch.cuda.synchronize()
+        batch.set_timing(True)
+        rows = []
+        for _ in range(args.reps):
+            run()
+            torch.cuda.synchronize()
+            rows.append(batch.timing())
+        batch.set_timing(False)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            run()
+        e1.record()
+        torch.cuda.synchronize()
+        lpf, second, _ = np.median(np.stack(rows), axis=0)
+        return float(lpf), float(second), e0.elapsed_time(e1) / args.reps
+
+    au = ddn.FmAudio(B, lpf_profile=ddn.LPF_P25_C4FM, block_len=8192, deemph=1, lpr_fast_hz=48000, lpr_slow_hz=8000)
+    cap = au.max_samples(n)
+    lpf, kern, call = measure(au, lambda: au.run_device(d_i.data_ptr(), n, d_o.data_ptr(), cap, st))
+    print(json.dumps(dict(stage="fm_audio", n=B * n, out_per_channel=cap, channel_lpf_ms=round(lpf, 4), k_fm_audio_ms=round(kern, 4),
+                          call_ms=round(call, 4), Msamples_per_s=round(B * n / call / 1e3, 1))), flush=True)
+    au.close()
+    fb = ddn.Batch(B, block_len=8192)
+    fb.set_iq_conditioning(1, 11, 0, 0.0, 0.0)
+    lpf, kern, call = measure(fb, lambda: fb.run_device(d_i.data_ptr(), n, d_o.data_ptr(), st))
+    print(json.dumps(dict(stage="fm_audio_yardstick_fsk_unfused_dc", n=B * n, channel_lpf_ms=round(lpf, 4), k_iq_cond_disc_ms=round(kern, 4),
+                          call_ms=round(call, 4), Msamples_per_s=round(B * n / call / 1e3, 1))), flush=True)
+    fb.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--input-format", choices=["cu8", "cs16", "cf32"], default="cu8",
                     help="raw I/Q format of the front-end stage and the P25 chain step (the other stages have one format)")
-    ap.add_argument("--stages", choices=["all", "input"], default="all",
-                    help="input: only the stages --input-format applies to (fused front end, P25 chain step from device and from host I/Q)")
+    ap.add_argument("--stages", choices=["all", "input", "fm_audio"], default="all",
+                    help="input: only the stages --input-format applies to (fused front end, P25 chain step from device and from host I/Q); "
+                         "fm_audio: only the analog FM monitor and its yardstick")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -111,9 +155,13 @@ def main():
     l = ddn.lib()
     rng = np.random.default_rng(1)
     st = torch.cuda.current_stream().cuda_stream
+    if args.stages == "fm_audio":
+        fm_audio_stage(args, np, torch, ddn, orc)
+        return
     input_stages(args, np, torch, ddn, orc)
     if args.stages == "input":
         return
+    fm_audio_stage(args, np, torch, ddn, orc)
 
     def timeit(fn):
         fn()

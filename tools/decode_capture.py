@@ -6,11 +6,14 @@ front end, receive loop, framer gathers, BCH / trellis / CRC / Hamming / Reed-So
 
 A cu8, cf32 or cs16 capture goes to the device in its own format (the kernels widen it).
 
-usage: python tools/decode_capture.py CAPTURE.iq[.json] [--lock SYMBOLS] [--max-frames N] [--m17]
+usage: python tools/decode_capture.py CAPTURE.iq[.json] [--lock SYMBOLS] [--max-frames N] [--m17] [--analog OUT.wav]
        --lock: in-frame symbols after a sync (default 840 = LDU-sized; 156 / 336 suit one- / three-block TSDU control
                channels - dibits read outside the in-frame span carry no soft decisions)
        --m17:  read the capture as M17 (cu8 at 48 kHz) through the fsk4 chain object instead and print a line per completed packet:
-               application length, CRC verdict, protocol identifier and, for SMS (0x05), the text"""
+               application length, CRC verdict, protocol identifier and, for SMS (0x05), the text
+       --analog OUT.wav: run the capture through the analog FM monitor instead (full_demod()'s audio output kind: de-emphasis 75 us,
+               DC block, low_pass_real to 8 kHz where the demod rate is a multiple of it) and write the audio as 16-bit PCM at full
+               scale pi - one phase step cannot exceed pi; the reference's consumer-side gains stay with the host"""
 import argparse
 import ctypes as C
 import os
@@ -226,13 +229,53 @@ def decode_m17(path, out=print):
     return lines
 
 
+def decode_analog(path, wav, out=print):
+    """the capture through ddn_fm_audio_run in calls of one second -> OUT.wav (ddn_wav_write_s16, full scale pi)"""
+    import numpy as np
+    import ddn
+    l = ddn.lib()
+    paths = (C.c_char_p * 1)(path.encode())
+    buf, n = C.c_void_p(), C.c_size_t()
+    info = (C.c_uint8 * 8192)()
+    rc = l.ddn_iq_load_batch(paths, 1, C.byref(buf), C.byref(n), info)
+    if rc != 0:
+        raise SystemExit("cannot open capture (%d): %s" % (rc, l.ddn_last_error().decode()))
+    fmt, rate, base_dec, _, demod_rate = (int(v) for v in np.frombuffer(bytes(info[:24]), np.uint32)[1:6])
+    dt, in_fmt = {1: (np.uint8, ddn.IN_CU8), 2: (np.float32, ddn.IN_CF32), 3: (np.int16, ddn.IN_CS16)}.get(fmt, (None, None))
+    if dt is None:
+        raise SystemExit("sample format %d is not a capture format this tool knows (cu8 / cf32 / cs16)" % fmt)
+    bps = l.ddn_input_format_bytes(in_fmt)
+    host = np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_uint8)), (n.value * bps,)).copy().view(dt).reshape(1, -1, 2)
+    l.ddn_iq_free(buf)
+    passes = base_dec.bit_length() - 1
+    block = 8192 << passes
+    audio_rate = 8000 if demod_rate % 8000 == 0 and demod_rate > 8000 else demod_rate
+    kw = dict(lpr_fast_hz=demod_rate, lpr_slow_hz=audio_rate) if audio_rate != demod_rate else {}
+    fm = ddn.FmAudio(1, sample_rate_hz=demod_rate, input_format=in_fmt, block_len=block, passes=passes, deemph=1, **kw)
+    per = block * max(1, (rate // block))                      # about a second, whole blocks: every call but the last ends on a block
+    total = host.shape[1] - host.shape[1] % (1 << passes)
+    parts = [fm.run_host(host[:, p:min(p + per, total)], min(p + per, total) - p) for p in range(0, total, per)]
+    pcm = np.ascontiguousarray(np.concatenate(parts, axis=1)[0]) if parts else np.zeros(0, np.float32)
+    fm.close()
+    rc = l.ddn_wav_write_s16(wav.encode(), audio_rate, 1, pcm.ctypes.data, pcm.size, float(np.float32(np.pi)))
+    if rc != 0:
+        raise SystemExit("cannot write %s (%d): %s" % (wav, rc, l.ddn_last_error().decode()))
+    out("analog: %d complex samples @ %d Hz (demod %d Hz) -> %d audio samples @ %d Hz, peak %.3f rad -> %s"
+        % (total, rate, demod_rate, pcm.size, audio_rate, float(np.abs(pcm).max()) if pcm.size else 0.0, wav))
+    return pcm
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("capture")
     ap.add_argument("--lock", type=int, default=840)
     ap.add_argument("--max-frames", type=int, default=64)
     ap.add_argument("--m17", action="store_true")
+    ap.add_argument("--analog", metavar="OUT.wav")
     a = ap.parse_args()
+    if a.analog:
+        decode_analog(a.capture, a.analog)
+        return
     if a.m17:
         decode_m17(a.capture)
         return
