@@ -1,6 +1,7 @@
 // ddn_api_chain_fsk4.cpp - the chain object of the protocols behind the fsk4 receive loop (include/ddn_chain.h): stage order, buffers
-// and streams on top of the library's own C-ABI stage calls.  Host-only code.  A protocol is a row of fsk4_traits[], a section of
-// ddn_fsk4_chain (ddn_chain_fsk4.h), a <proto>_alloc and a <proto>_decode.
+// and streams on top of the library's own C-ABI stage calls.  Host-only code.  A protocol is its row of the loop's table
+// (ddn_fsk4::kRow, ddn_fsk4_proto.h), a row of fsk4_traits[], a section of ddn_fsk4_chain (ddn_chain_fsk4.h), a <proto>_alloc and a
+// <proto>_decode.
 //
 // What it stands in for in a dsd-neo host: the demodulator thread's per-block loop (src/io/radio/rtl_sdr_fm.cpp:3458-3516) and
 // processFrame()'s DMR / NXDN branches (src/engine/protocol_dispatch.c -> dmr_data.c / dmr_bs.c, nxdn_frame.c), B channels wide.
@@ -11,16 +12,16 @@
 
 #include "ddn_chain_fsk4.h"
 #include "ddn_device.h"
+#include "ddn_fsk4_proto.h"
 #include "ddn_hip.h"
 
 struct ddn_fsk4_traits {
-    int sym_rate, levels, lpf; // the front end: symbols/s, slicer levels, channel filter
+    int levels, lpf;           // the front end: slicer levels, channel filter (its symbols/s are the loop's, ddn_fsk4::kRow)
     int T;                     // the tail of records kept back for the next call: a frame that began in this call ends inside it
     int min_sync_gap;          // symbols between two accepted syncs at least: bounds the decode slots (0 = the general bound)
     bool thresholds;           // every sync files the thresholds it left (s_thr / c_thr / d_thr)
-    // what the configuration may ask for: the handlers in the loop, inverted up to this value (-1 = not looked at), the vocoder, an
-    // rf_mod other than 0 / 2
-    bool handlers;
+    // what the configuration may ask for: inverted up to this value (-1 = not looked at), the vocoder, an rf_mod other than 0 / 2
+    // (the handlers in the loop: where the loop's row has a handler family)
     int inverted_max;
     bool vocoder, any_rf_mod;
     int (*alloc)(ddn_fsk4_chain*);
@@ -409,29 +410,30 @@ nxdn_decode(ddn_fsk4_chain* c, int cur, int, hipStream_t st) {
 }
 #undef BUF
 
-// One row per protocol, indexed by DDN_FSK4_*.  T: a DMR burst ends 54 symbols after its sync, an NXDN frame 182, an M17 frame 184;
+// One row per protocol, indexed by DDN_FSK4_* - the chain's own facts; the loop's (symbol rate, handler family) are in
+// ddn_fsk4::kRow.  T: a DMR burst ends 54 symbols after its sync, an NXDN frame 182, an M17 frame 184;
 // myc = 16 syncs can lie inside such a tail (a new sync needs 24 / 10 fresh symbols).
 static const ddn_fsk4_traits fsk4_traits[] = {
     {},
-    /* DMR    */ {4800, 4, DDN_LPF_12K5, 256, 0, false, true, -1, true, true, dmr_alloc, dmr_decode},
-    /* NXDN48 */ {2400, 4, DDN_LPF_6K25, 256, 0, false, true, -1, true, true, nxdn_alloc, nxdn_decode},
+    /* DMR    */ {4, DDN_LPF_12K5, 256, 0, false, -1, true, true, dmr_alloc, dmr_decode},
+    /* NXDN48 */ {4, DDN_LPF_6K25, 256, 0, false, -1, true, true, nxdn_alloc, nxdn_decode},
     // (NXDN96: a 12.5 kHz channel at 4800 symbols/s)
-    /* NXDN96 */ {4800, 4, DDN_LPF_12K5, 256, 0, false, true, -1, true, true, nxdn_alloc, nxdn_decode},
-    /* M17    */ {4800, 4, DDN_LPF_12K5, 256, 0, true, false, 0, true, true, m17_alloc, m17_decode},
+    /* NXDN96 */ {4, DDN_LPF_12K5, 256, 0, false, -1, true, true, nxdn_alloc, nxdn_decode},
+    /* M17    */ {4, DDN_LPF_12K5, 256, 0, true, 0, true, true, m17_alloc, m17_decode},
     // (a YSF frame's payload ends 460 symbols after its sync; the FICH ends 100 symbols after it)
-    /* YSF    */ {4800, 4, DDN_LPF_12K5, 480, 0, false, false, 0, true, true, ysf_alloc, ysf_decode},
+    /* YSF    */ {4, DDN_LPF_12K5, 480, 0, false, 0, true, true, ysf_alloc, ysf_decode},
     // (a dPMR superframe ends 372 symbols after its sync.)  The loop holds 372 symbols behind every sync and then hunts a fresh
     // 12-symbol window, so accepted syncs lie at least 384 symbols apart and the ones a call decodes (positions below its new-record
     // count) number ms / 384 + 1 at most
-    /* DPMR   */ {2400, 4, DDN_LPF_6K25, 480, 384, false, false, 1, true, false, dpmr_alloc, dpmr_decode},
+    /* DPMR   */ {4, DDN_LPF_6K25, 480, 384, false, 1, true, false, dpmr_alloc, dpmr_decode},
     // (D-STAR: 4800 symbols/s behind the 6.25 kHz filter the reference picks for -fd, as ddn_host_mode.c does; a header unit ends
     // 660 + 1992 = 2652 symbols after its sync.)  1992 / 2652 symbols behind every sync, then a fresh 24-symbol window: syncs at least
     // 2016 symbols apart
-    /* DSTAR  */ {4800, 4, DDN_LPF_6K25, 2688, 2016, true, false, 0, false, false, dstar_alloc, dstar_decode},
+    /* DSTAR  */ {4, DDN_LPF_6K25, 2688, 2016, true, 0, false, false, dstar_alloc, dstar_decode},
     // (EDACS: 9600 symbols/s, two levels, behind the ProVoice channel profile dsd_rtl_channel_profile_for(9600, 2, ..) picks,
     // src/runtime/decode_mode.c:83-99; a frame ends 240 symbols after its 48-symbol sync.)  240 symbols behind every sync, then a
     // fresh 48-symbol window: syncs at least 288 symbols apart
-    /* EDACS  */ {9600, 2, DDN_LPF_PROVOICE, 320, 288, true, false, 0, false, false, edacs_alloc, edacs_decode},
+    /* EDACS  */ {2, DDN_LPF_PROVOICE, 320, 288, true, 0, false, false, edacs_alloc, edacs_decode},
 };
 
 extern "C" void
@@ -456,7 +458,7 @@ static int
 fsk4_setup(ddn_fsk4_chain* c) {
     const ddn_fsk4_chain_config* cfg = &c->cfg;
     const ddn_fsk4_traits* tr = c->tr;
-    ddn_front_end_config fc = {c->B, 48000, tr->sym_rate, tr->levels, tr->lpf, cfg->input_format, cfg->block_len, 0.0f};
+    ddn_front_end_config fc = {c->B, 48000, ddn_fsk4::kRow[cfg->protocol].sym_rate, tr->levels, tr->lpf, cfg->input_format, cfg->block_len, 0.0f};
     DDN_TRY(ddn_batch_create(&fc, &c->fe));
     if (hipEventCreateWithFlags(&c->ev_reads, hipEventDisableTiming) != hipSuccess) {
         return DDN_EHIP;
@@ -508,8 +510,9 @@ fsk4_setup(ddn_fsk4_chain* c) {
 
 extern "C" int
 ddn_fsk4_chain_create(const ddn_fsk4_chain_config* cfg, ddn_fsk4_chain** out) {
-    const ddn_fsk4_traits* tr = (cfg && cfg->protocol >= DDN_FSK4_DMR && cfg->protocol <= DDN_FSK4_EDACS) ? &fsk4_traits[cfg->protocol] : nullptr;
-    if (!tr || !out || cfg->n_channels <= 0 || cfg->samples_per_call <= 0 || cfg->block_len <= 0 || (cfg->handlers && !tr->handlers)
+    static_assert(sizeof(fsk4_traits) / sizeof(fsk4_traits[0]) == ddn_fsk4::N_PROTO + 1, "one row per protocol of the loop");
+    const ddn_fsk4_traits* tr = (cfg && ddn_fsk4::known(cfg->protocol)) ? &fsk4_traits[cfg->protocol] : nullptr;
+    if (!tr || !out || cfg->n_channels <= 0 || cfg->samples_per_call <= 0 || cfg->block_len <= 0 || (cfg->handlers && !ddn_fsk4::kRow[cfg->protocol].handlers)
         || (tr->inverted_max >= 0 && (cfg->inverted < 0 || cfg->inverted > tr->inverted_max)) || (cfg->vocoder && !tr->vocoder)
         || (!tr->any_rf_mod && cfg->rf_mod != 0 && cfg->rf_mod != 2)) {
         ddn_set_error("ddn_fsk4_chain_create: bad configuration");

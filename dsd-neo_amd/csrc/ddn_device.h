@@ -143,7 +143,7 @@ typedef struct DdnRxState { /* per-channel words of dsd_state / frame_sync_runti
     long long dbg_wait;
 } DdnRxState;
 
-/* ---- profile-driven 4-level FSK receive loop (DMR / NXDN48), ddn_rx4.hip ---- */
+/* ---- fsk4 receive loop (the protocols of ddn_fsk4_proto.h), ddn_rx4.hip ---- */
 #define DDN_FSK4_MAX_PAT  20
 #define DDN_FSK4_MAX_TAPS 135
 #define DDN_FSK4_HIST     128 /* symbol / payload history kept per channel: 90 reachable + what the helper wave lags */
@@ -151,11 +151,18 @@ typedef struct DdnRxState { /* per-channel words of dsd_state / frame_sync_runti
 #ifndef DDN_FSK4_DMR_RC_PAT
 #define DDN_FSK4_DMR_RC_PAT 8 /* == include/ddn_fsk4.h: the DMR table's MS reverse-channel row */
 #endif
+/* What k_fsk4_rx reads at run time; a protocol's constants are compiled in (ddn_fsk4_proto.h).  The order is part of the kernel: its
+ * scalar loads come out in address order, and two scalars side by side are fused into one wider load, either of which moves the
+ * kernel's registers.  So the scalars keep their order and stay apart, with the byte tables and `handlers` (which the kernel does not
+ * read) between them; only sync_thr and pat_hi are meant to be fetched together. */
 typedef struct DdnFsk4Config {
-    int out_rate, sym_rate, rf_mod, win_len, t_max, warm_len, n_pat;
+    int out_rate;
+    uint8_t pat_type[DDN_FSK4_MAX_PAT];
+    int rf_mod;
+    uint8_t pat_neg[DDN_FSK4_MAX_PAT];
     uint32_t pat_bits[DDN_FSK4_MAX_PAT];
-    uint8_t pat_type[DDN_FSK4_MAX_PAT], pat_neg[DDN_FSK4_MAX_PAT], pat_class[DDN_FSK4_MAX_PAT];
-    int confirm, dmr_window, redigitize, slow_type, use_filter, nt;
+    int use_filter;
+    uint8_t pat_class[DDN_FSK4_MAX_PAT];
     int dbg; /* profiling only (env DDN_RX4_DBG) */
     int handlers;   /* 1 = the reference's handlers decide the in-frame length (ddn_fsk4h_dev.h) */
     int max_events; /* capacity of the per-channel event list */
@@ -178,6 +185,35 @@ typedef struct DdnFsk4State {
         uint32_t hist_hi; /* win_len > 24 (EDACS, no handlers): sign history bits 24..47, hist_bits holding bits 0..23 */
     };
 } DdnFsk4State;
+typedef struct DdnFsk4RxArgs { /* one launch of the loop (ddn_dev_fsk4_rx); B = n_channels */
+    const float* raw;       /* [B][stride] discriminator samples of this call */
+    const float* filt;      /* [B][stride] the always-on matched-filter stream of the same samples (read when cfg->use_filter) */
+    const float* prev_tail; /* [B][DDN_FSK4_MAX_TAPS - 1] the samples before this call, right-aligned */
+    float* fstale;          /* [B][DDN_FSK4_MAX_TAPS - 1] the gated filter's stale memory */
+    const float* taps;      /* [DDN_FSK4_MAX_TAPS] */
+    long n;                 /* samples per channel in this call */
+    size_t stride;
+    int n_channels;
+    const DdnFsk4Config* cfg; /* device memory */
+    DdnFsk4State* state;      /* [B] */
+    float *lbuf_store, *shist_store;     /* [24][B] level ring, [DDN_FSK4_HIST][B] symbol history */
+    uint8_t *phist_store, *rhist_store;  /* [DDN_FSK4_HIST][B] payload dibit / reliability history */
+    uint8_t *rec, *flags, *pay;          /* [B][max_sym][10], [B][max_sym], [B][max_sym][2] */
+    int32_t* counts;                     /* [B] */
+    size_t max_sym;
+    const int32_t* lock4;                /* [B][4] symbols read behind a sync, per sync class */
+    int32_t* sync_pos;                   /* [B][max_sync] */
+    uint8_t *sync_pat, *pre, *pre_rel;   /* [B][max_sync], [B][max_sync][DDN_FSK4_PRE] x 2 */
+    int32_t* n_sync;                     /* [B] */
+    int max_sync;
+    int channels_per_wave;  /* 1, 2 .. 32 */
+    int samples_per_symbol; /* out_rate / symbol rate, rounded up */
+    int protocol;           /* DDN_FSK4_* */
+    int handlers;           /* == cfg->handlers; then hwords [B][32] and hpay [B][144] carry the handlers' words and burst dibits */
+    int32_t* hwords;
+    uint8_t* hpay;
+    int32_t *events, *n_events; /* [B][cfg->max_events][4], [B], or both NULL */
+} DdnFsk4RxArgs;
 
 typedef struct DdnCqpskState { /* per-channel words of demod_state the CQPSK chain carries besides ted_state_t */
     float agc_avg;                          /* cqpsk_agc_avg */
@@ -224,17 +260,12 @@ hipError_t ddn_dev_p25_rx(const float* raw, const float* filt, const float* prev
                           uint8_t* flags, int32_t* counts, size_t max_sym, int channels_per_wave,
                           const int32_t* lock_cfg, DdnP25HState* hstate, float* hh_store, int32_t* events,
                           int32_t* n_events, hipStream_t st);
-hipError_t ddn_dev_fsk4_matched_filter(int nt, int tap_set, const float* in, long n, size_t stride, int n_channels, const float* hist,
+/* tap_set: ddn_fsk4::Taps (ddn_fsk4_proto.h), which also gives the tap count */
+hipError_t ddn_dev_fsk4_matched_filter(int tap_set, const float* in, long n, size_t stride, int n_channels, const float* hist,
                                        float* out, hipStream_t st);
-hipError_t ddn_dev_fsk4_filter_hist_update(int nt, const float* in, long n, size_t stride, int n_channels, float* hist,
+hipError_t ddn_dev_fsk4_filter_hist_update(int tap_set, const float* in, long n, size_t stride, int n_channels, float* hist,
                                            hipStream_t st);
-hipError_t ddn_dev_fsk4_rx(const float* raw, const float* filt, const float* prev_tail, float* fstale, const float* taps,
-                           long n, size_t stride, int n_channels, const DdnFsk4Config* cfg, DdnFsk4State* state,
-                           float* lbuf_store, float* shist_store, uint8_t* phist_store, uint8_t* rhist_store, uint8_t* rec,
-                           uint8_t* flags, uint8_t* pay, int32_t* counts, size_t max_sym, const int32_t* lock4,
-                           int32_t* sync_pos, uint8_t* sync_pat, uint8_t* pre, uint8_t* pre_rel, int32_t* n_sync,
-                           int max_sync, int channels_per_wave, int samples_per_symbol, int protocol, int handlers,
-                           int32_t* hwords, uint8_t* hpay, int32_t* events, int32_t* n_events, hipStream_t st);
+hipError_t ddn_dev_fsk4_rx(const DdnFsk4RxArgs* args, hipStream_t st);
 hipError_t ddn_dev_dmr_burst_gather(const uint8_t* rec, const int32_t* counts, size_t max_sym, const int32_t* sync_pos,
                                     const uint8_t* sync_pat, const uint8_t* pre, const int32_t* n_sync, int n_channels, int max_sync, int inverted,
                                     uint8_t* slot_type, uint8_t* info, uint8_t* cach, uint8_t* valid, hipStream_t st);

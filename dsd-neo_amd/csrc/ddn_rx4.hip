@@ -1,6 +1,7 @@
-// ddn_rx4.hip - batched fixed-protocol receive loop for the other 4-level FSK protocols of BASELINE configs[3]: DMR and
-// NXDN48.  One lane = one channel running what the reference's decoder thread runs per stream between
-// rtl_stream_read() and the protocol handler, driven by a profile (DdnFsk4Config):
+// ddn_rx4.hip - batched fixed-protocol receive loop for the FSK protocols besides P25 Phase 1 (BASELINE configs[3] runs
+// its DMR and NXDN48).  One row of ddn_fsk4::kRow (ddn_fsk4_proto.h) per protocol.  One lane = one channel running what the
+// reference's decoder thread runs per stream between rtl_stream_read() and the protocol handler: the protocol's constants are the
+// row's, compiled in; the batch's choices and the sync words come with a profile (DdnFsk4Config):
 //   getSymbol()      src/dsp/dsd_symbol.c:1343-1387,1769-1805; window selection :197-224 (C4FM left edge 1 once a DMR type
 //                    is the last sync; GFSK = the two samples next to the centre), accumulation :404-460 (sps-20 7..13 window
 //                    on top), slip rules :462-517 (sps 20 / GFSK / C4FM), clip only on C4FM :347-358, matched-filter family
@@ -30,9 +31,8 @@
 #include "ddn_crc_dev.h"
 #include "ddn_device.h"
 #include "ddn_slicer_dev.h"
+#include "ddn_fsk4_proto.h"
 #include "ddn_fsk4h_dev.h"
-#include "ddn_tables_fsk4.h"
-#include "ddn_tables_dpmr.h"
 #include "ddn_tables_ambe.h"
 
 namespace {
@@ -106,38 +106,16 @@ hunt_restart(DdnFsk4State& s) {
 }
 template <int PROTO>
 struct Fsk4Cfg {
-    // PROTO 1 DMR, 2 NXDN48, 3 NXDN96: NXDN's sync words, two-match confirmation and LICH gate at 4800 symbols/s on the 4800_4 hunt
-    // profile (level ring 24, src/dsp/dsd_frame_sync.c:1525-1556,1729-1744) behind the DMR matched filter
-    // (symbol_apply_matched_filter(), src/dsp/dsd_symbol.c:323-335)
-    // PROTO 4 M17 (round 5): C4FM lock at 4800 symbols/s without a matched filter (decode_mode_apply_m17(),
-    // src/runtime/decode_mode.c:486-510), eight-symbol words matched with one error allowed by frame_sync_try_m17()
-    // (src/dsp/dsd_frame_sync.c:865-1100: m17_hit() below; the pattern table only names the twelve outcomes), 8-symbol warm start,
-    // fixed counts behind a sync (dispatch_m17.c:25-68: preamble 8, everything else 184)
-    // PROTO 5 YSF (round 5): the 20-symbol FUSION_SYNC compared exactly in both polarities (frame_sync_try_ysf(),
-    // src/dsp/dsd_frame_sync.c:770-797), 20-symbol warm start, the DMR matched filter (src/dsp/dsd_symbol.c:306-309), a fixed count
-    // behind a sync (processYSF() reads 100 + 360 dibits for every frame type but FI = 3 with DT != 1, src/protocol/ysf/ysf.c)
-    // PROTO 6 dPMR (-fm): 2400 symbols/s on the 2400_4 hunt profile (level ring 12), the 12-symbol FS2 word compared exactly in the
-    // one polarity -xd selects (frame_sync_try_dpmr(), src/dsp/dsd_frame_sync.c:832-862), 12-symbol warm start, dpmr_filter
-    // (src/dsp/dsd_symbol.c:316-321), a fixed count behind a sync (processdPMRvoice() reads 372 dibits, dpmr_voice.c:397-425)
-    // PROTO 7 D-STAR (-fd): 4800 symbols/s on the 4800_2 hunt profile (level ring 24), the four 24-symbol words compared exactly
-    // (frame_sync_try_dstar(), src/dsp/dsd_frame_sync.c:1452-1503), 24-symbol warm start, no matched filter (dsd_symbol.c:300-336),
-    // fixed counts behind a sync (processDSTAR() 1992 symbols, processDSTAR_HD() 660 more)
-    // PROTO 8 EDACS (-fh / -fH / -fe / -fE): 9600 symbols/s on the 9600_2 hunt profile (5 samples per symbol at 48 ksps, level ring
-    // 24), the two 48-symbol words compared exactly (frame_sync_try_provoice(), src/dsp/dsd_frame_sync.c:1421-1450), 48-symbol warm
-    // start (frame_sync_accept_edacs(), :1399-1409), no matched filter, a fixed count behind a sync (edacs() reads 240 bits).  The
-    // sign history is 48 symbols long: bits 0..23 in hist_bits, 24..47 in hist_hi (`wide`); the patterns' high halves are in pat_hi.
-    static constexpr int sym_rate = (PROTO == 2 || PROTO == 6) ? 2400 : (PROTO == 8 ? 9600 : 4800);
-    static constexpr int win_len = (PROTO == 1 || PROTO == 7) ? 24 : (PROTO == 4 ? 8 : (PROTO == 5 ? 20 : (PROTO == 6 ? 12 : (PROTO == 8 ? 48 : 10))));
-    static constexpr int t_max = (PROTO == 2 || PROTO == 6) ? 12 : 24;
-    static constexpr int warm_len = (PROTO == 1 || PROTO == 7) ? 24 : (PROTO == 4 ? 8 : (PROTO == 5 ? 20 : (PROTO == 6 ? 12 : (PROTO == 8 ? 48 : 10))));
-    static constexpr int n_pat = PROTO == 1 ? 9 : (PROTO == 4 ? 12 : (PROTO == 5 || PROTO == 8 ? 2 : (PROTO == 6 ? 1 : (PROTO == 7 ? 4 : 10))));
-    static constexpr int confirm = (PROTO == 1 || PROTO == 4 || PROTO == 5 || PROTO == 6 || PROTO == 7 || PROTO == 8) ? 0 : 1, dmr_window = PROTO == 1 ? 1 : 0, redigitize = PROTO == 1 ? 1 : 0;
-    static constexpr bool wide = win_len > 24;      // sign history of more than 24 symbols (hist_bits + hist_hi)
+    // the protocol's constants: its row of ddn_fsk4::kRow (ddn_fsk4_proto.h), which also says where in the reference each is from
+    static constexpr const ddn_fsk4::Row& R = ddn_fsk4::kRow[PROTO];
+    static constexpr int sym_rate = R.sym_rate, win_len = R.win_len(), t_max = R.t_max, warm_len = R.warm_len, n_pat = R.n_pat();
+    static constexpr int confirm = R.confirm, dmr_window = R.dmr_window, redigitize = R.redigitize;
+    static constexpr bool wide = win_len > 24;      // sign history of more than 24 symbols (hist_bits + hist_hi; the patterns' high halves are in pat_hi)
     static constexpr int hcap = wide ? win_len : 24; // symbols the sign history counts up to
-    static constexpr bool short_sym = PROTO == 8;   // 5-sample symbols: the longer hand-off queue (Lds4 SHORT)
-    static constexpr bool m17 = PROTO == 4;
+    static constexpr bool short_sym = R.sps_min < 8; // 5-sample symbols: the longer hand-off queue (Lds4 SHORT)
+    static constexpr bool m17 = R.m17;
     static constexpr int slow_type = 0;
-    static constexpr int nt = PROTO == 2 ? DDN_NXDN48_FILTER_TAPS : (PROTO == 6 ? DDN_DPMR_FILTER_TAPS : DDN_DMR_FILTER_TAPS);
+    static constexpr int nt = ddn_fsk4::taps_len(R.taps);
     int out_rate, rf_mod, use_filter, dbg;
 };
 
@@ -237,8 +215,8 @@ k_fsk4_rx(const float* __restrict__ raw, const float* __restrict__ filt, const f
     const int ch = ch0 + lane;
     const bool live = !loader && lane < CPW && ch < n_channels;
     const int ln = lane < CPW ? lane : 0;
-    // The protocol's constants are compile-time (PROTO 1 = DMR, 2 = NXDN48; the host checks the profile against them), the
-    // batch's choices are read once from the profile in device memory, its pattern table sits in LDS.
+    // The protocol's constants are compile-time (Fsk4Cfg), the batch's choices are read once from the profile in device memory,
+    // its pattern table sits in LDS.
     using Cfg = Fsk4Cfg<PROTO>;
     Cfg cfg;
     cfg.out_rate = cfgp->out_rate;
@@ -2001,12 +1979,8 @@ k_nxdn_crc(const uint8_t* __restrict__ bytes, int stride, int n, int kind, uint8
 
 template <int CPW, int MAXW, int PROTO, bool HM>
 hipError_t
-launch(const float* raw, const float* filt, const float* prev_tail, float* fstale, const float* taps, long n, size_t stride,
-       int n_channels, const DdnFsk4Config* cfg, DdnFsk4State* state, float* lbuf_store, float* shist_store,
-       uint8_t* phist_store, uint8_t* rhist_store, uint8_t* rec, uint8_t* flags, uint8_t* pay, int32_t* counts,
-       size_t max_sym, const int32_t* lock4, int32_t* sync_pos, uint8_t* sync_pat, uint8_t* pre, uint8_t* pre_rel,
-       int32_t* n_sync, int max_sync, int32_t* hwords, uint8_t* hpay, int32_t* events,
-       int32_t* n_events, hipStream_t st) {
+launch(const DdnFsk4RxArgs& a, hipStream_t st) {
+    const int n_channels = a.n_channels;
     using LdsT = Lds4<CPW, Fsk4Cfg<PROTO>::short_sym>;
     const size_t shmem = HM ? (((sizeof(LdsT) + 15) & ~(size_t)15) + sizeof(Lds4H<CPW>)) : sizeof(LdsT);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fsk4_rx<CPW, MAXW, PROTO, HM>),
@@ -2023,100 +1997,62 @@ launch(const float* raw, const float* filt, const float* prev_tail, float* fstal
                 fa.numRegs, shmem, (n_channels + CPW - 1) / CPW);
     }
     hipLaunchKernelGGL((k_fsk4_rx<CPW, MAXW, PROTO, HM>), dim3((unsigned)((n_channels + CPW - 1) / CPW)), dim3(128), shmem, st,
-                       raw, filt, prev_tail, fstale, taps, n, stride, n_channels, cfg, state, lbuf_store, shist_store,
-                       phist_store, rhist_store, rec, flags, pay, counts, max_sym, lock4, sync_pos, sync_pat, pre, pre_rel,
-                       n_sync, max_sync, hwords, hpay, events, n_events);
+                       a.raw, a.filt, a.prev_tail, a.fstale, a.taps, a.n, a.stride, n_channels, a.cfg, a.state, a.lbuf_store,
+                       a.shist_store, a.phist_store, a.rhist_store, a.rec, a.flags, a.pay, a.counts, a.max_sym, a.lock4, a.sync_pos,
+                       a.sync_pat, a.pre, a.pre_rel, a.n_sync, a.max_sync, a.hwords, a.hpay, a.events, a.n_events);
     return hipGetLastError();
+}
+
+// The instantiations are what these walks reach: per CPW and protocol the row's MAXW values (ddn_fsk4::Row::maxw()), with the
+// handlers only where the row has a handler family.
+template <int CPW, int PROTO, bool HM>
+hipError_t
+launch_maxw(const DdnFsk4RxArgs& a, hipStream_t st) {
+    if constexpr (ddn_fsk4::kRow[PROTO].maxw_by_sps) {
+        if (ddn_fsk4::kRow[PROTO].maxw(a.samples_per_symbol > 0 ? a.samples_per_symbol : 64) == 22) {
+            return launch<CPW, 22, PROTO, HM>(a, st);
+        }
+    }
+    return launch<CPW, 12, PROTO, HM>(a, st);
+}
+template <int CPW, int PROTO = 1>
+hipError_t
+launch_proto(const DdnFsk4RxArgs& a, hipStream_t st) {
+    if constexpr (PROTO > ddn_fsk4::N_PROTO) {
+        return hipErrorInvalidValue;
+    } else {
+        if (a.protocol != PROTO) {
+            return launch_proto<CPW, PROTO + 1>(a, st);
+        }
+        if constexpr (ddn_fsk4::kRow[PROTO].handlers) {
+            if (a.handlers) {
+                return launch_maxw<CPW, PROTO, true>(a, st);
+            }
+        }
+        return launch_maxw<CPW, PROTO, false>(a, st);
+    }
+}
+template <int CPW = 1>
+hipError_t
+launch_cpw(const DdnFsk4RxArgs& a, hipStream_t st) { // the smallest CPW of 1, 2 .. 32 that holds channels_per_wave
+    if constexpr (CPW < 32) {
+        if (a.channels_per_wave > CPW) {
+            return launch_cpw<CPW * 2>(a, st);
+        }
+    }
+    return launch_proto<CPW>(a, st);
 }
 } // namespace
 
 extern "C" hipError_t
-ddn_dev_fsk4_rx(const float* raw, const float* filt, const float* prev_tail, float* fstale, const float* taps, long n,
-                size_t stride, int n_channels, const DdnFsk4Config* cfg, DdnFsk4State* state, float* lbuf_store,
-                float* shist_store, uint8_t* phist_store, uint8_t* rhist_store, uint8_t* rec, uint8_t* flags, uint8_t* pay,
-                int32_t* counts, size_t max_sym, const int32_t* lock4, int32_t* sync_pos, uint8_t* sync_pat, uint8_t* pre,
-                uint8_t* pre_rel, int32_t* n_sync, int max_sync, int channels_per_wave, int cfg_sps, int protocol, int handlers,
-                int32_t* hwords, uint8_t* hpay, int32_t* events, int32_t* n_events, hipStream_t st) {
-    if (n_channels <= 0 || n <= 0) {
+ddn_dev_fsk4_rx(const DdnFsk4RxArgs* a, hipStream_t st) {
+    if (a->n_channels <= 0 || a->n <= 0) {
         return hipSuccess;
     }
-    if (protocol < 1 || protocol > 8) {
+    if (!ddn_fsk4::known(a->protocol) || (a->handlers && (!ddn_fsk4::kRow[a->protocol].handlers || !a->hwords || !a->hpay))) {
         return hipErrorInvalidValue;
     }
-    if ((protocol == 4 || protocol == 5 || protocol == 6 || protocol == 7 || protocol == 8) && handlers) {
-        return hipErrorInvalidValue; // M17 / YSF / dPMR / D-STAR / EDACS frames are fixed counts: no handler family
-    }
-    if (handlers && (!hwords || !hpay)) {
-        return hipErrorInvalidValue;
-    }
-    // MAXW: the longest whole symbol the straight pass takes (samples per symbol + one slip sample); 12 covers 4800 baud at
-    // 48 ksps, 22 covers 2400 baud
-    const int sps = cfg_sps > 0 ? cfg_sps : 64;
-#define DDN_RX4_ARGS                                                                                                       \
-    raw, filt, prev_tail, fstale, taps, n, stride, n_channels, cfg, state, lbuf_store, shist_store, phist_store, rhist_store, rec,  \
-        flags, pay, counts, max_sym, lock4, sync_pos, sync_pat, pre, pre_rel, n_sync, max_sync, hwords, hpay, events,           \
-        n_events, st
-#define DDN_RX4_GO(CPW_, MAXW_)                                                                                            \
-    do {                                                                                                                   \
-        if (protocol == 1) {                                                                                               \
-            return handlers ? launch<CPW_, MAXW_, 1, true>(DDN_RX4_ARGS) : launch<CPW_, MAXW_, 1, false>(DDN_RX4_ARGS);     \
-        }                                                                                                                  \
-        if (protocol == 3) { /* NXDN96: 10 samples per symbol at 48 ksps - the straight pass of 12 */                      \
-            return handlers ? launch<CPW_, 12, 3, true>(DDN_RX4_ARGS) : launch<CPW_, 12, 3, false>(DDN_RX4_ARGS);           \
-        }                                                                                                                  \
-        if (protocol == 4) { /* M17: 4800 symbols/s, fixed counts */                                                       \
-            return launch<CPW_, 12, 4, false>(DDN_RX4_ARGS);                                                                \
-        }                                                                                                                  \
-        if (protocol == 5) { /* YSF: 4800 symbols/s, fixed counts */                                                       \
-            return launch<CPW_, 12, 5, false>(DDN_RX4_ARGS);                                                                \
-        }                                                                                                                  \
-        if (protocol == 6) { /* dPMR: 2400 symbols/s, fixed counts */                                                      \
-            return launch<CPW_, MAXW_, 6, false>(DDN_RX4_ARGS);                                                             \
-        }                                                                                                                  \
-        if (protocol == 7) { /* D-STAR: 4800 symbols/s, fixed counts */                                                    \
-            return launch<CPW_, 12, 7, false>(DDN_RX4_ARGS);                                                                \
-        }                                                                                                                  \
-        if (protocol == 8) { /* EDACS: 9600 symbols/s, 48-symbol words, a fixed count */                                   \
-            return launch<CPW_, 12, 8, false>(DDN_RX4_ARGS);                                                                \
-        }                                                                                                                  \
-        return handlers ? launch<CPW_, MAXW_, 2, true>(DDN_RX4_ARGS) : launch<CPW_, MAXW_, 2, false>(DDN_RX4_ARGS);         \
-    } while (0)
-    if (channels_per_wave <= 1) {
-        if (sps <= 11) {
-            DDN_RX4_GO(1, 12);
-        }
-        DDN_RX4_GO(1, 22);
-    }
-    if (channels_per_wave <= 2) {
-        if (sps <= 11) {
-            DDN_RX4_GO(2, 12);
-        }
-        DDN_RX4_GO(2, 22);
-    }
-    if (channels_per_wave <= 4) {
-        if (sps <= 11) {
-            DDN_RX4_GO(4, 12);
-        }
-        DDN_RX4_GO(4, 22);
-    }
-    if (channels_per_wave <= 8) {
-        if (sps <= 11) {
-            DDN_RX4_GO(8, 12);
-        }
-        DDN_RX4_GO(8, 22);
-    }
-    if (channels_per_wave <= 16) {
-        if (sps <= 11) {
-            DDN_RX4_GO(16, 12);
-        }
-        DDN_RX4_GO(16, 22);
-    }
-    if (sps <= 11) {
-        DDN_RX4_GO(32, 12);
-    }
-    DDN_RX4_GO(32, 22);
-#undef DDN_RX4_GO
-#undef DDN_RX4_ARGS
+    return launch_cpw(*a, st);
 }
 
 extern "C" hipError_t
@@ -2454,18 +2390,19 @@ ddn_dev_nxdn_crc(const uint8_t* bytes, int stride, int n, int kind, uint8_t* ok,
 }
 
 extern "C" hipError_t
-ddn_dev_fsk4_matched_filter(int nt, int tap_set, const float* in, long n, size_t stride, int n_channels, const float* hist, float* out,
+ddn_dev_fsk4_matched_filter(int tap_set, const float* in, long n, size_t stride, int n_channels, const float* hist, float* out,
                             hipStream_t st) {
+    using namespace ddn_fsk4;
     if (n_channels <= 0 || n <= 0) {
         return hipSuccess;
     }
     const dim3 grid((unsigned)((n + 1023) / 1024), (unsigned)n_channels);
-    if (nt == DDN_DMR_FILTER_TAPS && tap_set == 0) {
-        hipLaunchKernelGGL((k_fsk4_matched_filter<DDN_DMR_FILTER_TAPS, 0>), grid, dim3(128), 0, st, in, n, stride, hist, out);
-    } else if (nt == DDN_NXDN48_FILTER_TAPS && tap_set == 1) {
-        hipLaunchKernelGGL((k_fsk4_matched_filter<DDN_NXDN48_FILTER_TAPS, 1>), grid, dim3(128), 0, st, in, n, stride, hist, out);
-    } else if (nt == DDN_DPMR_FILTER_TAPS && tap_set == 2) {
-        hipLaunchKernelGGL((k_fsk4_matched_filter<DDN_DPMR_FILTER_TAPS, 2>), grid, dim3(128), 0, st, in, n, stride, hist, out);
+    if (tap_set == TAPS_DMR) {
+        hipLaunchKernelGGL((k_fsk4_matched_filter<taps_len(TAPS_DMR), TAPS_DMR>), grid, dim3(128), 0, st, in, n, stride, hist, out);
+    } else if (tap_set == TAPS_NXDN48) {
+        hipLaunchKernelGGL((k_fsk4_matched_filter<taps_len(TAPS_NXDN48), TAPS_NXDN48>), grid, dim3(128), 0, st, in, n, stride, hist, out);
+    } else if (tap_set == TAPS_DPMR) {
+        hipLaunchKernelGGL((k_fsk4_matched_filter<taps_len(TAPS_DPMR), TAPS_DPMR>), grid, dim3(128), 0, st, in, n, stride, hist, out);
     } else {
         return hipErrorInvalidValue;
     }
@@ -2473,11 +2410,11 @@ ddn_dev_fsk4_matched_filter(int nt, int tap_set, const float* in, long n, size_t
 }
 
 extern "C" hipError_t
-ddn_dev_fsk4_filter_hist_update(int nt, const float* in, long n, size_t stride, int n_channels, float* hist,
+ddn_dev_fsk4_filter_hist_update(int tap_set, const float* in, long n, size_t stride, int n_channels, float* hist,
                                 hipStream_t st) {
     if (n_channels <= 0 || n <= 0) {
         return hipSuccess;
     }
-    hipLaunchKernelGGL(k_fsk4_filter_hist, dim3((unsigned)n_channels), dim3(192), 0, st, nt, in, n, stride, hist);
+    hipLaunchKernelGGL(k_fsk4_filter_hist, dim3((unsigned)n_channels), dim3(192), 0, st, ddn_fsk4::taps_len(tap_set), in, n, stride, hist);
     return hipGetLastError();
 }
