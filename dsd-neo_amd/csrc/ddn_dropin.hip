@@ -7,7 +7,10 @@
 //   widen_u8_to_f32_bias127            reference: src/dsp/simd_widen.cpp:139-149
 //   ddn_fsk_modem_discriminator_process reference: src/dsp/fsk_modem.c:135-164
 // Like the reference's dispatcher (src/dsp/simd_fir.cpp:303-306,350-356) blocks shorter than 2*taps_len floats
-// use the non-fused (mul, add) order, longer ones the FMA order of the AVX2 unit.
+// use the non-fused (mul, add) order, longer ones the FMA order of the AVX2 unit - its vector loops' for the outputs they compute,
+// its scalar helpers' (centre product first) for the block-edge outputs they leave over.  The batched kernels (ddn_front_end.hip,
+// ddn_halfband.hip, ddn_cqpsk.hip) keep the vector loops' order for every output of a long block: the two differ only in the sign
+// of an output whose every product is a zero.
 
 #include <hip/hip_runtime.h>
 
@@ -35,10 +38,13 @@ splat<f2>(float h) {
 }
 
 // scratch = [hist (taps_len-1)] [block (n_in)] [pad: last sample repeated `center` times]
+// fused: outputs [vec_begin, vec_end) are the ones the reference's AVX2 unit computes in its vector loop (FMA onto +0.0 first);
+// the others go through its scalar helpers, which start from the plain centre product and fuse the rest
+// (src/dsp/simd_fir_avx2.cpp:143-160, 186-225, 310-319).  The two differ in the sign of an all-zero window's output.
 template <typename V>
 __global__ void
 k_sym_fir_single(const V* __restrict__ scratch, const float* __restrict__ taps, int taps_len, int n_out, int stride,
-                 int tap_step, int fused, V* __restrict__ out) {
+                 int tap_step, int fused, int vec_begin, int vec_end, V* __restrict__ out) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= n_out) {
         return;
@@ -47,7 +53,9 @@ k_sym_fir_single(const V* __restrict__ scratch, const float* __restrict__ taps, 
     const int center = hist_len >> 1;
     const int ci = hist_len + n * stride;
     V acc;
-    if (fused) {
+    if (fused && (n < vec_begin || n >= vec_end)) {
+        acc = splat<V>(taps[center]) * scratch[ci]; // the AVX2 unit's scalar helper: a zero product keeps its sign
+    } else if (fused) {
         acc = __builtin_elementwise_fma(splat<V>(taps[center]), scratch[ci], splat<V>(0.0f));
     } else {
         acc = splat<V>(0.0f) + splat<V>(taps[center]) * scratch[ci];
@@ -236,6 +244,27 @@ shift_hist(float* hist, const float* in, int n, int hist_len, int in_stride, int
     }
 }
 
+// [*begin, *end): the outputs of a complex half-band block of n samples that the reference's AVX2 unit computes in its vector
+// loop.  15 and 31 taps (src/dsp/simd_fir_avx2.cpp:348-390): after the outputs whose window reaches the history, eight per step
+// while the step's whole load footprint lies inside the block; other lengths (:499-511): four per step from output 0.
+void
+ddn_hb_vector_span(int n, int taps_len, int* begin, int* end) {
+    const int n_out = n >> 1;
+    if (taps_len == 15 || taps_len == 31) {
+        const int center = (taps_len - 1) >> 1;
+        int i = (center + 1) >> 1;
+        i = i < n_out ? i : n_out;
+        *begin = i;
+        while (i + 7 < n_out && (i << 1) + center + 15 < n) {
+            i += 8;
+        }
+        *end = i;
+    } else {
+        *begin = 0;
+        *end = n_out & ~3;
+    }
+}
+
 // returns complex outputs written, or <0 on device failure
 int
 run_complex(const float* in, int in_len, float* out, float* hist_i, float* hist_q, const float* taps, int taps_len,
@@ -245,6 +274,10 @@ run_complex(const float* in, int in_len, float* out, float* hist_i, float* hist_
     const int center = hist_len >> 1;
     const int n_out = (stride == 2) ? (n >> 1) : n;
     const int fused = (in_len >= taps_len * 2) ? 1 : 0;
+    int vec_begin = 0, vec_end = n_out & ~3; // the plain filter: eight, then four per step (simd_fir_avx2.cpp:425-446)
+    if (stride == 2) {
+        ddn_hb_vector_span(n, taps_len, &vec_begin, &vec_end);
+    }
     std::vector<float> scratch((size_t)(hist_len + n + center + 2) * 2);
     for (int k = 0; k < hist_len; k++) {
         scratch[2 * (size_t)k] = hist_i[k];
@@ -268,7 +301,8 @@ run_complex(const float* in, int in_len, float* out, float* hist_i, float* hist_
             return DDN_EHIP;
         }
         hipLaunchKernelGGL((k_sym_fir_single<f2>), dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, 0,
-                           (const f2*)ds.p, (const float*)dt.p, taps_len, n_out, stride, stride, fused, (f2*)dout.p);
+                           (const f2*)ds.p, (const float*)dt.p, taps_len, n_out, stride, stride, fused, vec_begin, vec_end,
+                           (f2*)dout.p);
         if (hipGetLastError() != hipSuccess
             || hipMemcpy(out, dout.p, (size_t)n_out * 2 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
             ddn_set_error("drop-in FIR: kernel/D2H failed");
@@ -326,7 +360,8 @@ simd_hb_decim2_real(const float* in, int in_len, float* out, float* hist, const 
         (void)hipMemcpy(ds.p, scratch.data(), scratch.size() * sizeof(float), hipMemcpyHostToDevice);
         (void)hipMemcpy(dt.p, taps, (size_t)taps_len * sizeof(float), hipMemcpyHostToDevice);
         hipLaunchKernelGGL((k_sym_fir_single<float>), dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, 0,
-                           (const float*)ds.p, (const float*)dt.p, taps_len, n_out, 2, 2, fused, (float*)dout.p);
+                           (const float*)ds.p, (const float*)dt.p, taps_len, n_out, 2, 2, fused, 0, n_out & ~7,
+                           (float*)dout.p); // eight outputs per vector step (simd_fir_avx2.cpp:556-604)
         if (hipGetLastError() != hipSuccess
             || hipMemcpy(out, dout.p, (size_t)n_out * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
             ddn_set_error("drop-in HB: kernel/D2H failed");

@@ -5,6 +5,10 @@
 // simd_fir_avx2.cpp): output m of a block is the symmetric FIR centred on input 2m, the window reads the previous
 // samples of the stream on the left (the carried hist_i/hist_q) and REPLICATES THE BLOCK'S LAST SAMPLE on the right;
 // blocks shorter than taps_len complex samples take the scalar unit's (mul, add) order, longer ones the FMA order.
+// (The AVX2 unit leaves the first and last few outputs of a block to a scalar helper that starts from the plain centre product
+// instead of an FMA onto +0.0; that changes only the sign of an output that is exactly zero.  The single-stream drop-in follows it,
+// ddn_dropin.hip; this kernel does not: its zero goes on into the next stage's and the channel filter's sums, where the sign of one
+// zero term is lost unless every other term of the window is a zero of the matching sign as well.)
 //
 // Unlike the discriminator this stage has no recurrence: every output depends only on the input stream, the block
 // partition and the carried history, so it is one thread per output, channel-major coalesced loads (the window of a

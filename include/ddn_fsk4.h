@@ -88,6 +88,9 @@ typedef struct ddn_fsk4_rx ddn_fsk4_rx;
 
 int ddn_fsk4_rx_create(const ddn_fsk4_rx_config* cfg, ddn_fsk4_rx** out);
 void ddn_fsk4_rx_destroy(ddn_fsk4_rx* b);
+/* a fresh stream for every channel (waits for the device first).  Configuration made through setters before the reset survives
+ * it; state does not: ddn_fsk4_rx_set_lock_symbols, the handlers, channels per wave and the armed event buffers stay; timing,
+ * slicer words, histories and the handlers' words (DMR colour code 16, confidence cleared) start afresh. */
 int ddn_fsk4_rx_reset(ddn_fsk4_rx* b);
 /* enable != 0: the reference's own handlers decide how long a frame is read in frame (plain -fs / -fi, inverted = 0), inside the
  * loop - lock_symbols[] then only serves the sync types without a restated handler (DMR MS / direct mode words):

@@ -91,7 +91,8 @@ typedef struct ddn_batch ddn_batch;
 
 int ddn_batch_create(const ddn_front_end_config* cfg, ddn_batch** out);
 void ddn_batch_destroy(ddn_batch* b);
-/* forget all carried per-channel state (FIR history, modem dc/peak/prev): a fresh stream */
+/* forget all carried per-channel state (FIR and half-band history, IQ conditioning, modem dc/peak/prev, the audio monitor's
+ * words): a fresh stream, queued on hip_stream.  Configuration made through setters before the reset survives it; state does not. */
 int ddn_batch_reset(ddn_batch* b, void* hip_stream);
 /* taps actually in use (host-designed, same rule as channel_lpf_ensure_plan); returns taps_len */
 int ddn_batch_get_taps(const ddn_batch* b, float* taps_out, int cap);
@@ -210,6 +211,8 @@ int ddn_fm_audio_plan(const ddn_fm_audio_config* cfg, int passes, int block_len,
 typedef struct ddn_slicer_batch ddn_slicer_batch;
 int ddn_slicer_batch_create(int n_channels, int negative_polarity, ddn_slicer_batch** out);
 void ddn_slicer_batch_destroy(ddn_slicer_batch* b);
+/* a fresh stream: slicer words, window, rings and the matched filter's history back at their reset values.  Configuration
+ * made through setters before the reset survives it; state does not (the polarity given at create stays). */
 int ddn_slicer_batch_reset(ddn_slicer_batch* b);
 int ddn_p25_slicer_run(ddn_slicer_batch* b, const float* d_symbols, size_t n, uint8_t* d_records10, void* hip_stream);
 int ddn_p25_slicer_run_host(ddn_slicer_batch* b, const float* symbols, size_t n, uint8_t* records10);
@@ -252,6 +255,9 @@ typedef struct ddn_p25_rx_config {
 typedef struct ddn_p25_rx ddn_p25_rx;
 int ddn_p25_rx_create(const ddn_p25_rx_config* cfg, ddn_p25_rx** out);
 void ddn_p25_rx_destroy(ddn_p25_rx* b);
+/* a fresh stream for every channel (waits for the device first).  Configuration made through setters before the reset survives
+ * it; state does not: the per-channel lengths of ddn_p25_rx_set_lock_symbols, the handlers, channels per wave, the filter
+ * placement and the armed event buffers stay; timing, slicer words, rings, histories and the handlers' words start afresh. */
 int ddn_p25_rx_reset(ddn_p25_rx* b);
 /* in-frame symbol count after a sync, per channel (host array [n_channels]; NULL = cfg.lock_symbols everywhere): lets one
  * batch mix traffic classes, e.g. 840 for voice channels (LDUs) and 156 / 336 for one- / three-block TSDU control channels */
@@ -314,6 +320,8 @@ int ddn_p25_rx_debug_counters(ddn_p25_rx* b, int channel, long long out2[2]);
 typedef struct ddn_ted_batch ddn_ted_batch;
 int ddn_ted_batch_create(int n_channels, int sps, int symbol_rate_hz, float ted_gain, ddn_ted_batch** out);
 void ddn_ted_batch_destroy(ddn_ted_batch* b);
+/* a fresh stream, queued on hip_stream.  Configuration made through setters before the reset survives it; state does not
+ * (ddn_ted_batch_set_block_len stays; the loop words and the delay line are cleared). */
 int ddn_ted_batch_reset(ddn_ted_batch* b, void* hip_stream);
 /* One ddn_gardner_run() call == one op25_gardner_cc() call by default.  With block_len > 0 the call is equivalent to
  * ceil(n / block_len) consecutive op25_gardner_cc() calls of block_len samples (the last one shorter): the loop gain is
@@ -559,7 +567,9 @@ int ddn_p25p1_framer_voice_index(ddn_p25p1_framer* f, const int32_t* d_nid4, con
 typedef struct ddn_resampler ddn_resampler;
 int ddn_resampler_create(int n_channels, int L, int M, ddn_resampler** out); /* 1 <= L <= 512, 1 <= M <= 2^22 */
 void ddn_resampler_destroy(ddn_resampler* b);
-int ddn_resampler_reset(ddn_resampler* b, void* hip_stream);                 /* == dsd_resampler_clear_history */
+/* == dsd_resampler_clear_history: polyphase index 0, history cleared (queued on hip_stream).  Configuration survives the reset
+ * (L, M and the taps); state does not. */
+int ddn_resampler_reset(ddn_resampler* b, void* hip_stream);
 size_t ddn_resampler_out_len(const ddn_resampler* b, size_t n);              /* outputs the next run of n inputs gives */
 int ddn_resampler_get_taps(const ddn_resampler* b, float* taps, int cap);    /* [L][16], oldest tap first; returns 16 L */
 int ddn_resampler_run(ddn_resampler* b, const float* d_in, size_t n, float* d_out, size_t out_stride, void* hip_stream);
@@ -598,6 +608,8 @@ typedef struct ddn_cqpsk_config {
 typedef struct ddn_cqpsk_batch ddn_cqpsk_batch;
 int ddn_cqpsk_batch_create(const ddn_cqpsk_config* cfg, ddn_cqpsk_batch** out);
 void ddn_cqpsk_batch_destroy(ddn_cqpsk_batch* b);
+/* a fresh stream, queued on hip_stream (a run queued on the same stream afterwards needs no host synchronisation).  Configuration
+ * survives the reset; state does not: filter history, AGC, FLL, Costas loop and the Gardner stage all start afresh. */
 int ddn_cqpsk_batch_reset(ddn_cqpsk_batch* b, void* hip_stream);
 size_t ddn_cqpsk_max_symbols(const ddn_cqpsk_batch* b, size_t n);
 int ddn_cqpsk_run(ddn_cqpsk_batch* b, const void* d_iq, size_t n, float* d_symbols, size_t sym_stride,

@@ -151,6 +151,8 @@ typedef struct ddn_mbe_batch ddn_mbe_batch;
 /* S talk paths; every path's {cur, prev, prev_enhanced} starts as mbe_initMbeParms leaves it */
 int ddn_mbe_batch_create(int codec, int n_streams, ddn_mbe_batch** out);
 void ddn_mbe_batch_destroy(ddn_mbe_batch* b);
+/* every talk path back to what mbe_initMbeParms leaves, queued on hip_stream.  Configuration made through setters before the
+ * reset survives it; state does not: ddn_mbe_batch_set_first_stream, ddn_mbe_batch_set_p25p1_tail_rule and the loaded tables stay. */
 int ddn_mbe_batch_reset(ddn_mbe_batch* b, void* hip_stream);
 /* Path s of this batch is path first_stream + s of a larger set split over several batches (devices): its unvoiced-noise sequence is
  * that path's, so a partition of the paths does not show in the PCM.  Resets every path (call before the first frame). */

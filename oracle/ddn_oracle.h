@@ -40,11 +40,13 @@ int orc_channel_lpf_design(int rate_hz, int profile, float* taps_out, int max_ta
 int orc_firdes_low_pass_blackman(double gain, double fs, double cutoff, double transition, float* taps_out,
                                  int max_taps);
 
-/* fma_order=1: the reference's AVX2 unit (vector FMA chain); 0: the scalar/SSE2 unit (mul, then add). */
+/* fma_order=1: the reference's AVX2 unit (vector FMA chain); 0: the scalar/SSE2 unit (mul, then add).  In the half-band
+ * functions order 1 also follows which outputs that unit leaves to its scalar helpers (centre product first). */
 void orc_fir_complex_apply(const float* in, int in_len, float* out, float* hist_i, float* hist_q, const float* taps,
                            int taps_len, int fma_order);
 int orc_hb_decim2_complex(const float* in, int in_len, float* out, float* hist_i, float* hist_q, const float* taps,
                           int taps_len, int fma_order);
+int orc_hb_decim2_real(const float* in, int in_len, float* out, float* hist, const float* taps, int taps_len, int fma_order);
 extern const float orc_hb15_taps[15];
 extern const float orc_hb31_taps[31];
 

@@ -157,13 +157,22 @@ orc_update_hist(const float* in, int n, float* hi, float* hq, int hist_len) {
     }
 }
 
+/* a third accumulation order beside fma_order 0 and 1: the AVX2 unit's scalar helpers (src/dsp/simd_fir_avx2.cpp:143-160,
+ * 186-225, 310-319) begin with the plain product of the centre tap, not an FMA onto +0, and go on with `acc += ce * (...)`,
+ * which that unit's build (-mfma, contraction on) fuses.  It differs from order 1 only where every term is a zero: the product
+ * keeps a negative zero that fmaf(h, x, +0.0f) turns into +0. */
+#define ORC_ORDER_MUL_FIRST 2
+
 static inline void
 orc_sym_taps(const orc_iq_src* s, const float* taps, int center, int center_idx, int tap_step, int fma_order,
              float* oi, float* oq) {
     float ci, cq;
     orc_fetch(s, center_idx, &ci, &cq);
     float ai, aq;
-    if (fma_order) {
+    if (fma_order == ORC_ORDER_MUL_FIRST) {
+        ai = taps[center] * ci;
+        aq = taps[center] * cq;
+    } else if (fma_order) {
         ai = fmaf(taps[center], ci, 0.0f);
         aq = fmaf(taps[center], cq, 0.0f);
     } else {
@@ -206,8 +215,12 @@ orc_fir_complex_apply(const float* in, int in_len, float* out, float* hist_i, fl
     const int hist_len = taps_len - 1;
     const int center = hist_len >> 1;
     orc_iq_src s = {in, hist_i, hist_q, hist_len, n, in[2 * (n - 1)], in[2 * (n - 1) + 1]};
+    /* the AVX2 unit takes eight, then four outputs per step and leaves the last n % 4 to its scalar helper
+     * (src/dsp/simd_fir_avx2.cpp:425-446) */
+    const int vec_end = n & ~3;
     for (int i = 0; i < n; i++) {
-        orc_sym_taps(&s, taps, center, hist_len + i, 1, fma_order, &out[2 * i], &out[2 * i + 1]);
+        const int order = !fma_order ? 0 : (i < vec_end ? 1 : ORC_ORDER_MUL_FIRST);
+        orc_sym_taps(&s, taps, center, hist_len + i, 1, order, &out[2 * i], &out[2 * i + 1]);
     }
     orc_update_hist(in, n, hist_i, hist_q, hist_len);
 }
@@ -222,6 +235,31 @@ const float orc_hb31_taps[31] = {
     0.0f, 1314.0f / 32768.0f, 0.0f, -2953.0f / 32768.0f, 0.0f, 10244.0f / 32768.0f, 16386.0f / 32768.0f,
     10244.0f / 32768.0f, 0.0f, -2953.0f / 32768.0f, 0.0f, 1314.0f / 32768.0f, 0.0f, -587.0f / 32768.0f, 0.0f,
     233.0f / 32768.0f, 0.0f, -73.0f / 32768.0f, 0.0f, 13.0f / 32768.0f, 0.0f, 0.0f};
+
+/* Which outputs of a block of n complex samples the AVX2 unit computes in its vector loop, [*begin, *end); the others go
+ * through its scalar helpers, which start from the plain centre product (ORC_ORDER_MUL_FIRST).
+ *   15 and 31 taps (src/dsp/simd_fir_avx2.cpp:348-390): the outputs whose window reaches the history (2 * i < centre)
+ *   come first, then eight per step while i + 7 < n_out and 2 * i + centre + 15 < n, then the rest;
+ *   other lengths (:499-511): four per step from output 0, then the last n_out % 4. */
+static void
+orc_hb_complex_vector_span(int n, int taps_len, int* begin, int* end) {
+    const int n_out = n >> 1;
+    if (taps_len == 15 || taps_len == 31) {
+        const int center = (taps_len - 1) >> 1;
+        int i = 0;
+        while (i < n_out && (i << 1) < center) {
+            i++;
+        }
+        *begin = i;
+        while (i + 7 < n_out && (i << 1) + center + 15 < n) {
+            i += 8;
+        }
+        *end = i;
+    } else {
+        *begin = 0;
+        *end = n_out & ~3;
+    }
+}
 
 int
 orc_hb_decim2_complex(const float* in, int in_len, float* out, float* hist_i, float* hist_q, const float* taps,
@@ -240,11 +278,70 @@ orc_hb_decim2_complex(const float* in, int in_len, float* out, float* hist_i, fl
     const int hist_len = taps_len - 1;
     const int center = hist_len >> 1;
     orc_iq_src s = {in, hist_i, hist_q, hist_len, n, in[in_len - 2], in[in_len - 1]};
+    int vec_begin = 0, vec_end = 0;
+    if (fma_order) {
+        orc_hb_complex_vector_span(n, taps_len, &vec_begin, &vec_end);
+    }
     for (int i = 0; i < n_out; i++) {
-        orc_sym_taps(&s, taps, center, hist_len + 2 * i, 2, fma_order, &out[2 * i], &out[2 * i + 1]);
+        const int order = !fma_order ? 0 : (i >= vec_begin && i < vec_end) ? 1 : ORC_ORDER_MUL_FIRST;
+        orc_sym_taps(&s, taps, center, hist_len + 2 * i, 2, order, &out[2 * i], &out[2 * i + 1]);
     }
     orc_update_hist(in, n, hist_i, hist_q, hist_len);
     return n_out << 1;
+}
+
+/* real half-band /2: src/dsp/simd_fir.cpp:229-283 (scalar unit), :303-305 and :376-384 (a block with
+ * in_len < 2 * taps_len takes the scalar unit), src/dsp/simd_fir_avx2.cpp:524-610 (AVX2 unit: eight outputs per step in
+ * the FMA-onto-zero order, then the last out_len % 8 outputs through :212-225, centre product first). */
+int
+orc_hb_decim2_real(const float* in, int in_len, float* out, float* hist, const float* taps, int taps_len, int fma_order) {
+    if (taps_len < 3 || (taps_len & 1) == 0 || in_len <= 0) {
+        return 0;
+    }
+    if (in_len < taps_len * 2) {
+        fma_order = 0;
+    }
+    const int hist_len = taps_len - 1;
+    const int center = hist_len >> 1;
+    const int n_out = in_len >> 1;
+    const int vec_end = n_out & ~7;
+    const float last = in[in_len - 1];
+    for (int i = 0; i < n_out; i++) {
+        const int ci = hist_len + 2 * i;
+#define ORC_REAL_AT(idx) ((idx) < hist_len ? hist[(idx)] : ((idx) - hist_len < in_len ? in[(idx) - hist_len] : last))
+        const float c = ORC_REAL_AT(ci);
+        float acc;
+        if (!fma_order) {
+            acc = 0.0f + taps[center] * c;
+        } else if (i < vec_end) {
+            acc = fmaf(taps[center], c, 0.0f);
+        } else {
+            acc = taps[center] * c;
+        }
+        for (int k = 0; k < center; k += 2) {
+            const float h = taps[k];
+            if (h == 0.0f) {
+                continue;
+            }
+            const int d = center - k;
+            const float sm = ORC_REAL_AT(ci - d) + ORC_REAL_AT(ci + d);
+            if (fma_order) {
+                acc = fmaf(h, sm, acc);
+            } else {
+                acc += h * sm;
+            }
+        }
+#undef ORC_REAL_AT
+        out[i] = acc;
+    }
+    if (in_len >= hist_len) {
+        memcpy(hist, in + (in_len - hist_len), (size_t)hist_len * sizeof(float));
+    } else {
+        const int keep = hist_len - in_len;
+        memmove(hist, hist + in_len, (size_t)keep * sizeof(float));
+        memcpy(hist + keep, in, (size_t)in_len * sizeof(float));
+    }
+    return n_out;
 }
 
 /* DC-corrected mean power, double accumulation, src/dsp/demod_pipeline.cpp:926-945 */

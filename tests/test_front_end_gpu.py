@@ -234,17 +234,24 @@ def test_dropin_symbols_match_oracle(built):
     ph = np.cumsum(rng.normal(0.0, 0.15, n))
     iq = np.stack([np.cos(ph), np.sin(ph)], axis=1).astype(np.float32)
     st = ddn.FskModemState(48000, 4800, 4, 4, 0, 0, 0, 0, 0)
+    st3 = ddn.FskModemState(48000, 4800, 4, 4, 0, 0, 0, 0, 0)      # the same stream through the reference-named twin
     ost = np.zeros(5, np.float32)
     d1 = np.zeros(n, np.float32)
     d2 = np.zeros(n, np.float32)
+    d3 = np.zeros(n, np.float32)
     for a, bnd in ((0, 1000), (1000, n)):
         c1 = l.ddn_fsk_modem_discriminator_process(C.byref(st), iq[a:bnd].ctypes.data, 2 * (bnd - a),
                                                    d1[a:].ctypes.data, bnd - a)
         c2 = o.orc_fsk_discriminator(ost.ctypes.data, iq[a:bnd].ctypes.data, 2 * (bnd - a), d2[a:].ctypes.data,
                                      bnd - a)
-        assert c1 == c2 == bnd - a
+        c3 = l.dsd_fsk_modem_discriminator_process(C.addressof(st3), iq[a:bnd].ctypes.data, 2 * (bnd - a),
+                                                   d3[a:].ctypes.data, bnd - a)
+        assert c1 == c2 == c3 == bnd - a
+        assert bytes(st) == bytes(st3)                   # the whole carried state after every block
     check(d1, d2, exact=True)
+    check(d3, d1, exact=True)
     assert st.dc_est == ost[3] and st.discriminator_peak_est == ost[4]
+    assert st3.have_prev == 1 and l.dsd_fsk_modem_discriminator_process(None, iq.ctypes.data, 2 * n, d3.ctypes.data, n) == 0
 
 
 def test_full_size_c2_properties(built):
