@@ -637,6 +637,35 @@ PROTOTYPES.update({
 })
 
 
+class NxdnCtrlInput(C.Structure):  # == ddn_nxdn_ctrl_input
+    _fields_ = [("n_channels", C.c_int), ("max_symbols", C.c_size_t), ("max_syncs", C.c_size_t)] + [
+        (k, C.c_void_p) for k in ("d_records10", "d_counts", "d_sync_pos", "d_n_sync", "d_lich", "d_valid", "d_sacch", "d_sacch_ok",
+                                  "d_sacch_hard", "d_sacch_hard_ok")]
+
+
+class NxdnCtrlFrames(C.Structure):  # == ddn_nxdn_ctrl_frames
+    _fields_ = [(k, C.c_void_p) for k in ("d_kind", "d_bits208", "d_bytes26", "d_crc_ok", "d_fallback", "d_ran", "d_sf")]
+
+
+class NxdnCtrlMessages(C.Structure):  # == ddn_nxdn_ctrl_messages
+    _fields_ = [(k, C.c_void_p) for k in ("d_sacch_status", "d_pf", "d_seq_ok", "d_msg72", "d_msg_status", "d_last_ran", "d_cac_fail")]
+
+
+class NxdnCtrlChainResults(C.Structure):  # == ddn_nxdn_ctrl_chain_results
+    _fields_ = [("max_syncs", C.c_size_t), ("d_n_sync", C.c_void_p), ("d_sync_pos", C.c_void_p), ("d_valid", C.c_void_p),
+                ("frames", NxdnCtrlFrames), ("messages", NxdnCtrlMessages)]
+
+
+PROTOTYPES.update({
+    "ddn_nxdn_ctrl_state_bytes": (C.c_size_t, []),
+    "ddn_nxdn_ctrl_state_init": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ddn_nxdn_ctrl_decode_batch": (C.c_int, [C.c_void_p] * 3),
+    "ddn_nxdn_ctrl_walk_batch": (C.c_int, [C.c_void_p] * 5),
+    "ddn_fsk4_chain_set_nxdn_ctrl": (C.c_int, [C.c_void_p, C.c_int]),
+    "ddn_fsk4_chain_get_nxdn_ctrl_results": (C.c_int, [C.c_void_p, C.c_void_p]),
+})
+
+
 def dpmr_air_interface_id(v):
     """ddn_dpmr_air_interface_id: the seven characters the reference prints for a raw 24-bit dPMR ID"""
     out = C.create_string_buffer(8)
@@ -788,6 +817,16 @@ class Fsk4ChainC:
     def set_dmr_pdu_slots(self, max_pdus):
         """ddn_fsk4_chain_set_dmr_pdu_slots: assemble data PDUs on the device, 1 .. 8 stored per channel and call; before the first run"""
         _check(lib().ddn_fsk4_chain_set_dmr_pdu_slots(self.h, max_pdus), "ddn_fsk4_chain_set_dmr_pdu_slots")
+
+    def nxdn_ctrl_results(self):
+        """ddn_fsk4_chain_get_nxdn_ctrl_results (NXDN chains after set_nxdn_ctrl): CAC / FACCH2 / UDCH frames and the SACCH walk of the last call"""
+        r = NxdnCtrlChainResults()
+        _check(lib().ddn_fsk4_chain_get_nxdn_ctrl_results(self.h, C.byref(r)), "ddn_fsk4_chain_get_nxdn_ctrl_results")
+        return r
+
+    def set_nxdn_ctrl(self, enable=1):
+        """ddn_fsk4_chain_set_nxdn_ctrl: decode CAC / FACCH2 / UDCH frames and assemble SACCH superframes on the device; before the first run"""
+        _check(lib().ddn_fsk4_chain_set_nxdn_ctrl(self.h, enable), "ddn_fsk4_chain_set_nxdn_ctrl")
 
     @property
     def rx(self):

@@ -375,6 +375,41 @@ nxdn_alloc(ddn_fsk4_chain* c) {
     return voice_tail_alloc(c, V * 4, c->B);
 }
 
+// CAC / FACCH2 / UDCH frames and the SACCH walk (ddn_fsk4_chain_set_nxdn_ctrl): the buffers of the feature, made when it is
+// enabled; the state block starts as ddn_nxdn_ctrl_state_init leaves it
+static int
+nxdn_ctrl_alloc(ddn_fsk4_chain* c) {
+    const size_t B = (size_t)c->B, S = c->S;
+    DDN_TRY(alloc_rc(BUF(nxdn.ctrl.state, B * ddn_nxdn_ctrl_state_bytes()) && BUF(nxdn.ctrl.kind, S) && BUF(nxdn.ctrl.bits, S * 208)
+                       && BUF(nxdn.ctrl.bytes, S * 26) && BUF(nxdn.ctrl.crc, S) && BUF(nxdn.ctrl.fallback, S) && BUF(nxdn.ctrl.ran, S)
+                       && BUF(nxdn.ctrl.sf, S) && BUF(nxdn.ctrl.sacch_status, S) && BUF(nxdn.ctrl.pf, S) && BUF(nxdn.ctrl.seq, S)
+                       && BUF(nxdn.ctrl.msg, S * 72) && BUF(nxdn.ctrl.msg_status, S) && BUF(nxdn.ctrl.last_ran, S)
+                       && BUF(nxdn.ctrl.cac_fail, S)));
+    DDN_TRY(ddn_nxdn_ctrl_state_init(c->nxdn.ctrl.state, B, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return DDN_OK;
+}
+
+static void
+nxdn_ctrl_outputs(const ddn_fsk4_chain* c, ddn_nxdn_ctrl_frames* fr, ddn_nxdn_ctrl_messages* ms) {
+    const auto& p = c->nxdn.ctrl;
+    *fr = ddn_nxdn_ctrl_frames{p.kind, p.bits, p.bytes, p.crc, p.fallback, p.ran, p.sf};
+    *ms = ddn_nxdn_ctrl_messages{p.sacch_status, p.pf, p.seq, p.msg, p.msg_status, p.last_ran, p.cac_fail};
+}
+
+// (the records of this call's buffer set are written again by the loop of the call after the next, which waits for the whole of the
+// next decode stage: the gather may read them behind ev_reads; the sync list and the counts are the decode stage's own copies)
+static int
+nxdn_ctrl_stage(ddn_fsk4_chain* c, int cur, hipStream_t st) {
+    ddn_nxdn_ctrl_input in{c->B,           c->stride,          (size_t)c->myd,      c->d_rec[cur],        c->d_cnt_full, c->d_spos, c->d_ns, c->nxdn.lich,
+                           c->nxdn.valid, c->nxdn.sacch, c->nxdn.sacch_ok, c->nxdn.sacch_hard, c->nxdn.sacch_hard_ok};
+    ddn_nxdn_ctrl_frames fr;
+    ddn_nxdn_ctrl_messages ms;
+    nxdn_ctrl_outputs(c, &fr, &ms);
+    DDN_TRY(ddn_nxdn_ctrl_decode_batch(&in, &fr, st));
+    return ddn_nxdn_ctrl_walk_batch(&in, &fr, c->nxdn.ctrl.state, &ms, st);
+}
+
 // frame gather -> SACCH / FACCH1 K=5 soft decode -> CRC6 / CRC12 -> the reference's greedy retry for the SACCH
 static int
 nxdn_decode(ddn_fsk4_chain* c, int cur, int, hipStream_t st) {
@@ -405,6 +440,9 @@ nxdn_decode(ddn_fsk4_chain* c, int cur, int, hipStream_t st) {
         DDN_TRY(ddn_mbe_frame_decode_batch(DDN_MBE_AMBE_3600X2450, c->d_ambe_fr, c->d_ambe_rel, V4, c->d_ambe_d, c->d_ambe_res, st));
         DDN_TRY(ddn_mbe_result_skip_batch(c->d_skip, V4, c->d_ambe_res, st));
         DDN_TRY(ddn_mbe_synth_batch(c->mbe, c->d_ambe_d, c->d_ambe_res, (size_t)c->nxdn.vf * 4, c->d_pcm, c->d_res_out, st));
+    }
+    if (c->nxdn.ctrl.on) {
+        DDN_TRY(nxdn_ctrl_stage(c, cur, st));
     }
     return DDN_OK;
 }
@@ -867,6 +905,35 @@ ddn_fsk4_chain_get_dmr_pdu_results(ddn_fsk4_chain* c, ddn_dmr_pdu_chain_results*
     r->d_n_losses = c->dmr.pw.nl;
     r->d_loss_before = c->dmr.pw.lb;
     dmr_pdu_output(c, &r->out);
+    return DDN_OK;
+}
+
+extern "C" int
+ddn_fsk4_chain_set_nxdn_ctrl(ddn_fsk4_chain* c, int enable) {
+    if (!c || (c->cfg.protocol != DDN_FSK4_NXDN48 && c->cfg.protocol != DDN_FSK4_NXDN96) || !c->cfg.handlers || c->step != 0
+        || (enable != 0 && enable != 1)) {
+        ddn_set_error("ddn_fsk4_chain_set_nxdn_ctrl: an NXDN48 / NXDN96 chain with handlers = 1 before its first run, enable 0 / 1");
+        return DDN_EINVAL;
+    }
+    if (enable && !c->nxdn.ctrl.state) {
+        DDN_TRY(nxdn_ctrl_alloc(c));
+    }
+    c->nxdn.ctrl.on = enable;
+    return DDN_OK;
+}
+
+extern "C" int
+ddn_fsk4_chain_get_nxdn_ctrl_results(ddn_fsk4_chain* c, ddn_nxdn_ctrl_chain_results* r) {
+    if (!c || !r || (c->cfg.protocol != DDN_FSK4_NXDN48 && c->cfg.protocol != DDN_FSK4_NXDN96) || !c->nxdn.ctrl.on) {
+        ddn_set_error("ddn_fsk4_chain_get_nxdn_ctrl_results: an NXDN48 / NXDN96 chain with ddn_fsk4_chain_set_nxdn_ctrl enabled");
+        return DDN_EINVAL;
+    }
+    memset(r, 0, sizeof(*r));
+    r->max_syncs = (size_t)c->myd;
+    r->d_n_sync = c->d_ns;
+    r->d_sync_pos = c->d_spos;
+    r->d_valid = c->nxdn.valid;
+    nxdn_ctrl_outputs(c, &r->frames, &r->messages);
     return DDN_OK;
 }
 

@@ -77,6 +77,13 @@ struct ddn_fsk4_chain {
         int vf;
         uint8_t *lich, *valid, *ss, *sr, *fs, *fr, *sacch, *sacch_ok, *hard_in, *sacch_hard, *sacch_hard_ok, *facch, *facch_ok;
         int32_t* vpos;
+        // CAC / FACCH2 / UDCH frames and the SACCH walk (ddn_nxdn_ctrl.hip), off until ddn_fsk4_chain_set_nxdn_ctrl: nothing allocated,
+        // nothing launched.  The state carried per channel, the outputs per sync slot
+        struct {
+            int on;
+            uint8_t *state, *kind, *bits, *bytes, *crc, *fallback, *ran, *sf, *sacch_status, *pf, *seq, *msg, *msg_status;
+            int32_t *last_ran, *cac_fail;
+        } ctrl;
     } nxdn;
     struct { // M17: the frame decoders' slot arrays (ddn_m17_*_batch), the carried LICH assembly buffer
         uint8_t *lsf, *lsf_st, *l6, *cnt, *fp, *st, *assembly, *ll, *ll_st;

@@ -40,6 +40,12 @@ constexpr Code P25_CRC12{12, 0x897u, 0u, 0xFFFu, false};
 // x^6 + x^5 + x^2 + x + 1 (nxdn_deperm.c:1246-1261) and x^12 + x^11 + x^3 + x^2 + x + 1 (crc12f, nxdn_dcr_utils.c:21-42)
 constexpr Code NXDN_CRC6{6, 0x27u, 0x3Fu, 0u, false};
 constexpr Code NXDN_CRC12F{12, 0x80Fu, 0xFFFu, 0u, false};
+// x^15 + x^14 + x^11 + x^10 + x^7 + x^6 + x^2 + 1: crc15() of FACCH2 / UDCH (nxdn_dcr_utils.c:44-69)
+constexpr Code NXDN_CRC15{15, 0x4CC5u, 0x7FFFu, 0u, false};
+// crc16cac() (nxdn_deperm.c:1263-1275) divides message + field by x^16 + x^12 + x^5 + 1 from a register of 0xC3EE and inverts: as
+// with ysf_crc16() the division leaves crc(message) ^ field, so a good CAC (remainder 0) carries crc(message) in its field.  The
+// division's register runs sixteen bits ahead of this form's: the start value is 0xC3EE shifted through sixteen zeros (check, below)
+constexpr Code NXDN_CRC16CAC{16, 0x1021u, 0x5FE7u, 0xFFFFu, false};
 // x^7 + x^3 + 1: dpmr_crc7()
 constexpr Code DPMR_CRC7{7, 0x09u, 0u, 0u, false};
 // CRC-16/X25: dstar_crc16() (dstar_header_utils.c), which returns it byte-swapped - the frame carries the low byte first
@@ -213,6 +219,7 @@ static_assert(of_bytes(DSTAR_X25, digits, 9) == 0x906Eu, "CRC-16/X25");
 static_assert(of_bytes(CCITT16, digits, 9) == (0x31C3u ^ 0xFFFFu), "CRC-16/XMODEM, inverted");
 static_assert(of_bytes(CRC32, digits, 9) == 0x765E7680u, "CRC-32/CKSUM");
 static_assert(byte(CRC32, byte_table(CRC32), 0x12345678u, 0x9Au) == byte(CRC32, 0x12345678u, 0x9Au), "table form");
+static_assert(byte(NXDN_CRC16CAC, byte(NXDN_CRC16CAC, 0xC3EEu, 0u), 0u) == NXDN_CRC16CAC.init, "crc16cac's register, sixteen bits on");
 } // namespace check
 
 } // namespace ddn_crc

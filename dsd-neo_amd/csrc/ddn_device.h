@@ -436,6 +436,22 @@ hipError_t ddn_dev_dmr_emb_collect(const int32_t* events, const int32_t* n_event
                                    size_t max_sym, int n_channels, int max_lc, uint8_t* sig, uint8_t* in128, int32_t* lc_pos,
                                    int32_t* lc_n, hipStream_t st);
 hipError_t ddn_dev_dmr_emb_finish(const uint8_t* out77, const int32_t* lc_pos, int n, uint8_t* ok, hipStream_t st);
+// NXDN CAC / FACCH2 / UDCH frames and the SACCH superframe state (ddn_nxdn_ctrl.hip).  gather: kind and the two wanted flags of
+// every slot, the K = 5 decoders' rows of the wanted ones ([S][350] CAC, [S][406] FACCH2 / UDCH: symbols, reliabilities, hard bits);
+// finish: soft rows of stride 26, hard rows of stride 208, any output may be null
+size_t ddn_dev_nxdn_ctrl_state_bytes(void);
+hipError_t ddn_dev_nxdn_ctrl_state_init(void* state, int n_channels, hipStream_t st);
+hipError_t ddn_dev_nxdn_ctrl_gather(const uint8_t* rec, const int32_t* counts, size_t max_sym, const int32_t* sync_pos, const int32_t* n_sync,
+                                    int n_channels, int max_sync, uint8_t* kind, uint8_t* sym_c, uint8_t* rel_c, uint8_t* hard_c,
+                                    uint8_t* sym_f, uint8_t* rel_f, uint8_t* hard_f, uint8_t* want_c, uint8_t* want_f, hipStream_t st);
+hipError_t ddn_dev_nxdn_ctrl_finish(const uint8_t* kind, const uint8_t* soft_c, const uint8_t* soft_f, const uint8_t* hard_c,
+                                    const uint8_t* hard_f, size_t n, uint8_t* bits208, uint8_t* bytes26, uint8_t* crc_ok, uint8_t* fallback,
+                                    uint8_t* ran, uint8_t* sf, hipStream_t st);
+hipError_t ddn_dev_nxdn_ctrl_walk(const int32_t* n_sync, int n_channels, int max_sync, const uint8_t* lich, const uint8_t* valid,
+                                  const uint8_t* sacch, const uint8_t* sacch_ok, const uint8_t* sacch_hard, const uint8_t* sacch_hard_ok,
+                                  const uint8_t* kind, const uint8_t* crc_ok, const uint8_t* ran, const uint8_t* sf, void* state,
+                                  uint8_t* sacch_status, uint8_t* pf, uint8_t* seq_ok, uint8_t* msg72, uint8_t* msg_status, int32_t* last_ran,
+                                  int32_t* cac_fail, hipStream_t st);
 // the DMR protocol layer behind the data bursts: resets / carrier loss between them, the walk to completed PDUs (ddn_dmr_pdu.hip)
 size_t ddn_dev_dmr_pdu_state_bytes(void);
 hipError_t ddn_dev_dmr_pdu_marks(const int32_t* events, const int32_t* n_events, int max_events, const uint8_t* flags, size_t stride,

@@ -582,6 +582,25 @@ typedef struct ddn_dmr_pdu_chain_results { /* device pointers valid until the ne
 int ddn_fsk4_chain_set_dmr_pdu_slots(ddn_fsk4_chain* c, int max_pdus);
 int ddn_fsk4_chain_get_dmr_pdu_results(ddn_fsk4_chain* c, ddn_dmr_pdu_chain_results* out);
 
+/* ---- NXDN control and data channels (protocol DDN_FSK4_NXDN48 / _NXDN96, handlers = 1), opt-in: ddn_fsk4_chain_set_nxdn_ctrl(c, 1)
+ * before the first run; handlers = 0, a chain that has run or another protocol is DDN_EINVAL.  Until it is called the chain
+ * launches nothing and allocates nothing for it, and ddn_fsk4_chain_get_nxdn_ctrl_results is DDN_EINVAL.  Enabled, every call runs
+ * ddn_nxdn_ctrl_decode_batch -> ddn_nxdn_ctrl_walk_batch (include/ddn_fsk4.h: kinds, status bytes, the cac_fail deviation) behind the
+ * SACCH / FACCH1 decodes, over the slots ddn_fsk4_chain_results names: entry c * max_syncs + k here is the same frame as there.
+ * part_of_frame, the segment store with its CRC flags, the last RAN and cac_fail are carried per channel across calls and through
+ * flush (set when the feature is enabled), so a superframe whose segments lie in different calls is delivered once, in the call that
+ * decodes its last frame.  ddn_fsk4_chain_config and ddn_fsk4_chain_results keep their sizes. */
+typedef struct ddn_nxdn_ctrl_chain_results { /* device pointers valid until the next run */
+    size_t max_syncs;           /* slots per channel (= ddn_fsk4_chain_results.max_syncs) */
+    const int32_t* d_n_sync;    /* [n_channels] */
+    const int32_t* d_sync_pos;  /* [S] */
+    const uint8_t* d_valid;     /* [S] */
+    ddn_nxdn_ctrl_frames frames;     /* per slot: CAC / FACCH2 / UDCH */
+    ddn_nxdn_ctrl_messages messages; /* per slot: the SACCH walk */
+} ddn_nxdn_ctrl_chain_results;
+int ddn_fsk4_chain_set_nxdn_ctrl(ddn_fsk4_chain* c, int enable);
+int ddn_fsk4_chain_get_nxdn_ctrl_results(ddn_fsk4_chain* c, ddn_nxdn_ctrl_chain_results* out);
+
 /* ---- a mixed batch (BASELINE configs[3]): P25 Phase 1 + DMR + NXDN48 channel groups of one GPU, every receive loop with the
  * reference's handlers inside it; one stream per group inside the object, the groups' stages lined up (the three front ends, then the
  * three receive loops side by side), the frame FEC / voice stages on a fourth stream behind their loops so that the next call's

@@ -461,6 +461,80 @@ int ddn_dmr_pdu_marks_batch(const int32_t* d_events, const int32_t* d_n_events, 
                             size_t stride_symbols, int carry_symbols, const int32_t* d_new, const int32_t* d_burst_start,
                             const int32_t* d_n_bursts, int n_channels, int max_bursts, void* d_state, int32_t* d_reset_before,
                             int32_t* d_n_resets, int32_t* d_loss_before, int32_t* d_n_losses, int max_marks, void* hip_stream);
+
+/* ---- NXDN control and data channels: CAC, FACCH2 / UDCH and the SACCH superframe (ddn_nxdn_ctrl.hip) -----------------------------
+ * What nxdn_frame() does with a frame whose LICH names no SACCH / FACCH1 pair, and the state it keeps between frames
+ * (src/protocol/nxdn/nxdn_frame.c:117-160,237-263,311-346,488-494; nxdn_deperm.c:164-205,245-340,496-530,610-634,1263-1372;
+ * nxdn_dcr_utils.c:44-106; nxdn_element.c:158-200).  Sync slots as ddn_nxdn_frame_gather has them: slot c * max_syncs + k, S =
+ * n_channels * max_syncs.
+ *
+ * ddn_nxdn_ctrl_decode_batch: per slot the LICH is read again from the records (parity, then profile) and the frame classed:
+ *   kind 0 none (no whole frame, gate closed, or a channel left to the caller: SACCH / FACCH1 frames, SCCH, FACCH3 / UDCH2, SACCH2,
+ *   PICH / TCH)   1 CAC (LICH 0x01, 0x05; bits 16..315)   2 FACCH2 (0x28, 0x29, 0x49; bits 16..363)   3 UDCH (0x2E, 0x2F, 0x4E, 0x4F)
+ * Kinds 1..3: de-permutation, 12-in-14 de-puncture, CNXDNConvolution soft decode over 175 / 203 steps with 171 / 199 bits chained
+ * back, crc16cac over the 171 bits = 0 / crc15 over bits 0..183 against bits 184..198; where that fails trellis_decode() over the
+ * de-punctured hard bits is taken instead, whatever its CRC says (d_fallback = 1), and d_crc_ok is that result's verdict.
+ * d_bits208 = the reference's trellis_buf (one bit per byte, zeros behind 171 / 199), d_bytes26 = its m_data (22 / 26 bytes, zeros
+ * behind), d_ran = bits 2..7, d_sf = bits 0..1.  d_kind is written for every slot; the other rows of a kind-0 slot stay as they
+ * were.  Only the two decoder launches' wanted slots are decoded: a batch without control frames pays for the LICH reads.
+ *
+ * ddn_nxdn_ctrl_walk_batch: one channel's slots in air order through the state of d_state (n_channels x
+ * ddn_nxdn_ctrl_state_bytes(); all zeros is NOT a start: ddn_nxdn_ctrl_state_init sets part_of_frame 0, the segment store and its
+ * CRC flags all 1, last RAN none, cac_fail 0).  A slot that is not d_valid is passed over.  Per frame: a LICH with good parity that
+ * misses the profile table resets the segment store (a parity failure does not); a SACCH frame takes the soft SACCH where d_sacch_ok,
+ * else the greedy retry, through nxdn_handle_sacch(); a FACCH2 / UDCH frame sets part_of_frame = 3 - SF and last RAN on a good CRC,
+ * part_of_frame = 0 on a bad one; a CAC sets last RAN on a good CRC and counts consecutive bad ones in cac_fail.  Per slot:
+ *   d_sacch_status  0 no SACCH in this frame, 1 segment stored with good CRC, 2 stored with bad CRC, 3 non-superframe good, 4 bad
+ *   d_pf            part_of_frame after the frame          d_seq_ok  the sequence rule held ("PF n/4", not "PF X/4"; "PF 1/1")
+ *   d_msg_status    0 none, 1 delivered (all four segment CRCs good; a good non-superframe SACCH), 2 completed but a segment was bad
+ *   d_msg72         written where d_msg_status != 0 or d_sacch_status is 3 / 4: the four 18-bit segments; a non-superframe SACCH's
+ *                   24 bits (message + CRC6) in the first 24, zeros behind
+ *   d_last_ran      after the frame, -1 = none             d_cac_fail  after the frame
+ * Deviation: above ten consecutive bad CACs the reference resets its symbolizer (thresholds, sample history, sync state) and the
+ * counter.  The device cannot hand a decode verdict back into a receive-loop pass that has already run, so the reset is NOT
+ * applied: the frame that would trigger it reports d_cac_fail = 11 and the carried counter starts again from 0.  A host that wants
+ * the reset has the object resets (ddn_fsk4_rx_reset).  Message parsing (NXDN_Elements_Content_decode), trunking, aliases and the
+ * cipher LFSR bookkeeping stay on the host.  A NULL output pointer means that array is not wanted (d_kind, and for the walk d_crc_ok,
+ * d_ran and d_sf, are inputs of the later stages and required). */
+typedef struct ddn_nxdn_ctrl_input {
+    int n_channels;
+    size_t max_symbols;              /* row length of d_records10 in symbols */
+    size_t max_syncs;
+    const uint8_t* d_records10;      /* [n_channels][max_symbols][10] */
+    const int32_t* d_counts;         /* [n_channels] records held per row */
+    const int32_t* d_sync_pos;       /* [S] */
+    const int32_t* d_n_sync;         /* [n_channels] */
+    /* the walk only: what ddn_nxdn_frame_gather and the SACCH decoders made of the same slots */
+    const uint8_t* d_lich;           /* [S] 7-bit LICH, bit 7 = parity good */
+    const uint8_t* d_valid;          /* [S] */
+    const uint8_t* d_sacch;          /* [S][4] soft decode, packed */
+    const uint8_t* d_sacch_ok;       /* [S] */
+    const uint8_t* d_sacch_hard;     /* [S][32] greedy retry, one bit per byte */
+    const uint8_t* d_sacch_hard_ok;  /* [S] */
+} ddn_nxdn_ctrl_input;
+typedef struct ddn_nxdn_ctrl_frames {
+    uint8_t* d_kind;      /* [S] */
+    uint8_t* d_bits208;   /* [S][208] */
+    uint8_t* d_bytes26;   /* [S][26] */
+    uint8_t* d_crc_ok;    /* [S] */
+    uint8_t* d_fallback;  /* [S] */
+    uint8_t* d_ran;       /* [S] */
+    uint8_t* d_sf;        /* [S] */
+} ddn_nxdn_ctrl_frames;
+typedef struct ddn_nxdn_ctrl_messages {
+    uint8_t* d_sacch_status; /* [S] */
+    uint8_t* d_pf;           /* [S] */
+    uint8_t* d_seq_ok;       /* [S] */
+    uint8_t* d_msg72;        /* [S][72] */
+    uint8_t* d_msg_status;   /* [S] */
+    int32_t* d_last_ran;     /* [S] */
+    int32_t* d_cac_fail;     /* [S] */
+} ddn_nxdn_ctrl_messages;
+size_t ddn_nxdn_ctrl_state_bytes(void);
+int ddn_nxdn_ctrl_state_init(void* d_state, size_t n_channels, void* hip_stream);
+int ddn_nxdn_ctrl_decode_batch(const ddn_nxdn_ctrl_input* in, const ddn_nxdn_ctrl_frames* out, void* hip_stream);
+int ddn_nxdn_ctrl_walk_batch(const ddn_nxdn_ctrl_input* in, const ddn_nxdn_ctrl_frames* fr, void* d_state,
+                             const ddn_nxdn_ctrl_messages* out, void* hip_stream);
 #ifdef __cplusplus
 }
 #endif

@@ -6,11 +6,14 @@ front end, receive loop, framer gathers, BCH / trellis / CRC / Hamming / Reed-So
 
 A cu8, cf32 or cs16 capture goes to the device in its own format (the kernels widen it).
 
-usage: python tools/decode_capture.py CAPTURE.iq[.json] [--lock SYMBOLS] [--max-frames N] [--m17] [--analog OUT.wav]
+usage: python tools/decode_capture.py CAPTURE.iq[.json] [--lock SYMBOLS] [--max-frames N] [--m17] [--nxdn 48|96] [--analog OUT.wav]
        --lock: in-frame symbols after a sync (default 840 = LDU-sized; 156 / 336 suit one- / three-block TSDU control
                channels - dibits read outside the in-frame span carry no soft decisions)
        --m17:  read the capture as M17 (cu8 at 48 kHz) through the fsk4 chain object instead and print a line per completed packet:
                application length, CRC verdict, protocol identifier and, for SMS (0x05), the text
+       --nxdn 48|96: read the capture as NXDN48 / NXDN96 (cu8 at 48 kHz) through the fsk4 chain object with the control-channel stage on
+               and print a line per delivered SACCH message and per CAC / FACCH2 / UDCH frame: RAN, channel, message type, CRC; the
+               reference's NXDN48 capture prints its "VCALL ... Src=901" lines
        --analog OUT.wav: run the capture through the analog FM monitor instead (full_demod()'s audio output kind: de-emphasis 75 us,
                DC block, low_pass_real to 8 kHz where the demod rate is a multiple of it) and write the audio as 16-bit PCM at full
                scale pi - one phase step cannot exceed pi; the reference's consumer-side gains stay with the host"""
@@ -229,6 +232,76 @@ def decode_m17(path, out=print):
     return lines
 
 
+NXDN_KIND = {1: "CAC", 2: "FACCH2", 3: "UDCH"}
+
+
+def nxdn_message_line(channel, ran, bits, crc_ok):
+    """a line for one NXDN layer-3 message (bits = the message behind the 8 header bits): RAN, channel, message type (bits 2..7 of its
+    first byte), CRC; a VCALL (type 0x01) adds its source and destination"""
+    val = lambda a, b: int("".join(str(int(v)) for v in bits[a:b]), 2)
+    t = val(2, 8)
+    text = "RAN %02d %-6s type 0x%02X%s CRC %s" % (ran, channel, t, " VCALL" if t == 1 else "", "ok" if crc_ok else "ERR")
+    if t == 1 and crc_ok and len(bits) >= 56:
+        text += " Src=%d Dst=%d" % (val(24, 40), val(40, 56))
+    return text
+
+
+def decode_nxdn(path, which, out=print):
+    """the capture through ddn_fsk4_chain (NXDN48 / NXDN96, handlers = 1, ddn_fsk4_chain_set_nxdn_ctrl) in calls of one second + the
+    flush -> a line per delivered SACCH message and per CAC / FACCH2 / UDCH frame, from the library's own outputs"""
+    import numpy as np
+    import ddn
+    l = ddn.lib()
+    paths = (C.c_char_p * 1)(path.encode())
+    buf, n = C.c_void_p(), C.c_size_t()
+    info = (C.c_uint8 * 8192)()
+    rc = l.ddn_iq_load_batch(paths, 1, C.byref(buf), C.byref(n), info)
+    if rc != 0:
+        raise SystemExit("cannot open capture (%d): %s" % (rc, l.ddn_last_error().decode()))
+    fmt, rate, base_dec, _, demod_rate = np.frombuffer(bytes(info[:24]), np.uint32)[1:6]
+    if int(fmt) != 1 or int(demod_rate) != 48000 or int(base_dec) != 1:
+        raise SystemExit("--nxdn takes cu8 captures at 48 kHz (format %d, %d Hz, base_decimation %d)" % (fmt, demod_rate, base_dec))
+    host = np.ctypeslib.as_array(C.cast(buf, C.POINTER(C.c_uint8)), (n.value * 2,)).copy().reshape(1, -1, 2)
+    l.ddn_iq_free(buf)
+    per = 48000
+    calls = -(-host.shape[1] // per)
+    pad = np.full((1, calls * per, 2), 127, np.uint8)
+    pad[:, :host.shape[1]] = host
+    ch = ddn.Fsk4ChainC(1, per, ddn.FSK4_NXDN48 if which == 48 else ddn.FSK4_NXDN96, rf_mod=0 if which == 48 else 2, handlers=1, vocoder=0)
+    ch.set_nxdn_ctrl(1)
+    lines = []
+
+    def take():
+        d = ch.nxdn_ctrl_results()
+        S, f, m = int(d.max_syncs), d.frames, d.messages
+        u8 = lambda p, *sh: ch.fetch(p, np.uint8, (S,) + sh)
+        ns = min(int(ch.fetch(d.d_n_sync, np.int32, (1,))[0]), S)
+        kind, bits, ok, ran = u8(f.d_kind), u8(f.d_bits208, 208), u8(f.d_crc_ok), u8(f.d_ran)
+        mst, sst, msg, last = u8(m.d_msg_status), u8(m.d_sacch_status), u8(m.d_msg72, 72), ch.fetch(m.d_last_ran, np.int32, (S,))
+        valid = u8(d.d_valid)
+        for k in range(ns):
+            if not valid[k]:
+                continue
+            if kind[k]:
+                lines.append(nxdn_message_line(NXDN_KIND[int(kind[k])], int(ran[k]), bits[k, 8:155 if kind[k] == 1 else 184], int(ok[k])))
+            elif mst[k] == 1:
+                lines.append(nxdn_message_line("SACCH", int(last[k]), msg[k, :72 if sst[k] == 1 else 18], 1))
+
+    for k in range(calls):
+        part = np.ascontiguousarray(pad[:, k * per:(k + 1) * per])
+        p = C.c_void_p()
+        assert l.ddn_device_alloc(part.nbytes, C.byref(p)) == 0 and l.ddn_device_upload(p, part.ctypes.data, part.nbytes) == 0
+        ch.run(p)
+        take()
+        l.ddn_device_free(p)
+    ch.flush()
+    take()
+    ch.close()
+    for t in lines:
+        out(t)
+    return lines
+
+
 def decode_analog(path, wav, out=print):
     """the capture through ddn_fm_audio_run in calls of one second -> OUT.wav (ddn_wav_write_s16, full scale pi)"""
     import numpy as np
@@ -272,7 +345,11 @@ def main():
     ap.add_argument("--max-frames", type=int, default=64)
     ap.add_argument("--m17", action="store_true")
     ap.add_argument("--analog", metavar="OUT.wav")
+    ap.add_argument("--nxdn", type=int, choices=(48, 96))
     a = ap.parse_args()
+    if a.nxdn:
+        decode_nxdn(a.capture, a.nxdn)
+        return
     if a.analog:
         decode_analog(a.capture, a.analog)
         return
