@@ -656,6 +656,42 @@ class NxdnCtrlChainResults(C.Structure):  # == ddn_nxdn_ctrl_chain_results
                 ("frames", NxdnCtrlFrames), ("messages", NxdnCtrlMessages)]
 
 
+class DmrMsInput(C.Structure):  # == ddn_dmr_ms_input
+    _fields_ = [("n_channels", C.c_int), ("max_symbols", C.c_size_t), ("max_syncs", C.c_size_t)] + [
+        (k, C.c_void_p) for k in ("d_records10", "d_counts", "d_new", "d_sync_pos", "d_sync_pat", "d_n_sync", "d_pre", "d_pre_rel")]
+
+
+class DmrMsBursts(C.Structure):  # == ddn_dmr_ms_bursts
+    _fields_ = [("max_data", C.c_int), ("max_voice", C.c_int), ("max_lc", C.c_int)] + [
+        (k, C.c_void_p) for k in ("d_n_data", "d_data_start", "d_data_sync", "d_data_gate", "d_data_pat", "d_data_slot", "d_data_status", "d_data_cc",
+                                  "d_n_voice", "d_voice_start", "d_voice_pre", "d_voice_vc", "d_voice_tact_ok", "d_voice_emb_ok", "d_voice_emb_cc",
+                                  "d_voice_power", "d_voice_sync48", "d_n_lc", "d_lc_pos", "d_lc_in128", "d_cc", "d_dropped", "d_phase")]
+
+
+class DmrMsData(C.Structure):  # == ddn_dmr_ms_data
+    _fields_ = [(k, C.c_void_p) for k in ("d_type", "d_info196", "d_bits96", "d_bytes12", "d_errs", "d_crc", "d_r34_unconfirmed", "d_r34_confirmed",
+                                          "d_r34_confirmed_crc", "d_r34_pool", "d_r34_pool_n")]
+
+
+class DmrMsVoice(C.Structure):  # == ddn_dmr_ms_voice
+    _fields_ = [(k, C.c_void_p) for k in ("d_ambe_frames", "d_skip", "d_lc77", "d_lc_errs", "d_lc_ok", "d_ambe_bits", "d_ambe_result", "d_pcm")]
+
+
+class DmrMsChainResults(C.Structure):  # == ddn_dmr_ms_chain_results
+    _fields_ = [("max_syncs", C.c_size_t), ("bursts", DmrMsBursts), ("data", DmrMsData), ("voice", DmrMsVoice)]
+
+
+PROTOTYPES.update({
+    "ddn_dmr_ms_state_bytes": (C.c_size_t, []),
+    "ddn_dmr_ms_state_init": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ddn_dmr_ms_walk_batch": (C.c_int, [C.c_void_p] * 4),
+    "ddn_dmr_ms_data_batch": (C.c_int, [C.c_void_p] * 4),
+    "ddn_dmr_ms_voice_batch": (C.c_int, [C.c_void_p] * 5),
+    "ddn_fsk4_chain_set_dmr_ms": (C.c_int, [C.c_void_p, C.c_int]),
+    "ddn_fsk4_chain_get_dmr_ms_results": (C.c_int, [C.c_void_p, C.c_void_p]),
+})
+
+
 PROTOTYPES.update({
     "ddn_nxdn_ctrl_state_bytes": (C.c_size_t, []),
     "ddn_nxdn_ctrl_state_init": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -827,6 +863,16 @@ class Fsk4ChainC:
     def set_nxdn_ctrl(self, enable=1):
         """ddn_fsk4_chain_set_nxdn_ctrl: decode CAC / FACCH2 / UDCH frames and assemble SACCH superframes on the device; before the first run"""
         _check(lib().ddn_fsk4_chain_set_nxdn_ctrl(self.h, enable), "ddn_fsk4_chain_set_nxdn_ctrl")
+
+    def dmr_ms_results(self):
+        """ddn_fsk4_chain_get_dmr_ms_results (DMR chains after set_dmr_ms): MS / direct-mode data bursts, voice bursts and embedded LCs of the last call"""
+        r = DmrMsChainResults()
+        _check(lib().ddn_fsk4_chain_get_dmr_ms_results(self.h, C.byref(r)), "ddn_fsk4_chain_get_dmr_ms_results")
+        return r
+
+    def set_dmr_ms(self, enable=1):
+        """ddn_fsk4_chain_set_dmr_ms: decode the bursts behind the MS / direct-mode words on the device; before the first run"""
+        _check(lib().ddn_fsk4_chain_set_dmr_ms(self.h, enable), "ddn_fsk4_chain_set_dmr_ms")
 
     @property
     def rx(self):

@@ -298,10 +298,57 @@ dmr_pdu_walk(ddn_fsk4_chain* c, int cur, hipStream_t st) {
     return ddn_dmr_pdu_walk_batch(&in, p.state, &out, st);
 }
 
+// MS / direct-mode bursts (ddn_fsk4_chain_set_dmr_ms): the buffers of the feature, made when it is enabled.  Syncs lie at least 288
+// symbols apart behind a data word and 1728 behind a voice word, a unit's bursts 288: a call of ms new symbols ends ms / 288 + 2
+// bursts of either kind at most and ms / 1728 + 2 units
+static int
+dmr_ms_alloc(ddn_fsk4_chain* c) {
+    auto& p = c->dmr.ms;
+    const size_t B = (size_t)c->B;
+    p.b.max_data = p.b.max_voice = (int)(c->ms / 288 + 2);
+    p.b.max_lc = (int)(c->ms / 1728 + 2);
+    const size_t D = B * (size_t)p.b.max_data, V = B * (size_t)p.b.max_voice, L = B * (size_t)p.b.max_lc;
+    uint8_t* pool = nullptr;
+    DDN_TRY(alloc_rc(
+        BUF(dmr.ms.state, B * ddn_dmr_ms_state_bytes()) && BUF(dmr.ms.b.d_n_data, B) && BUF(dmr.ms.b.d_data_start, D) && BUF(dmr.ms.b.d_data_sync, D)
+        && BUF(dmr.ms.b.d_data_gate, D) && BUF(dmr.ms.b.d_data_pat, D) && BUF(dmr.ms.b.d_data_slot, D) && BUF(dmr.ms.b.d_data_status, D)
+        && BUF(dmr.ms.b.d_data_cc, D) && BUF(dmr.ms.b.d_n_voice, B) && BUF(dmr.ms.b.d_voice_start, V) && BUF(dmr.ms.b.d_voice_pre, V)
+        && BUF(dmr.ms.b.d_voice_vc, V) && BUF(dmr.ms.b.d_voice_tact_ok, V) && BUF(dmr.ms.b.d_voice_emb_ok, V) && BUF(dmr.ms.b.d_voice_emb_cc, V)
+        && BUF(dmr.ms.b.d_voice_power, V) && BUF(dmr.ms.b.d_voice_sync48, V * 48) && BUF(dmr.ms.b.d_n_lc, B) && BUF(dmr.ms.b.d_lc_pos, L)
+        && BUF(dmr.ms.b.d_lc_in128, L * 128) && BUF(dmr.ms.b.d_cc, B) && BUF(dmr.ms.b.d_dropped, B) && BUF(dmr.ms.b.d_phase, B)
+        && BUF(dmr.ms.d.d_type, D) && BUF(dmr.ms.d.d_info196, D * 196) && BUF(dmr.ms.d.d_bits96, D * 96) && BUF(dmr.ms.d.d_bytes12, D * 12)
+        && BUF(dmr.ms.d.d_errs, D) && BUF(dmr.ms.d.d_crc, D) && BUF(dmr.ms.d.d_r34_unconfirmed, D * 18) && BUF(dmr.ms.d.d_r34_confirmed, D * 18)
+        && BUF(dmr.ms.d.d_r34_confirmed_crc, D) && c->pool.alloc(&pool, D * 34 * 24) && BUF(dmr.ms.d.d_r34_pool_n, D)
+        && BUF(dmr.ms.v.d_ambe_frames, V * 3 * 96) && BUF(dmr.ms.v.d_skip, V * 3) && BUF(dmr.ms.v.d_lc77, L * 77) && BUF(dmr.ms.v.d_lc_errs, L)
+        && BUF(dmr.ms.v.d_lc_ok, L)));
+    p.d.d_r34_pool = pool;
+    if (c->cfg.vocoder) {
+        DDN_TRY(alloc_rc(BUF(dmr.ms.v.d_ambe_bits, V * 3 * 49) && BUF(dmr.ms.v.d_ambe_result, V * 3 * 5) && BUF(dmr.ms.v.d_pcm, V * 3 * 160)));
+        DDN_TRY(ddn_mbe_batch_create(DDN_MBE_AMBE_3600X2450, c->B, &p.mbe));
+    }
+    DDN_TRY(ddn_dmr_ms_state_init(p.state, B, nullptr));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return DDN_OK;
+}
+
+// (all of it ahead of ev_reads: the walk and both gathers read the records and the decode list's hand-overs)
+static int
+dmr_ms_stage(ddn_fsk4_chain* c, int cur, hipStream_t st) {
+    const auto& p = c->dmr.ms;
+    const ddn_dmr_ms_input in{c->B, c->stride, (size_t)c->myd, c->d_rec[cur], c->d_cnt_full, c->d_new[cur], c->d_spos, c->d_spat, c->d_ns, c->d_pre,
+                              c->d_prel};
+    DDN_TRY(ddn_dmr_ms_walk_batch(&in, p.state, &p.b, st));
+    DDN_TRY(ddn_dmr_ms_data_batch(&in, &p.b, &p.d, st));
+    return ddn_dmr_ms_voice_batch(&in, &p.b, &p.v, p.mbe, st);
+}
+
 static int
 dmr_decode(ddn_fsk4_chain* c, int cur, int flush, hipStream_t st) {
     const size_t S = c->S;
     const uint8_t* rec = c->d_rec[cur];
+    if (c->dmr.ms.on) {
+        DDN_TRY(dmr_ms_stage(c, cur, st));
+    }
     // burst gather -> slot type Golay(20,8) -> BPTC(196,96); an RC sync (pattern 8) carries no burst: its slot stays invalid
     HIP_TRY(ddn_dev_dmr_burst_gather(rec, c->d_cnt_full, c->stride, c->d_spos, c->d_spat, c->d_pre, c->d_ns, c->B, (int)c->myd,
                                      c->cfg.inverted, c->dmr.st, c->dmr.info, c->dmr.cach, c->dmr.valid, st));
@@ -487,6 +534,7 @@ ddn_fsk4_chain_destroy(ddn_fsk4_chain* c) {
     ddn_fsk4_rx_destroy(c->rx);
     ddn_mbe_batch_destroy(c->mbe);
     ddn_mbe_batch_destroy(c->ysf.mbe_i);
+    ddn_mbe_batch_destroy(c->dmr.ms.mbe);
     c->pool.release();
     delete c;
 }
@@ -934,6 +982,51 @@ ddn_fsk4_chain_get_nxdn_ctrl_results(ddn_fsk4_chain* c, ddn_nxdn_ctrl_chain_resu
     r->d_sync_pos = c->d_spos;
     r->d_valid = c->nxdn.valid;
     nxdn_ctrl_outputs(c, &r->frames, &r->messages);
+    return DDN_OK;
+}
+
+extern "C" int
+ddn_fsk4_chain_set_dmr_ms(ddn_fsk4_chain* c, int enable) {
+    if (!c || c->cfg.protocol != DDN_FSK4_DMR || !c->cfg.handlers || c->cfg.inverted != 0 || c->step != 0 || (enable != 0 && enable != 1)) {
+        ddn_set_error("ddn_fsk4_chain_set_dmr_ms: a DMR chain with handlers = 1 and inverted = 0 before its first run, enable 0 / 1");
+        return DDN_EINVAL;
+    }
+    if (enable && !c->dmr.ms.state) {
+        DDN_TRY(dmr_ms_alloc(c));
+    }
+    if (enable != c->dmr.ms.on) {
+        // what the loop holds behind an MS / direct-mode word: dmrMSData()'s and dmrMS()'s counts, or the row's defaults again (with the
+        // handlers on the counts serve no BS word)
+        const int* def = ddn_fsk4::kRow[DDN_FSK4_DMR].lock_symbols;
+        int32_t* lock = new (std::nothrow) int32_t[(size_t)c->B * 4];
+        if (!lock) {
+            return DDN_ENOMEM;
+        }
+        for (int i = 0; i < c->B; i++) {
+            lock[4 * i] = enable ? DDN_DMR_MS_LOCK_DATA : def[0];
+            lock[4 * i + 1] = enable ? DDN_DMR_MS_LOCK_VOICE : def[1];
+            lock[4 * i + 2] = def[2];
+            lock[4 * i + 3] = def[3];
+        }
+        const int rc = ddn_fsk4_rx_set_lock_symbols(c->rx, lock);
+        delete[] lock;
+        DDN_TRY(rc);
+    }
+    c->dmr.ms.on = enable;
+    return DDN_OK;
+}
+
+extern "C" int
+ddn_fsk4_chain_get_dmr_ms_results(ddn_fsk4_chain* c, ddn_dmr_ms_chain_results* r) {
+    if (!c || !r || c->cfg.protocol != DDN_FSK4_DMR || !c->dmr.ms.on) {
+        ddn_set_error("ddn_fsk4_chain_get_dmr_ms_results: a DMR chain with ddn_fsk4_chain_set_dmr_ms enabled");
+        return DDN_EINVAL;
+    }
+    memset(r, 0, sizeof(*r));
+    r->max_syncs = (size_t)c->myd;
+    r->bursts = c->dmr.ms.b;
+    r->data = c->dmr.ms.d;
+    r->voice = c->dmr.ms.v;
     return DDN_OK;
 }
 

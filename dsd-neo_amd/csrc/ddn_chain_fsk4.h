@@ -72,6 +72,16 @@ struct ddn_fsk4_chain {
             uint8_t *state, *b_conf, *b_crc, *b_dbsn, *b_status, *kind, *slot, *bytes, *crc4, *bcrc;
             int32_t *b_counter, *b_pick, *n_pdus, *burst, *len, *hdr, *rb, *nr, *lb, *nl;
         } pw;
+        // MS / direct-mode bursts (ddn_dmr_ms.hip), off until ddn_fsk4_chain_set_dmr_ms: nothing allocated, nothing launched.  The state
+        // carried per channel, the walk's lists and the decoders' outputs (include/ddn_fsk4.h), a vocoder batch of B talk paths
+        struct {
+            int on;
+            uint8_t* state;
+            ddn_dmr_ms_bursts b;
+            ddn_dmr_ms_data d;
+            ddn_dmr_ms_voice v;
+            ddn_mbe_batch* mbe;
+        } ms;
     } dmr;
     struct { // NXDN48 / NXDN96; vf: voice frames per channel and call
         int vf;

@@ -452,6 +452,31 @@ hipError_t ddn_dev_nxdn_ctrl_walk(const int32_t* n_sync, int n_channels, int max
                                   const uint8_t* kind, const uint8_t* crc_ok, const uint8_t* ran, const uint8_t* sf, void* state,
                                   uint8_t* sacch_status, uint8_t* pf, uint8_t* seq_ok, uint8_t* msg72, uint8_t* msg_status, int32_t* last_ran,
                                   int32_t* cac_fail, hipStream_t st);
+// DMR MS / direct-mode bursts (ddn_dmr_ms.hip).  walk: one lane per channel, every array required; gathers: one workgroup per burst
+// slot, a slot the walk left unused (gate < 0 / vc = 0) writes zeros
+struct DdnDmrMsWalk {
+    const uint8_t* rec;
+    const int32_t *counts, *n_new, *sync_pos, *n_sync;
+    const uint8_t *sync_pat, *pre90;
+    size_t max_sym;
+    int n_channels, max_syncs, max_data, max_voice, max_lc;
+    void* state;
+    int32_t *n_data, *data_start, *data_pre, *data_gate;
+    uint8_t *data_pat, *data_slot, *data_status, *data_cc;
+    int32_t *n_voice, *voice_start, *voice_pre;
+    uint8_t *voice_vc, *voice_tact, *voice_emb_ok, *voice_emb_cc, *voice_power, *voice_sync48;
+    int32_t *n_lc, *lc_pos;
+    uint8_t* lc_in128;
+    int32_t *cc, *dropped, *phase;
+};
+size_t ddn_dev_dmr_ms_state_bytes(void);
+hipError_t ddn_dev_dmr_ms_state_init(void* state, int n_channels, hipStream_t st);
+hipError_t ddn_dev_dmr_ms_walk(const DdnDmrMsWalk* w, hipStream_t st);
+hipError_t ddn_dev_dmr_ms_data_gather(const uint8_t* rec, size_t max_sym, const int32_t* dstart, const int32_t* dpre, const int32_t* gate,
+                                      const uint8_t* pre90, const uint8_t* prel90, int max_data, int n_channels, uint8_t* slot_type,
+                                      uint8_t* info, uint8_t* td98, uint8_t* rel98, hipStream_t st);
+hipError_t ddn_dev_dmr_ms_voice_gather(const uint8_t* rec, size_t max_sym, const int32_t* vstart, const int32_t* vpre, const uint8_t* vc,
+                                       const uint8_t* pre90, int max_voice, int n_channels, uint8_t* dib108, uint8_t* skip3, hipStream_t st);
 // the DMR protocol layer behind the data bursts: resets / carrier loss between them, the walk to completed PDUs (ddn_dmr_pdu.hip)
 size_t ddn_dev_dmr_pdu_state_bytes(void);
 hipError_t ddn_dev_dmr_pdu_marks(const int32_t* events, const int32_t* n_events, int max_events, const uint8_t* flags, size_t stride,

@@ -601,6 +601,26 @@ typedef struct ddn_nxdn_ctrl_chain_results { /* device pointers valid until the 
 int ddn_fsk4_chain_set_nxdn_ctrl(ddn_fsk4_chain* c, int enable);
 int ddn_fsk4_chain_get_nxdn_ctrl_results(ddn_fsk4_chain* c, ddn_nxdn_ctrl_chain_results* out);
 
+/* ---- DMR MS / direct mode (protocol DDN_FSK4_DMR, handlers = 1, inverted = 0), opt-in: ddn_fsk4_chain_set_dmr_ms(c, 1) before the
+ * first run; handlers = 0, inverted = 1, a chain that has run or another protocol is DDN_EINVAL.  Until it is called the chain is
+ * what it was: nothing launched, nothing allocated, the loop's counts behind an MS / direct-mode word the defaults, and
+ * ddn_fsk4_chain_get_dmr_ms_results is DDN_EINVAL.  Enabling sets every channel's lock_symbols to {DDN_DMR_MS_LOCK_DATA,
+ * DDN_DMR_MS_LOCK_VOICE, 12, 0} (with the handlers on they serve the MS / direct-mode / RC words only: BS traffic decodes as before)
+ * and every call then runs ddn_dmr_ms_walk_batch -> _data_batch -> _voice_batch (include/ddn_fsk4.h: layouts, status bytes, the
+ * talk-path deviation) over the call's decode list, ahead of the BS stages.  The open voice unit, the embedded-signalling fragments,
+ * the colour code and - vocoder = 1 - one talk path per channel are carried across calls and through flush, so a unit may span any
+ * number of calls.  Entries: bursts.max_data / max_voice / max_lc per channel and call; a sync slot named by d_data_sync /
+ * d_voice_pre is a slot of ddn_fsk4_chain_results (d_sync_pos, d_pre).  voice.d_ambe_bits, d_ambe_result and d_pcm are NULL with
+ * vocoder = 0.  ddn_fsk4_chain_config and ddn_fsk4_chain_results keep their sizes.  The mixed chain has no such setter. */
+typedef struct ddn_dmr_ms_chain_results { /* device pointers valid until the next run */
+    size_t max_syncs;         /* slots per channel (= ddn_fsk4_chain_results.max_syncs) */
+    ddn_dmr_ms_bursts bursts; /* the walk's lists and the per-channel words */
+    ddn_dmr_ms_data data;     /* per data burst */
+    ddn_dmr_ms_voice voice;   /* per voice burst and per embedded link control */
+} ddn_dmr_ms_chain_results;
+int ddn_fsk4_chain_set_dmr_ms(ddn_fsk4_chain* c, int enable);
+int ddn_fsk4_chain_get_dmr_ms_results(ddn_fsk4_chain* c, ddn_dmr_ms_chain_results* out);
+
 /* ---- a mixed batch (BASELINE configs[3]): P25 Phase 1 + DMR + NXDN48 channel groups of one GPU, every receive loop with the
  * reference's handlers inside it; one stream per group inside the object, the groups' stages lined up (the three front ends, then the
  * three receive loops side by side), the frame FEC / voice stages on a fourth stream behind their loops so that the next call's

@@ -93,7 +93,8 @@ void ddn_fsk4_rx_destroy(ddn_fsk4_rx* b);
  * slicer words, histories and the handlers' words (DMR colour code 16, confidence cleared) start afresh. */
 int ddn_fsk4_rx_reset(ddn_fsk4_rx* b);
 /* enable != 0: the reference's own handlers decide how long a frame is read in frame (plain -fs / -fi, inverted = 0), inside the
- * loop - lock_symbols[] then only serves the sync types without a restated handler (DMR MS / direct mode words):
+ * loop - lock_symbols[] then only serves the DMR MS / direct-mode and RC words, which need no handler: dmrMSData() and dmrMS() read
+ * fixed counts (DDN_DMR_MS_LOCK_DATA / _VOICE below) and the stage behind the loop decodes them ("DMR MS / direct mode"):
  *   DMR BS data word   dmr_data_sync() (src/protocol/dmr/dmr_data.c:117-343): TACT Hamming(7,4) on the cached CACH (fails: no live
  *                      dibit), 5 live dibits, slot type Golay(20,8) (fails: stop) + colour-code gate, 49 more; then skipDibit(66)
  *   DMR BS voice word  dmrBSBootstrap() + dmrBS() (src/protocol/dmr/dmr_bs.c:697-948): 54 live dibits, then 144 per burst with the
@@ -535,6 +536,117 @@ int ddn_nxdn_ctrl_state_init(void* d_state, size_t n_channels, void* hip_stream)
 int ddn_nxdn_ctrl_decode_batch(const ddn_nxdn_ctrl_input* in, const ddn_nxdn_ctrl_frames* out, void* hip_stream);
 int ddn_nxdn_ctrl_walk_batch(const ddn_nxdn_ctrl_input* in, const ddn_nxdn_ctrl_frames* fr, void* d_state,
                              const ddn_nxdn_ctrl_messages* out, void* hip_stream);
+
+/* ---- DMR MS / direct mode: the bursts behind sync patterns 2..7 (ddn_dmr_ms.hip) ---------------------------------------------------
+ * What dmrMSData() and dmrMSBootstrap() + dmrMS() (src/protocol/dmr/dmr_ms.c:420-497, 384-417, 323-381) read behind an MS or
+ * direct-mode word at the default options (trunk_enable 0, dmr_stereo 1, inverted_dmr 0).  Both read fixed counts with no early
+ * exit - 264 symbols behind a data word (54 + 144 + 66), 1704 behind a voice word (54 + 144 + 9 x 144 + 210; the reference's own
+ * tests/protocol/dmr/test_dmr_ms_data.c holds 264, 1506, 1704 and 15 / 18 vocoder calls) - so the receive loop needs no handler:
+ * DDN_DMR_MS_LOCK_DATA / _VOICE as its lock_symbols[0] / [1] are all it takes.  p = row index of a sync's last symbol:
+ *   data word (patterns 2, 4, 5)   one burst: dibits 0..89 = the hand-over d_pre / d_pre_rel of the sync, 90..143 = records p + 1 ..
+ *     p + 54.  dmr_data_sync() (dmr_data.c:117-343) with dmr_stereo = 1, dmr_ms_mode = 1: TACT Hamming(7,4) (fails: status 1), slot
+ *     type Golay(20,8) (fails: status 2), no confidence gate, colour code from the slot type, slot 0 - 1 behind the direct-mode TS2
+ *     data word - then dmr_data_burst_handler(): the FEC-level results the BS data bursts have (ddn_chain.h, d_dmr_data_*).
+ *   voice word (patterns 3, 6, 7)  the bootstrap burst (VC 1) laid out the same way, then five bursts k = 0..4 (VC k + 2) of 144
+ *     records from p + 199 + 288 k.  Every burst: three AMBE 3600x2450 frames (dibits 12..47, 48..65 + 90..107, 108..143), its 48
+ *     sync-field bits; VC 2..6 file them as embedded signalling and try QR(16,7,6) on the EMB (good: colour code, power bit); at
+ *     VC 6 BPTC(128,77) runs over the fragments of VC 2..5 and the 5-bit checksum is checked.  d_voice_tact_ok is what
+ *     dmr_ms_decode_tact() computes - Hamming(7,4) over the first seven CACH dibits taken as bits - and the reference ignores.
+ * ddn_dmr_ms_walk_batch: one channel's decode list (the syncs whose 54 records are in the row) and the voice unit left open by the
+ * previous call (d_state: n_channels x ddn_dmr_ms_state_bytes(), started by ddn_dmr_ms_state_init - all zeros is NOT a start) -> the
+ * bursts that end in this call, in air order per list.  A data or bootstrap burst is listed in the call that lists its sync; a later
+ * burst of a unit in the call whose row (d_counts records) holds its last symbol - its first is at most 143 records back, so a
+ * carry of 144 records or more keeps it whole; a unit may span any number of calls.  d_new is how far the row moves on before the
+ * next call.  A burst that finds its list full is counted in d_dropped (running) and written nowhere; the unit goes on.
+ *   d_data_start / d_voice_start  row index of the burst's first CACH dibit; down to -89 for a data or bootstrap burst (those dibits
+ *                      are the hand-over), DDN_DMR_MS_UNUSED in an unused entry
+ *   d_data_sync / d_voice_pre     the sync slot (c * max_syncs + k) whose hand-over opens the burst; -1: a later burst of a unit
+ *   d_data_status      0 decoded, 1 TACT failed, 2 slot type failed (the rows of ddn_dmr_ms_data are zeros, d_type 0xFF); d_data_cc
+ *                      0xFF unless 0; d_data_gate 0 / -1 is the same verdict as ddn_dmr_ms_data_batch reads it
+ *   d_voice_vc         1 bootstrap, 2..6, 0 unused; d_voice_tact_ok / _emb_ok 0xFF for VC 1 (not decoded there), d_voice_emb_cc 0xFF
+ *                      and d_voice_power 9 where the EMB did not decode
+ *   d_lc_pos           row index of the VC 6 burst's last symbol, -1 unused; d_lc_in128 the 8 x 16 matrix (zeros where unused)
+ *   d_cc               the colour code carried per channel (16 until a slot type or an EMB decodes), d_phase the open unit's next
+ *                      burst k (5: none open)
+ * ddn_dmr_ms_data_batch: gather, Golay(20,8), BPTC(196,96), the data type's CRC / RS(12,9), the rate 3/4 decoders and pool - the
+ * BS data-burst stage's kernels on the walk's list.  ddn_dmr_ms_voice_batch: the frames, BPTC(128,77) + checksum per listed link
+ * control, and - mbe != NULL, an AMBE 3600x2450 batch of n_channels talk paths - frame FEC, skip marks and synthesis, 3 max_voice
+ * frames per path.  One talk path per channel (dmrMS() forces slot 0) whose history streams from call to call.
+ * Deviation: the reference keeps one mbe_parms set for slot 0, shared by the MS path and the BS slot-0 path of the same receiver;
+ * here the MS talk path is its own, so BS and MS traffic alternating on one channel do not see each other's vocoder history.
+ * Not here: message parsing, dmr_sbrc(), late-entry MI, the keystreams, -xr polarity, the reverse-channel word (pattern 8). */
+#define DDN_DMR_MS_LOCK_DATA 264
+#define DDN_DMR_MS_LOCK_VOICE 1704
+#define DDN_DMR_MS_UNUSED INT32_MIN
+typedef struct ddn_dmr_ms_input {
+    int n_channels;
+    size_t max_symbols;          /* row length of d_records10 in symbols */
+    size_t max_syncs;
+    const uint8_t* d_records10;  /* [n_channels][max_symbols][10] */
+    const int32_t* d_counts;     /* [n_channels] records held per row */
+    const int32_t* d_new;        /* [n_channels] records the row moves on by before the next call */
+    const int32_t* d_sync_pos;   /* [S] */
+    const uint8_t* d_sync_pat;   /* [S] */
+    const int32_t* d_n_sync;     /* [n_channels] */
+    const uint8_t* d_pre;        /* [S][DDN_FSK4_PRE] */
+    const uint8_t* d_pre_rel;    /* [S][DDN_FSK4_PRE] */
+} ddn_dmr_ms_input;
+typedef struct ddn_dmr_ms_bursts { /* the walk's lists: D = n_channels * max_data, V = n_channels * max_voice, L = n_channels * max_lc */
+    int max_data, max_voice, max_lc;
+    int32_t* d_n_data;         /* [n_channels] */
+    int32_t* d_data_start;     /* [D] */
+    int32_t* d_data_sync;      /* [D] */
+    int32_t* d_data_gate;      /* [D] */
+    uint8_t* d_data_pat;       /* [D] sync pattern */
+    uint8_t* d_data_slot;      /* [D] */
+    uint8_t* d_data_status;    /* [D] */
+    uint8_t* d_data_cc;        /* [D] */
+    int32_t* d_n_voice;        /* [n_channels] */
+    int32_t* d_voice_start;    /* [V] */
+    int32_t* d_voice_pre;      /* [V] */
+    uint8_t* d_voice_vc;       /* [V] */
+    uint8_t* d_voice_tact_ok;  /* [V] */
+    uint8_t* d_voice_emb_ok;   /* [V] */
+    uint8_t* d_voice_emb_cc;   /* [V] */
+    uint8_t* d_voice_power;    /* [V] */
+    uint8_t* d_voice_sync48;   /* [V][48] */
+    int32_t* d_n_lc;           /* [n_channels] */
+    int32_t* d_lc_pos;         /* [L] */
+    uint8_t* d_lc_in128;       /* [L][128] */
+    int32_t* d_cc;             /* [n_channels] */
+    int32_t* d_dropped;        /* [n_channels] */
+    int32_t* d_phase;          /* [n_channels] */
+} ddn_dmr_ms_bursts;
+typedef struct ddn_dmr_ms_data { /* per data burst, as ddn_fsk4_chain_results.d_dmr_data_* / d_dmr_r34_* */
+    uint8_t* d_type;               /* [D] 0xFF: not decoded */
+    uint8_t* d_info196;            /* [D][196] */
+    uint8_t* d_bits96;             /* [D][96] */
+    uint8_t* d_bytes12;            /* [D][12] */
+    uint32_t* d_errs;              /* [D] */
+    uint8_t* d_crc;                /* [D] */
+    uint8_t* d_r34_unconfirmed;    /* [D][18] */
+    uint8_t* d_r34_confirmed;      /* [D][18] */
+    uint8_t* d_r34_confirmed_crc;  /* [D] */
+    void* d_r34_pool;              /* [D][34] ddn_r34_candidate (include/ddn_hip.h) */
+    int32_t* d_r34_pool_n;         /* [D] */
+} ddn_dmr_ms_data;
+typedef struct ddn_dmr_ms_voice {
+    uint8_t* d_ambe_frames;   /* [V][3][4][24] */
+    uint8_t* d_skip;          /* [V][3] 0xFF: no burst in this entry */
+    uint8_t* d_lc77;          /* [L][77] */
+    uint32_t* d_lc_errs;      /* [L] */
+    uint8_t* d_lc_ok;         /* [L] the 5-bit checksum held */
+    /* with a vocoder batch: */
+    uint8_t* d_ambe_bits;     /* [V][3][49] */
+    int32_t* d_ambe_result;   /* [V][3][5] */
+    float* d_pcm;             /* [V][3][160] */
+} ddn_dmr_ms_voice;
+size_t ddn_dmr_ms_state_bytes(void);
+int ddn_dmr_ms_state_init(void* d_state, size_t n_channels, void* hip_stream);
+int ddn_dmr_ms_walk_batch(const ddn_dmr_ms_input* in, void* d_state, const ddn_dmr_ms_bursts* out, void* hip_stream);
+int ddn_dmr_ms_data_batch(const ddn_dmr_ms_input* in, const ddn_dmr_ms_bursts* bursts, const ddn_dmr_ms_data* out, void* hip_stream);
+int ddn_dmr_ms_voice_batch(const ddn_dmr_ms_input* in, const ddn_dmr_ms_bursts* bursts, const ddn_dmr_ms_voice* out, void* mbe_batch,
+                           void* hip_stream);
 #ifdef __cplusplus
 }
 #endif
