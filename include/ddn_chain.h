@@ -273,6 +273,8 @@ typedef struct ddn_p25p2_chain_results { /* device pointers, valid until the nex
 typedef struct ddn_p25p2_chain ddn_p25p2_chain;
 int ddn_p25p2_chain_create(const ddn_p25p2_chain_config* cfg, const uint64_t* seed44, ddn_p25p2_chain** out);
 void ddn_p25p2_chain_destroy(ddn_p25p2_chain* c);
+/* both wait for hip_stream on the host before they return their last work to it: the run inside ddn_p25p2_groups_batch (it reads its
+ * list lengths), the flush once more behind its decode */
 int ddn_p25p2_chain_run(ddn_p25p2_chain* c, const void* d_iq, void* hip_stream);
 int ddn_p25p2_chain_flush(ddn_p25p2_chain* c, void* hip_stream);
 int ddn_p25p2_chain_get_results(ddn_p25p2_chain* c, ddn_p25p2_chain_results* out);
@@ -433,8 +435,12 @@ typedef struct ddn_fsk4_chain_results { /* device pointers, S = n_channels * max
 typedef struct ddn_fsk4_chain ddn_fsk4_chain;
 int ddn_fsk4_chain_create(const ddn_fsk4_chain_config* cfg, ddn_fsk4_chain** out);
 void ddn_fsk4_chain_destroy(ddn_fsk4_chain* c);
+/* queued on hip_stream; no wait of its own in a call (the first one sizes the stages' buffers and waits for that).  Its decode stages
+ * take stream-ordered scratch: queued behind an unfinished call on the same stream it can be held up in the HIP runtime (include/
+ * ddn_hip.h, "Streams"); the same holds for the stages as separate calls below */
 int ddn_fsk4_chain_run(ddn_fsk4_chain* c, const void* d_iq, void* hip_stream);
-int ddn_fsk4_chain_flush(ddn_fsk4_chain* c, void* hip_stream); /* end of a stream: decode the syncs the carry still holds back */
+/* end of a stream: decode the syncs the carry still holds back; waits for hip_stream on the host (the results are there on return) */
+int ddn_fsk4_chain_flush(ddn_fsk4_chain* c, void* hip_stream);
 int ddn_fsk4_chain_stage(ddn_fsk4_chain* c, int stage, const void* d_iq, void* hip_stream); /* 0 front end, 1 loop, 2 frame FEC + voice */
 int ddn_fsk4_chain_get_results(ddn_fsk4_chain* c, ddn_fsk4_chain_results* out);
 void* ddn_fsk4_chain_front_end(ddn_fsk4_chain* c); /* ddn_batch* */

@@ -29,6 +29,15 @@
  * any number of objects in parallel.  The stateless ddn_fec_* / ddn_p25p1_* batch entry points take their scratch
  * from the stream (hipMallocAsync) and may be called concurrently from several host threads / streams.
  * ddn_last_error() is per thread.
+ *
+ * Streams: a call with a `hip_stream` parameter queues its work on that stream and returns; an object is used on one stream at a
+ * time.  Two kinds of call also wait for the stream on the host.  A run call of an object that keeps work buffers of the call's
+ * length (ddn_front_end_run with decimation passes or IQ conditioning, ddn_fm_audio_run, ddn_p25_rx_run and ddn_fsk4_rx_run with the
+ * matched filter, ddn_cqpsk_run, ddn_mbe_synth_batch) waits for hip_stream before it replaces such a buffer: on its first use and on
+ * every call longer than all before it, never otherwise.  ddn_p25p2_groups_batch waits once in every call (see there), and so do the
+ * chain calls built on it and the chains' flushes (include/ddn_chain.h).  A call that takes stream-ordered scratch (hipMallocAsync /
+ * hipFreeAsync) may also be held up inside the HIP runtime while earlier scratch-taking work on the same stream is unfinished; the
+ * results do not depend on it.
  */
 #ifndef DDN_HIP_H
 #define DDN_HIP_H
@@ -121,7 +130,8 @@ int ddn_batch_set_iq_conditioning(ddn_batch* b, int dc_block_enable, int dc_shif
  *            per sample, widened as (float)s * (1.0f / 32768.0f), src/io/radio/rtl_device.cpp:1247-1264; d_iq 4-byte aligned)
  *   d_disc : [B][n] float discriminator samples (AGC'd to +-30000, clipped to int16 range)
  * The call is equivalent to ceil(n / block_len) consecutive full_demod() calls per channel; carried state
- * persists in `b` across calls.  Asynchronous on `hip_stream` (NULL = default stream). */
+ * persists in `b` across calls.  Asynchronous on `hip_stream` (NULL = default stream), but for a call that grows a work buffer
+ * ("Streams" above). */
 int ddn_front_end_run(ddn_batch* b, const void* d_iq, size_t n, float* d_disc, void* hip_stream);
 /* same, host buffers (H2D, run, D2H, synchronous) */
 int ddn_front_end_run_host(ddn_batch* b, const void* h_iq, size_t n, float* h_disc);
@@ -184,7 +194,8 @@ int ddn_batch_set_audio_monitor(ddn_batch* b, const ddn_fm_audio_config* cfg);
 /* the most samples per channel a call of n input samples can produce, whatever the carried phases (a row's capacity) */
 size_t ddn_fm_audio_max_samples(const ddn_batch* b, size_t n);
 /* d_iq [B][n] as for ddn_front_end_run (n a multiple of 2^passes); d_audio [B][audio_stride] floats, the first *out_count of each row
- * written, audio_stride >= the call's count (DDN_ERANGE otherwise, before anything runs).  Asynchronous on hip_stream. */
+ * written, audio_stride >= the call's count (DDN_ERANGE otherwise, before anything runs).  Asynchronous on hip_stream, but for
+ * a call that grows a work buffer ("Streams" above). */
 int ddn_fm_audio_run(ddn_batch* b, const void* d_iq, size_t n, float* d_audio, size_t audio_stride, size_t* out_count, void* hip_stream);
 /* same, host buffers (H2D, run, D2H, synchronous) */
 int ddn_fm_audio_host_run(ddn_batch* b, const void* h_iq, size_t n, float* h_audio, size_t audio_stride, size_t* out_count);

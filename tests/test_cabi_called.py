@@ -24,14 +24,9 @@ _HOST = ("ddn_fec_viterbi_k5", "ddn_fec_p25_lsd", "ddn_fec_rs28", "ddn_audio_s16
          "ddn_p25p2_ess", "ddn_p25p2_burst_fields")
 REACHED_THROUGH = {name + "_batch": name + "_host" for name in _HOST}
 REACHED_THROUGH.update({
-    "ddn_p25_slicer_run": "ddn_p25_slicer_run_host",
-    "ddn_p25_matched_filter_run": "ddn_p25_matched_filter_run_host",
-    "ddn_resampler_run": "ddn_resampler_run_host",
     "ddn_fsk4_rx_set_events": "ddn_fsk4_rx_events_host_arm",          # arms the object's own buffers through the setter
     "ddn_fec_bptc_128x77_batch": "ddn_fsk4_chain_run",                # the DMR section's embedded-signalling stage
-    "ddn_fsk4_chain_stage": "ddn_fsk4_chain_run",                     # run = front end, then this
     "ddn_p25_rx_set_event_data": "ddn_p25_chain_run",                 # the chain's loop stage points the loop at its payload rows
-    "ddn_p25p1_framer_gather_lsd": "ddn_p25_chain_run",               # the chain's decode stage
     "ddn_p25p1_framer_device_dropped": "ddn_p25_chain_get_results",
     "ddn_p25p1_framer_device_syncs": "ddn_p25_chain_get_results",
     "ddn_p25_chain_set_first_channel": "ddn_node_create",             # every part's talk paths are numbered by its first channel
